@@ -2,6 +2,7 @@
 """Benchmark of the FTLE hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5] [--scaling weak|strong]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the whole hot path over one batch of synthetic input: pack the wind series into the
 gather image, advect every seed through all time levels (fused kernel), exchange the 2-row halo (N>1), compute
@@ -15,6 +16,11 @@ Workloads (BASELINE.json configs; all float32, SETTLS_order K=4, interp_order 1,
   c5: 64 start times x 2048^2 seeds x 200 steps on a 264-level series, members sharded over N ranks, no exchange.
   c2: BASELINE configs[1], 1024^2 field nodes = seeds, moving ideal vortex, 200 steps, float64, N=1 only.
 
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: `value`, `ms_per_step` (wall
+time of one timed step) and the event times of those steps (`kernel_ms`, `roofline`).  --full adds what takes runs or
+measurements of its own: the CPU baseline, the device copy peak and, in the default one-GPU c3 run, the non-headline
+workloads under "secondary" and the live rocprofv3 child passes described below.
+
 Prints ONE JSON line on rank 0.  `roofline` describes the dominant kernel (the fused advection):
   bound     the unit that limits it.  The advect kernels are bound by the vector ALU's instruction throughput
             (time follows the VALU cycle count when instructions are removed; tools/ubench_valu.hip, DESIGN.md
@@ -24,7 +30,7 @@ Prints ONE JSON line on rank 0.  `roofline` describes the dominant kernel (the f
   algorithmic_GBps   SURVEY 8d's byte figure B_adv(K, order) x particle-timesteps / that duration (it charges every
             cache-served tap to memory, so it may exceed the HBM peak; kept for cross-round comparison only).
   hbm       compulsory bytes (every image level + seeds + outputs once), their rate as a fraction of the 8 TB/s peak,
-            and the measured traffic per launch and its fraction: in the default one-GPU run MEASURED BY THIS RUN (two
+            and the measured traffic per launch and its fraction: in the --full one-GPU c3 run MEASURED BY THIS RUN (two
             counter-only child passes of this command under rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE after the timed
             region, live_traffic()); otherwise replayed from a committed rocprofv3 --pmc summary collected on exactly
             this csrc/ (hash-stamped) for this workload, or null.
@@ -520,12 +526,50 @@ def watchdog(seconds: float, what: str, rank: int):
     return t
 
 
-def timed_case(torch, eng, prepare, advect, sigma, steps, warmup, pack_and_advect=None):
+DUMP_BUDGET_BYTES = 60_000_000     # --dump-outputs: every file of one call together (headers included) stays under 64 MB
+DUMP_SAMPLE_SEED = 20260355
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES, suffix=""):
+    """--dump-outputs: write `arrays` ({name: tensor, or a list of equally shaped tensors standing for their stack}) as
+    `out_dir/<name><suffix>.npy` in their own dtype (float32 / float64).  An array that does not fit in its share of `budget`
+    is written as a fixed sample: the elements at `n` flat indices of the (stacked) array drawn without replacement by
+    numpy's default_rng(DUMP_SAMPLE_SEED) and sorted, `n` = its share / element size -- the same indices for the same shape
+    in every run, so two builds can be compared output for output.  Returns {name: [full shape, elements written]}."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // max(len(arrays), 1) - 4096                     # (4096: room for the .npy header)
+    out, picks = {}, {}
+    for name, parts in arrays.items():
+        parts = list(parts) if isinstance(parts, (list, tuple)) else [parts]
+        shape = ([len(parts)] if len(parts) > 1 else []) + list(parts[0].shape)
+        n_part = parts[0].numel()
+        total = n_part * len(parts)
+        n = min(total, share // parts[0].element_size())
+        if n == total:
+            host = np.concatenate([p.detach().reshape(-1).cpu().numpy() for p in parts]).reshape(shape)
+        else:
+            if (total, n) not in picks:
+                picks[total, n] = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(total, n, replace=False))
+            idx = picks[total, n]
+            host = np.empty(n, dtype={torch.float32: np.float32, torch.float64: np.float64}[parts[0].dtype])
+            cut = np.searchsorted(idx, np.arange(len(parts) + 1) * n_part)
+            for i, p in enumerate(parts):
+                sel = torch.as_tensor(idx[cut[i]:cut[i + 1]] - i * n_part, device=p.device)
+                host[cut[i]:cut[i + 1]] = p.detach().reshape(-1)[sel].cpu().numpy()
+        assert host.dtype in (np.float32, np.float64), (name, host.dtype)
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), host)
+        out[name] = [shape, int(host.size)]
+    return out
+
+
+def timed_case(torch, eng, prepare, advect, sigma, steps, warmup, pack_and_advect=None, last=None):
     """`steps` passes of pack -> advect -> sigma (after `warmup` untimed ones): wall time per step and the mean HIP-event
     time of each stage on the launch stream.  `pack_and_advect` (Engine.pack_and_advect where its pipelined form is the
     default: chunk k+1 packed on a side stream while chunk k is advected): the TIMED passes run that one call instead of
     prepare + advect, `pack_advect_overlapped` is its event time, and the stage times `pack` / `advect` come from serial
-    passes (prepare, advect one after the other) run after the timed region -- they overlap in the timed passes."""
+    passes (prepare, advect one after the other) run after the timed region -- they overlap in the timed passes.
+    `last` (a dict): receives the last timed pass's results as sigma, x_dep and y_dep."""
     def one(serial):
         m = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         m[0].record()
@@ -539,19 +583,21 @@ def timed_case(torch, eng, prepare, advect, sigma, steps, warmup, pack_and_advec
         m[2].record()
         s = sigma(r)
         m[3].record()
-        return s, m
+        return s, m, r
     for _ in range(warmup):
         one(False)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     marks = []
     for _ in range(steps):
-        s, m = one(False)
+        s, m, r = one(False)
         marks.append(m)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     ms = {k: float(np.mean([m[i].elapsed_time(m[i + 1]) for m in marks])) for i, k in enumerate(("pack", "advect", "sigma"))}
     assert bool(torch.isfinite(s).all()), "non-finite sigma in a benchmark case"
+    if last is not None:
+        last.update(sigma=s, x_dep=r[0], y_dep=r[1])
     if pack_and_advect is not None:
         ms["pack_advect_overlapped"] = ms["advect"]
         one(True)
@@ -801,13 +847,14 @@ def run_c2(args, torch, flows, Engine, local_rank, csrc):
     if os.environ.get("LCS_PIPELINE"):                      # A/B: force the pipelined form on (1) or off (0), LCS_PIPELINE_CHUNK levels
         piped = os.environ["LCS_PIPELINE"] != "0" and bool(args.fuse_levels)
     pchunk = int(os.environ["LCS_PIPELINE_CHUNK"]) if os.environ.get("LCS_PIPELINE_CHUNK") else None
+    last = {}
     per_step, ms = timed_case(
         torch, eng, lambda: eng.prepare_field(ud, vd, lat, lon, order, fuse_levels=args.fuse_levels, ext_image=ext_image),
         lambda f: eng.advect(f, lat_d, lon_d, -900.0, K, order, True), lambda r: eng.sigma(r[0], r[1], lat_d, dlat, dlon),
         args.steps, args.warmup,
         (lambda: eng.pack_and_advect(ud, vd, lat, lon, lat_d, lon_d, -900.0, K, order, True, fuse_levels=args.fuse_levels,
                                      pipeline=True, chunk=pchunk, ext_image=ext_image)[1:])
-        if piped else None)
+        if piped else None, last=last)
     el = per_step * args.steps
     pts = ny * nx * (nt - 1)
     wl = {"workload": "c2", "order": order, "K": K, "dtype": "f64", "fuse_levels": bool(args.fuse_levels)}
@@ -831,8 +878,10 @@ def run_c2(args, torch, flows, Engine, local_rank, csrc):
         "roofline": roofline(eng.last_advect_kernel(), "valu" if "lds" in eng.last_advect_kernel() else "tcp", pts, ms["advect"], K, order, 8, 8,
                              bool(args.fuse_levels), comp, wl, csrc, eng.last_advect_launches()),
     }
-    del ud, vd
-    if not args.no_cpu_baseline:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
+    del ud, vd, last
+    if args.full and not args.no_cpu_baseline:
         from oracle import lcs_oracle as O
         us, vs, la, lo = flows.config2(n=256, nt=21)
         c0 = time.perf_counter()
@@ -931,21 +980,29 @@ def main():
     ap.add_argument("--nt", type=int, default=None, help="time levels (default 97 / 385 / 264 for c3 / c4 / c5)")
     ap.add_argument("--settls", type=int, default=4)
     ap.add_argument("--order", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: the CPU baseline, the device copy peak, "
+                         "and in the default one-GPU c3 run the secondary workloads and the live rocprofv3 child passes.  Without "
+                         "it the run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (sigma, x_dep, y_dep; the trajectories with "
+                         "--traj) as DIR/<name>.npy, under 64 MB in all: an array too large for its share as a fixed, seeded "
+                         "sample of its elements (dump_outputs()); a rank of an N-GPU run writes its own rows as <name>_rank<r>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="c2 only: pack the whole series, then advect (the default everywhere since round 5; LCS_PIPELINE=1 forces "
                          "the form that packs chunk k+1 on a side stream while chunk k is advected)")
     ap.add_argument("--no-live-counters", action="store_true",
-                    help="do not run the two rocprofv3 --pmc child passes that measure roofline.traffic in the default "
+                    help="do not run the two rocprofv3 --pmc child passes that measure roofline.traffic in the --full "
                          "one-GPU c3 run (the hash-stamped summaries under profiles/ are replayed instead; also skipped with "
                          "--no-secondary / --no-cpu-baseline and when the run is itself under rocprofv3)")
     ap.add_argument("--save-profiles", default=None, metavar="DIR",
-                    help="default one-GPU c3 run: also write what the live profiler passes measured -- the kernel-trace "
+                    help="--full one-GPU c3 run: also write what the live profiler passes measured -- the kernel-trace "
                          "statistics, the traffic and SQ / TCP counter summaries (the format profiles/*/c3_o1_* has, stamped "
                          "with the library's build id) and the line itself -- into DIR: profiles/rNN/ regenerated by the run "
                          "that produced the number")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the non-headline workloads the default one-GPU c3 run appends under \"secondary\"")
+                    help="skip the non-headline workloads the --full one-GPU c3 run appends under \"secondary\"")
     ap.add_argument("--traj", action="store_true",
                     help="return_traj=True: also store the positions after every step (not the headline)")
     ap.add_argument("--wind-scale", type=float, default=1.0,
@@ -964,6 +1021,10 @@ def main():
                          "promotion through LCS/trajectory.py:86-87,110-112, SURVEY Q10 -- LC_F64_WIND_F32)")
     args = ap.parse_args()
     args.fuse_levels = not args.exact_order
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
+    if args.save_profiles and not args.full:
+        raise SystemExit("--save-profiles writes what the live profiler passes of a --full run measured: add --full")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # not a rank yet: start the ranks as fresh children BEFORE anything here touches the GPU (spawn_ranks above)
@@ -1145,10 +1206,11 @@ def main():
         sig = eng.sigma(x_ext, y_ext, slat_d[in_row0:in_row0 + x_ext.shape[0]], dlat, dlon, ny_global=ny_global,
                         in_row0=in_row0, out_row0=lo, n_out_rows=hi - lo)
         marks[3].record()
-        return (sig, x_ext, y_ext), marks
+        return (sig, x_ext, y_ext, *res[2:]), marks          # (--traj: the trajectories after them)
 
     last = {}   # outputs of the most recent step (for the checks after the timed region); cleared before the
                 # next step allocates, so that steps reuse one set of device buffers instead of ping-ponging two
+    every = bool(args.dump_outputs)   # --dump-outputs: last["members"] keeps every member's results, not only the last one's
     # c5: independent members alternate between two HIP streams, so one member's last workgroups (the tail of its
     # launch) run beside the next member's first ones.  The events bracket each member on its own stream.
     nstreams = max(1, int(os.environ.get("LCS_MEMBER_STREAMS", "2"))) if wk == "c5" else 1
@@ -1174,14 +1236,17 @@ def main():
             pos = sharded.ensemble_advect(eng, field, slat_d, slon_d, dt, members, nsteps, K, order, True, ens_chunk, nstreams)
             m[1].record()          # (ensemble_advect has joined its streams into the current one)
             m[2].record()
-            sig = None
+            sig, kept = None, []
             for x, y in pos:
                 sig = eng.sigma(x, y, slat_d, dlat, dlon)
+                if every:
+                    kept.append((sig, x, y))
             m[3].record()
             if record:
                 ev_marks.append((pack, [m]))
-            last.update(sig=sig, x_ext=pos[-1][0], y_ext=pos[-1][1], field=field)
+            last.update(sig=sig, x_ext=pos[-1][0], y_ext=pos[-1][1], field=field, members=kept)
             return
+        kept = []
         with eng.concurrent_calls((hi - lo) * nx, max(len(side), 1)):   # the kernel choice sees the seeds in flight
             for i, e in enumerate(members):
                 if side:
@@ -1194,11 +1259,14 @@ def main():
                 else:
                     res, m = member_pass(field, e if wk == "c5" else 0)
                 mm.append(m)
+                if every:
+                    kept.append(res)
         for st in side:
             cur.wait_stream(st)
         if record:
             ev_marks.append((pack, mm))
-        last.update(sig=res[0] if res else None, x_ext=res[1] if res else None, y_ext=res[2] if res else None, field=field)
+        last.update(sig=res[0] if res else None, x_ext=res[1] if res else None, y_ext=res[2] if res else None, field=field,
+                    members=kept)
 
     for _ in range(args.warmup):
         one_step(False)
@@ -1243,6 +1311,24 @@ def main():
         assert bool(torch.isfinite(sig).all()), "non-finite sigma in the benchmark output"
     advect_kernel = eng.last_advect_kernel()
     pack_kernel = eng.last_pack_kernel()
+
+    # ---- --dump-outputs: what the last timed step computed, the rows a caller of this rank's path receives ----
+    if args.dump_outputs:
+        def own(t):                     # x / y of the rank's own rows (a block or window also holds its neighbours' rows)
+            if not chunks:
+                return t[n_lo:n_lo + hi - lo]
+            parts, off = [], 0
+            for c_lo, c_hi in chunks:
+                a, b = sharded.chunk_window(ny_global, c_lo, c_hi)
+                parts.append(t[off + c_lo - a:off + c_hi - a])
+                off += b - a
+            return torch.cat(parts)
+        kept = last["members"]
+        arrays = {"sigma": [r[0] for r in kept], "x_dep": [own(r[1]) for r in kept], "y_dep": [own(r[2]) for r in kept]}
+        if len(kept[0]) > 3:            # --traj (where the path returns them)
+            arrays.update(traj_x=[r[3] for r in kept], traj_y=[r[4] for r in kept])
+        dump_outputs(args.dump_outputs, arrays, budget=DUMP_BUDGET_BYTES // world, suffix=f"_rank{rank}" if world > 1 else "")
+        del kept, arrays
 
     # ---- halo check (outside the timed region): the rows received must equal, bit for bit, the same rows
     # advected redundantly by this rank (LCS_NATIVE_HALO=1 times and checks the C ABI's lc_halo_exchange instead)
@@ -1336,7 +1422,7 @@ def main():
     n_mem_global = args.members if wk == "c5" else 1
     pts_per_step = n_mem_global * ny_global * nx * nsteps
     value = pts_per_step * args.steps / elapsed
-    copy_gbps = measured_copy_peak(torch)                                       # after the timed region
+    copy_gbps = measured_copy_peak(torch) if args.full else None                # after the timed region
     sig_s = ms["sigma"] / n_launch / 1e3
     sigma_gbps = (hi - lo) * nx * 3 * s_p / sig_s / 1e9
     # compulsory HBM bytes of one launch: the nsteps+1 levels of img it reads, the nsteps of ext, seeds, outputs
@@ -1397,7 +1483,7 @@ def main():
                      "measured_copy_peak_GBps": copy_gbps},
         "roofline_sigma": {
             "bound": "hbm", "kernel": eng.last_sigma_kernel(), "achieved": sigma_gbps, "peak": HBM_PEAK_GBPS,
-            "unit": "GB/s", "frac": sigma_gbps / HBM_PEAK_GBPS, "frac_of_measured_copy_peak": sigma_gbps / copy_gbps,
+            "unit": "GB/s", "frac": sigma_gbps / HBM_PEAK_GBPS, "frac_of_measured_copy_peak": sigma_gbps / copy_gbps if copy_gbps else None,
             "algorithmic_bytes_per_cell": 3 * s_p,
             **(lambda st: {"traffic": st.get("traffic"), "traffic_source": st.get("traffic_source"),
                            "hbm_traffic_frac": (st["traffic"] / sig_s / 1e9 / HBM_PEAK_GBPS) if st.get("traffic") else None})(
@@ -1414,9 +1500,9 @@ def main():
         out["halo_ms"] = ms["halo"]
         out["per_rank"] = per_rank
 
-    # ---- the non-headline workloads, a few steps each, after the headline's timed region (default one-GPU run only) ----
+    # ---- the non-headline workloads, a few steps each, after the headline's timed region (--full one-GPU run only) ----
     plain = (wk == "c3" and world == 1 and std and order == 1 and K == 4 and not args.traj and args.wind_scale == 1.0 and not knobs)
-    if plain and not args.no_secondary:
+    if args.full and plain and not args.no_secondary:
         last.clear()
         del sig, x_ext, y_ext, field          # the headline's outputs: the secondary cases reuse the memory
         torch.cuda.empty_cache()
@@ -1434,10 +1520,10 @@ def main():
             out["secondary"]["c1 through the drop-in"] = config1_dropin(flows, not args.no_cpu_baseline)
         except Exception as exc:
             out["secondary"]["c1 through the drop-in"] = {"error": f"{type(exc).__name__}: {exc}"[:300]}
-    # ---- roofline.traffic measured by this run (default one-GPU run only): two counter-only child passes of this command ----
+    # ---- roofline.traffic measured by this run (--full one-GPU run only): two counter-only child passes of this command ----
     profiled = any(k.startswith(("ROCPROF", "ROCP_TOOL")) for k in os.environ)      # this run is itself under rocprofv3
     to_save = None
-    if plain and not (args.no_live_counters or args.no_secondary or args.no_cpu_baseline or profiled):
+    if args.full and plain and not (args.no_live_counters or args.no_secondary or args.no_cpu_baseline or profiled):
         sk = out["roofline_sigma"]["kernel"]        # (the headline's: the secondary cases have launched others since)
         torch.cuda.empty_cache()
         t_live = time.time()
@@ -1512,7 +1598,7 @@ def main():
         if args.save_profiles:
             to_save = (kt, live, lu, sk)
     # ---- CPU baseline: the oracle (numpy+scipy port) on a bounded sample, rank 0, N=1 only ----
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(flows, u, v, lat, lon, dt, K, order, nsteps)
     if to_save is not None:
         save_profiles(args.save_profiles, out, wl, build_id, to_save[0], to_save[1], to_save[2], advect_kernel, to_save[3])

@@ -1,5 +1,5 @@
-"""bench.py prints exactly one JSON line carrying the driver's contract fields plus `roofline` and
-`cpu_baseline` (miniature workloads here; the headline sizes are bench.py's defaults)."""
+"""bench.py prints exactly one JSON line carrying the driver's contract fields plus `roofline` (and, with --full,
+`cpu_baseline`) (miniature workloads here; the headline sizes are bench.py's defaults)."""
 import json
 import os
 import subprocess
@@ -21,7 +21,7 @@ def _bench(*args, env=None, launcher=()):
 
 
 def test_bench_prints_one_json_line_with_the_contract_fields():
-    d = _bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--seeds", "256", "--nt", "5")
+    d = _bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--seeds", "256", "--nt", "5", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -45,6 +45,66 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     assert cb["kind"] == "port" and cb["cores"] == 1 and cb["value"] > 0 and "sample" in cb
     # value = seeds x steps-per-pass x passes / wall time
     assert abs(d["value"] - 256 * 256 * 4 * 2 / (d["ms_per_step"] * 2 / 1e3)) / d["value"] < 1e-6
+
+
+def test_plain_bench_run_times_its_steps_and_nothing_else():
+    """Without --full the line carries the headline figure and the event times of the timed steps; the CPU baseline,
+    the copy peak and the secondary workloads are --full's."""
+    d = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--seeds", "256", "--nt", "5")
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert abs(d["value"] - 256 * 256 * 4 * 3 / (d["ms_per_step"] * 3 / 1e3)) / d["value"] < 1e-6
+    assert "cpu_baseline" not in d and "secondary" not in d and "kernel_ms_rocprof" not in d
+    assert d["roofline"]["measured_copy_peak_GBps"] is None and d["roofline"]["kernel"] == "advect_lds_kernel<1, 4, true>"
+    assert set(d["kernel_ms"]) == {"pack", "advect", "halo", "sigma"} and d["kernel_ms"]["advect"] > 0
+
+
+def _npys(d):
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d)) if f.endswith(".npy")}
+
+
+def test_bench_dump_outputs_are_the_last_steps_results(tmp_path):
+    """--dump-outputs writes sigma, x_dep and y_dep of the last timed step; the same arguments give the same inputs, so two
+    runs write the same arrays; a two-rank run writes each rank's own rows, which together are the one-GPU result."""
+    import numpy as np
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    small = ["--seeds", "256", "--nt", "5"]
+    _bench("--steps", "2", "--warmup", "1", *small, "--dump-outputs", a)
+    _bench("--steps", "1", "--warmup", "0", *small, "--dump-outputs", b)
+    da, db = _npys(a), _npys(b)
+    assert sorted(da) == ["sigma", "x_dep", "y_dep"] == sorted(db)
+    for k, v in da.items():
+        assert v.dtype == np.float32 and v.shape == (256, 256) and np.isfinite(v).all(), k
+        assert np.array_equal(v, db[k]), k
+    assert sum(os.path.getsize(os.path.join(a, f)) for f in os.listdir(a)) < 64e6
+    assert np.abs(da["y_dep"]).max() <= 90                            # departure latitudes, in degrees
+    # two ranks (gloo rehearsal, both on GPU 0), the same 256^2 grid split between them: each writes its own rows
+    c = str(tmp_path / "c")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(LCS_BENCH_BACKEND="gloo", LCS_BENCH_ONE_GPU="1")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
+                        "--scaling", "strong", *small, "--dump-outputs", c], capture_output=True, text=True, timeout=900,
+                       cwd=ROOT, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    dc = _npys(c)
+    assert sorted(dc) == ["sigma_rank0", "sigma_rank1", "x_dep_rank0", "x_dep_rank1", "y_dep_rank0", "y_dep_rank1"]
+    for k in ("sigma", "x_dep", "y_dep"):
+        assert np.array_equal(np.concatenate([dc[k + "_rank0"], dc[k + "_rank1"]]), da[k]), k
+
+
+def test_bench_dump_outputs_of_the_ensemble_and_float64_workloads(tmp_path):
+    """c5: every member's results, stacked in member order; c2: float64."""
+    import numpy as np
+    _bench("--workload", "c5", "--steps", "1", "--warmup", "1", "--seeds", "256", "--nt", "14", "--members", "4",
+           "--dump-outputs", str(tmp_path / "c5"))
+    d = _npys(str(tmp_path / "c5"))
+    assert sorted(d) == ["sigma", "x_dep", "y_dep"]
+    assert all(v.shape == (4, 256, 256) and v.dtype == np.float32 and np.isfinite(v).all() for v in d.values())
+    assert not np.array_equal(d["x_dep"][0], d["x_dep"][3])          # members start at different levels
+    _bench("--workload", "c2", "--steps", "1", "--warmup", "1", "--dump-outputs", str(tmp_path / "c2"))
+    d = _npys(str(tmp_path / "c2"))
+    assert sorted(d) == ["sigma", "x_dep", "y_dep"]
+    assert all(v.shape == (1024, 1024) and v.dtype == np.float64 and np.isfinite(v).all() for v in d.values())
 
 
 def test_bench_direct_kernel_is_named_as_such():
