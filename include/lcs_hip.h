@@ -38,7 +38,7 @@ extern "C" {
  * client built against 100 must be rebuilt), lc_ctx_get_level_chunk, lc_ctx_set/get_f64_fidelity, lc_advect_ex and
  * lc_sample_raw added, lc_field_pack accepts packed_dev == NULL at order 1 (fused-level image only).  lc_version() returns the value the LIBRARY
  * was built with: compare it with this macro before any other call (tests/c/abi_smoke.c, _capi.load do). */
-#define LC_VERSION 104 /* 0.1.4: + lc_ctx_set_host_pipeline, lc_copy_to_device, lc_copy_to_host, lc_ctx_set_host_cache, lc_ctx_trim, lc_ctx_last_host_marks, lc_ctx_set_xcd_split (0.1.3: + lc_ctx_last_pack_kernel; 0.1.2: + lc_ctx_set_verify, lc_ctx_read_verify, LC_F64_WIND_F32_LIN32) */
+#define LC_VERSION 104 /* 0.1.4: + lc_tracer_sample, lc_ctx_last_tracer_kernel (additive: no argument list changed), + lc_ctx_set_host_pipeline, lc_copy_to_device, lc_copy_to_host, lc_ctx_set_host_cache, lc_ctx_trim, lc_ctx_last_host_marks, lc_ctx_set_xcd_split (0.1.3: + lc_ctx_last_pack_kernel; 0.1.2: + lc_ctx_set_verify, lc_ctx_read_verify, LC_F64_WIND_F32_LIN32) */
 
 typedef struct lc_ctx lc_ctx;
 
@@ -216,6 +216,9 @@ const char *lc_ctx_last_sigma_kernel(const lc_ctx *ctx);
  * nodes or more: both prefilter sweeps in one pass), "prefilter_cols_stream_kernel + prefilter_rows_stream_kernel".  The pads
  * / fused-level pass that follows is not named.  Same lifetime as lc_ctx_last_advect_kernel's string. */
 const char *lc_ctx_last_pack_kernel(const lc_ctx *ctx);
+/* The kernel the context's last lc_tracer_sample launched ("" before any): "tracer_kernel<float | double, interp_order>".
+ * Same lifetime as lc_ctx_last_advect_kernel's string. */
+const char *lc_ctx_last_tracer_kernel(const lc_ctx *ctx);
 /* Wave-state audit (diagnostic; no reference counterpart).  mode 1: float32 lc_advect calls that dispatch to the one-seed
  * LDS-tile kernels (orders 1 and 3 below 2^23 seeds per call, SETTLS_order > 0, no whole-line trajectory stores) run their "verify" instances:
  * after the iterations of every time level each wave reads back the tile of the wind image it staged in LDS for that
@@ -441,6 +444,40 @@ int lc_sample_raw(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, c
                   double lat_min, double lat_max, double lon_min, double lon_max, int level,
                   const void *pos_x_dev, const void *pos_y_dev, int ny, int nx,
                   int row0, int ny_global, int interp_order, void *out_u, void *out_v);
+
+/* ---- scalar tracers along trajectories --------------------------------------
+ * The C= argument the reference's research driver hands parcel_propagation (LCS/area_of_influence.py:314-321; the
+ * dead flag tracer_account of LCS/trajectory.py:45): a tracer C [nt][ny_f][nx_f] on the wind's grid and time levels,
+ * sampled at the parcel positions.  Trajectory entry j is sampled at field level level0 + j with lc_sample's rule
+ * (tools.xr_map_coordinates at interp_order: Q2 index scale, 'wrap' on interior rows, order 1 + 'constant' on the first /
+ * last interp_order GLOBAL seed rows, row0 / ny_global as in lc_advect).
+ *   tracer_lin, tracer_cub, c1_raw, c2_raw   the (C1, C2) tracer images / planes, exactly as lc_sample_raw takes the (u, v)
+ *                ones: lc_field_pack(C1, C2) with the tracers in the (u, v) slots; one tracer is packed as (C, C) with
+ *                c2_out / sum2 / mean2_out NULL.  Order 1 needs tracer_lin (LC_F32) or the raw planes (LC_F64); orders
+ *                2..5 need tracer_cub of that order and an order-1 source for the pole rows (tracer_lin or the planes).
+ *   traj_x, traj_y   [n_levels][ny*nx] positions in degrees (dtype elements, device): lc_advect's traj_x / traj_y, or a
+ *                range of entries of them.
+ *   c1_out, c2_out   NULL or [n_levels][ny*nx] dtype: the sampled values.
+ *   sum1, sum2   NULL or [ny*nx] float64, device: the entries' values are ADDED in level order (float64 for both dtypes),
+ *                so a series sampled in consecutive ranges carries its sums from call to call.
+ *   mean1_out, mean2_out   NULL or [ny*nx] dtype: (dtype)(sum / mean_count) after this range, sum including what sum1 /
+ *                sum2 held on entry -- the reference driver's cs.mean('time') over entries 0..nsteps is mean_count =
+ *                nsteps + 1 (equal up to summation order).
+ * NaN in the tracer is not specified: the sampled value is whatever the interpolation makes of it. */
+typedef struct lc_tracer_args {
+    size_t struct_size;                                       /* sizeof(lc_tracer_args) as the caller compiled it */
+    const void *tracer_lin, *tracer_cub, *c1_raw, *c2_raw;
+    int dtype, nt, ny_f, nx_f;                                /* dtype: LC_F32 or LC_F64 (tracer, positions, outputs) */
+    double lat_min, lat_max, lon_min, lon_max;
+    int ny, nx, row0, ny_global, interp_order;
+    const void *traj_x, *traj_y;
+    int level0, n_levels;                                     /* entry j is sampled at field level level0 + j (< nt) */
+    void *c1_out, *c2_out;
+    double *sum1, *sum2;
+    void *mean1_out, *mean2_out;
+    int mean_count;
+} lc_tracer_args;
+int lc_tracer_sample(lc_ctx *ctx, const lc_tracer_args *args);
 
 /* ---- K3: flow-map gradient + largest singular value ------------------------
  * Replaces LCS.flowmap_gradient (LCS/LCS.py:171-225), tools.derivative_spherical_coords

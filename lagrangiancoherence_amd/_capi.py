@@ -50,6 +50,7 @@ PROTOTYPES = {
     "lc_ctx_last_advect_launches": (_i, [_vp]),
     "lc_ctx_last_sigma_kernel": (C.c_char_p, [_vp]),
     "lc_ctx_last_pack_kernel": (C.c_char_p, [_vp]),
+    "lc_ctx_last_tracer_kernel": (C.c_char_p, [_vp]),
     "lc_ctx_set_verify": (_i, [_vp, _i]),
     "lc_ctx_read_verify": (_i, [_vp, C.POINTER(C.c_uint), _i]),
     "lc_malloc": (_i, [_vp, _sz, C.POINTER(_vp)]),
@@ -108,6 +109,24 @@ class AdvectArgs(C.Structure):
 
 
 PROTOTYPES["lc_advect_ex"] = (_i, [_vp, C.POINTER(AdvectArgs)])
+
+
+class TracerArgs(C.Structure):
+    """``lc_tracer_args`` of include/lcs_hip.h, field for field."""
+    _fields_ = [("struct_size", _sz),
+                ("tracer_lin", _vp), ("tracer_cub", _vp), ("c1_raw", _vp), ("c2_raw", _vp),
+                ("dtype", _i), ("nt", _i), ("ny_f", _i), ("nx_f", _i),
+                ("lat_min", _d), ("lat_max", _d), ("lon_min", _d), ("lon_max", _d),
+                ("ny", _i), ("nx", _i), ("row0", _i), ("ny_global", _i), ("interp_order", _i),
+                ("traj_x", _vp), ("traj_y", _vp),
+                ("level0", _i), ("n_levels", _i),
+                ("c1_out", _vp), ("c2_out", _vp),
+                ("sum1", _vp), ("sum2", _vp),
+                ("mean1_out", _vp), ("mean2_out", _vp),
+                ("mean_count", _i)]
+
+
+PROTOTYPES["lc_tracer_sample"] = (_i, [_vp, C.POINTER(TracerArgs)])
 
 _lib = None
 

@@ -4428,6 +4428,142 @@ int sample_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
     return LC_OK;
 }
 
+// ---- scalar tracers along trajectories (lc_tracer_sample) ----
+// The (C1, C2) image sits in the (u, v) slots of lc_field_pack's layout, so one sample<> call is sample_kernel's
+// arithmetic for both tracers: same index map, weights, wrap / 'constant' modes and pole rows.
+template <typename T>
+struct TracerOut {
+    T *c1, *c2;           // NULL or [n_levels][n]: the per-entry values
+    double *sum1, *sum2;  // NULL or [n]: running sums carried between calls (read, added to in level order, written back)
+    T *mean1, *mean2;     // NULL or [n]: (T)(sum / count) after this call's range
+    int count;
+};
+
+// One seed per lane, a range of trajectory entries per launch.  The positions are a pure stream ([level][n], coalesced)
+// and a wave walks all its levels, so the kernel is latency-bound unless several levels' positions are in flight: a ring
+// of TRACER_DEPTH entries is held in registers and each slot is refilled right after its gathers are issued (vector
+// loads return in issue order: a refill issued BEFORE a gather would be waited for with it).  The sums are float64 in
+// registers, in level order, whatever T is.
+constexpr int TRACER_DEPTH = 4;
+
+// The walk over the levels for one order-1 / image source (SRC: 0 raw planes 'constant', 1 raw planes 'wrap', 2 lin image
+// 'constant', 3 the ORDER image 'wrap'): a lane's source is fixed for its whole walk, so it is chosen once, outside the loop
+// (one straight loop per source: the refills stay next to the gathers they follow).
+template <typename T, int ORDER, int SRC>
+__device__ __forceinline__ void tracer_walk(const AdvectArgs<T> &A, const T *__restrict__ px, const T *__restrict__ py, int level0,
+                                            int n_levels, const TracerOut<T> &O, size_t n, size_t i, double &s1, double &s2) {
+    // entry j's slot is refilled with entry j + TRACER_DEPTH, clamped to the last one (an unconditional, in-bounds load: a
+    // conditional one makes the compiler wait for it together with the gathers)
+    const int last = n_levels - 1;
+    T qx[TRACER_DEPTH], qy[TRACER_DEPTH];
+#pragma unroll
+    for (int d = 0; d < TRACER_DEPTH; ++d) {
+        const size_t e = (size_t)(d < last ? d : last) * n + i;
+        qx[d] = px[e];
+        qy[d] = py[e];
+    }
+    auto step = [&](int j, T &sx, T &sy) {
+        const T x = sx, y = sy;
+        const size_t level = (size_t)(level0 + j);
+        Pair<T> r;
+        if constexpr (SRC == 0) r = sample<T, 1, false, true>(A.u_raw + level * A.raw_plane, A, x, y);
+        if constexpr (SRC == 1) r = sample<T, 1, true, true>(A.u_raw + level * A.raw_plane, A, x, y);
+        if constexpr (SRC == 2) r = sample<T, 1, false>(A.lin + level * A.level_elems, A, x, y);
+        if constexpr (SRC == 3) r = sample<T, ORDER, true>(A.img + level * A.level_elems, A, x, y);
+        const size_t e = (size_t)(j + TRACER_DEPTH < last ? j + TRACER_DEPTH : last) * n + i;
+        sx = px[e];
+        sy = py[e];
+        if (O.c1) O.c1[(size_t)j * n + i] = r.u;
+        if (O.c2) O.c2[(size_t)j * n + i] = r.v;
+        s1 += (double)r.u;
+        s2 += (double)r.v;
+    };
+    int j0 = 0;
+    for (; j0 + TRACER_DEPTH <= n_levels; j0 += TRACER_DEPTH) {
+#pragma unroll
+        for (int d = 0; d < TRACER_DEPTH; ++d) step(j0 + d, qx[d], qy[d]);
+    }
+#pragma unroll
+    for (int d = 0; d < TRACER_DEPTH - 1; ++d)
+        if (j0 + d < n_levels) step(j0 + d, qx[d], qy[d]);
+}
+
+template <typename T, int ORDER>
+__global__ void __launch_bounds__(256) tracer_kernel(const AdvectArgs<T> A, const T *__restrict__ px, const T *__restrict__ py,
+                                                     int level0, int n_levels, const TracerOut<T> O) {
+    const size_t n = (size_t)A.ny * A.nx;
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int grow = A.row0 + (int)(i / A.nx);
+    const bool pole = grow < A.order || grow >= A.ny_global - A.order;
+    double s1 = O.sum1 ? O.sum1[i] : 0.0, s2 = O.sum2 ? O.sum2[i] : 0.0;
+    // sample_kernel's choice of source: the raw planes as the order-1 source where given, else the lin image at the pole rows
+    if (A.u_raw && (pole || ORDER == 1)) {
+        if (pole)
+            tracer_walk<T, ORDER, 0>(A, px, py, level0, n_levels, O, n, i, s1, s2);
+        else
+            tracer_walk<T, ORDER, 1>(A, px, py, level0, n_levels, O, n, i, s1, s2);
+    } else if (pole)
+        tracer_walk<T, ORDER, 2>(A, px, py, level0, n_levels, O, n, i, s1, s2);
+    else
+        tracer_walk<T, ORDER, 3>(A, px, py, level0, n_levels, O, n, i, s1, s2);
+    if (O.sum1) O.sum1[i] = s1;
+    if (O.sum2) O.sum2[i] = s2;
+    if (O.mean1) O.mean1[i] = (T)(s1 / (double)O.count);
+    if (O.mean2) O.mean2[i] = (T)(s2 / (double)O.count);
+}
+
+template <typename T>
+int tracer_impl(lc_ctx *ctx, const lc_tracer_args &a, const void *c1_raw, const void *c2_raw) {
+    AdvectArgs<T> A = {};
+    A.lin = (const T *)a.tracer_lin;
+    A.img = (a.interp_order != 1) ? (const T *)a.tracer_cub : (const T *)a.tracer_lin;
+    A.u_raw = (const T *)c1_raw;
+    A.v_raw = (const T *)c2_raw;
+    A.raw_plane = (size_t)a.ny_f * a.nx_f;
+    A.level_elems = lc_level_elems(a.ny_f, a.nx_f);
+    A.pitch = a.nx_f + LC_PAD;
+    A.ny_f = a.ny_f;
+    A.nx_f = a.nx_f;
+    A.lat_min = (T)a.lat_min;
+    A.lon_min = (T)a.lon_min;
+    A.lat_span = (T)a.lat_max - (T)a.lat_min;
+    A.lon_span = (T)a.lon_max - (T)a.lon_min;
+    set_fast_transform(A);
+    A.ny = a.ny;
+    A.nx = a.nx;
+    A.row0 = a.row0;
+    A.ny_global = a.ny_global;
+    A.order = a.interp_order;
+    TracerOut<T> O;
+    O.c1 = (T *)a.c1_out;
+    O.c2 = (T *)a.c2_out;
+    O.sum1 = a.sum1;
+    O.sum2 = a.sum2;
+    O.mean1 = (T *)a.mean1_out;
+    O.mean2 = (T *)a.mean2_out;
+    O.count = a.mean_count;
+    const size_t n = (size_t)a.ny * a.nx;
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    static const char *const names[2][5] = {
+        {"tracer_kernel<float, 1>", "tracer_kernel<float, 2>", "tracer_kernel<float, 3>", "tracer_kernel<float, 4>", "tracer_kernel<float, 5>"},
+        {"tracer_kernel<double, 1>", "tracer_kernel<double, 2>", "tracer_kernel<double, 3>", "tracer_kernel<double, 4>", "tracer_kernel<double, 5>"}};
+#define LC_TRACER(ORD)                                                                                                  \
+    hipLaunchKernelGGL((tracer_kernel<T, ORD>), dim3(blocks), dim3(256), 0, ctx->stream, A, (const T *)a.traj_x,          \
+                       (const T *)a.traj_y, a.level0, a.n_levels, O)
+    switch (a.interp_order) {
+        case 2: LC_TRACER(2); break;
+        case 3: LC_TRACER(3); break;
+        case 4: LC_TRACER(4); break;
+        case 5: LC_TRACER(5); break;
+        default: LC_TRACER(1); break;
+    }
+#undef LC_TRACER
+    LC_HIP_CHECK(hipGetLastError());
+    ctx->last_tracer_kernel = names[sizeof(T) == 8][a.interp_order - 1];
+    return LC_OK;
+}
+
 }  // namespace
 
 #ifdef LCS_STAMPS
@@ -4502,6 +4638,35 @@ extern "C" int lc_sample(lc_ctx *ctx, const void *packed_lin, const void *packed
                          int interp_order, void *out_u, void *out_v) {
     return lc_sample_raw(ctx, packed_lin, packed_cub, nullptr, nullptr, dtype, nt, ny_f, nx_f, lat_min, lat_max, lon_min, lon_max,
                          level, pos_x_dev, pos_y_dev, ny, nx, row0, ny_global, interp_order, out_u, out_v);
+}
+
+extern "C" int lc_tracer_sample(lc_ctx *ctx, const lc_tracer_args *args) {
+    LC_REQUIRE(args, "lc_tracer_sample: null arguments");
+    LC_REQUIRE(args->struct_size == sizeof(lc_tracer_args), "lc_tracer_sample: struct_size %zu, this library's lc_tracer_args has %zu bytes",
+               args->struct_size, sizeof(lc_tracer_args));
+    LC_REQUIRE(ctx, "lc_tracer_sample: null context");
+    const lc_tracer_args &a = *args;
+    LC_REQUIRE(a.dtype == LC_F32 || a.dtype == LC_F64, "lc_tracer_sample: bad dtype %d", a.dtype);
+    if (a.interp_order < 1 || a.interp_order > 5) {
+        lc_set_error("lc_tracer_sample: interp_order %d unsupported (scipy's spline orders 1..5; 0 fails in the reference)",
+                     a.interp_order);
+        return LC_EUNSUPPORTED;
+    }
+    LC_REQUIRE((a.c1_raw == nullptr) == (a.c2_raw == nullptr), "lc_tracer_sample: c1_raw and c2_raw must both be set or both NULL");
+    LC_REQUIRE((a.tracer_lin || raw_replaces_lin(a.c1_raw, a.c2_raw, a.dtype, a.interp_order)) && (a.interp_order == 1 || a.tracer_cub),
+               "lc_tracer_sample: missing tracer image");
+    LC_REQUIRE(a.traj_x && a.traj_y, "lc_tracer_sample: null trajectory pointer");
+    LC_REQUIRE(a.ny_f >= 4 && a.nx_f >= 4 && a.ny >= 1 && a.nx >= 1 && a.n_levels >= 1, "lc_tracer_sample: bad sizes");
+    LC_REQUIRE(a.level0 >= 0 && a.level0 <= a.nt - a.n_levels, "lc_tracer_sample: levels [%d, %d + %d) outside the %d field levels",
+               a.level0, a.level0, a.n_levels, a.nt);
+    LC_REQUIRE(a.row0 >= 0 && a.row0 + a.ny <= a.ny_global, "lc_tracer_sample: rows outside the global grid");
+    LC_REQUIRE(a.lat_max > a.lat_min && a.lon_max > a.lon_min, "lc_tracer_sample: field coordinates must be ascending");
+    LC_REQUIRE(!(a.mean1_out || a.mean2_out) || a.mean_count >= 1, "lc_tracer_sample: mean_count %d", a.mean_count);
+    LC_HIP_CHECK(hipSetDevice(ctx->device));
+    const bool raw = raw_replaces_lin(a.c1_raw, a.c2_raw, a.dtype, a.interp_order);
+    const void *c1_raw = raw ? a.c1_raw : nullptr, *c2_raw = raw ? a.c2_raw : nullptr;
+    if (a.dtype == LC_F32) return tracer_impl<float>(ctx, a, c1_raw, c2_raw);
+    return tracer_impl<double>(ctx, a, c1_raw, c2_raw);
 }
 
 extern "C" int lc_advect(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, const void *packed_ext,

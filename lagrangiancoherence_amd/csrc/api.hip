@@ -82,6 +82,7 @@ extern "C" int lc_ctx_create(int device, lc_ctx **out) {
     c->last_advect_launches = 0;
     c->last_sigma_kernel = "";
     c->last_pack_kernel = "";
+    c->last_tracer_kernel = "";
     c->verify_dev = nullptr;
     c->trunc = nullptr;
     c->xfer = nullptr;
@@ -263,6 +264,7 @@ extern "C" const char *lc_ctx_last_advect_kernel(const lc_ctx *ctx) { return ctx
 extern "C" int lc_ctx_last_advect_launches(const lc_ctx *ctx) { return ctx ? ctx->last_advect_launches : 0; }
 extern "C" const char *lc_ctx_last_sigma_kernel(const lc_ctx *ctx) { return ctx ? ctx->last_sigma_kernel : ""; }
 extern "C" const char *lc_ctx_last_pack_kernel(const lc_ctx *ctx) { return ctx ? ctx->last_pack_kernel : ""; }
+extern "C" const char *lc_ctx_last_tracer_kernel(const lc_ctx *ctx) { return ctx ? ctx->last_tracer_kernel : ""; }
 
 static void host_ws_destroy(lc_ctx *ctx);  // (below, with the one-call host route)
 

@@ -33,6 +33,7 @@ struct lc_ctx {
     const char *last_advect_kernel;
     const char *last_sigma_kernel;
     const char *last_pack_kernel;   // what the last lc_field_pack launched for the prefilter / interleave stage (lc_ctx_last_pack_kernel)
+    const char *last_tracer_kernel; // what the last lc_tracer_sample launched (lc_ctx_last_tracer_kernel)
     unsigned *verify_dev;  // NULL, or 16 uint32 wave-state counters in device memory (lc_ctx_set_verify)
     lc_trunc_cache *trunc;
     struct lc_host_xfer *xfer;  // NULL until a one-call host route first needs it: the pinned staging ring + its threads (hostxfer.h)

@@ -107,8 +107,17 @@ def _to_np(t):
 # ---------------------------------------------------------------------------
 # trajectory.parcel_propagation
 # ---------------------------------------------------------------------------
+def _check_tracer(C, U, u_time, lat, lon, propdim):
+    """The tracer's values as (time, latitude, longitude) after sorting, checked against U's dims and coordinates."""
+    assert set(C.dims) == set(U.dims), "C and U dims are different"
+    c, c_time, c_lat, c_lon = _sorted_tll(C, propdim)
+    assert np.array_equal(c_time, u_time) and np.array_equal(c_lat, lat) and np.array_equal(c_lon, lon), \
+        "C coordinates differ from U coordinates"
+    return c
+
+
 def parcel_propagation(U, V, timestep=1, propdim="time", verbose=True, return_traj=False, SETTLS_order=0,
-                       copy=False, interp_order=3, cyclic_xboundary=False):
+                       copy=False, interp_order=3, cyclic_xboundary=False, C=None):
     """Lagrangian 2-time-level advection.  Signature of LCS/trajectory.py:8-18.
 
     Returns ``(positions_x, positions_y)``: 2-D ``(latitude, longitude)`` arrays with a
@@ -116,10 +125,17 @@ def parcel_propagation(U, V, timestep=1, propdim="time", verbose=True, return_tr
     time list (trajectory.py:141-142), or with ``return_traj`` 3-D
     ``(propdim, latitude, longitude)`` arrays whose entry 0 is the seed grid
     (trajectory.py:73-74,138-139).
+
+    ``C``: a scalar tracer on U's grid and time levels (the call LCS/area_of_influence.py:314-316 makes; the dead flag
+    ``tracer_account`` of trajectory.py:45).  Returns ``(positions_x, positions_y, c)``: ``c`` has ``positions_x``'s dims
+    and labels, entry i the tracer at time level i (stored order, Q6) sampled at trajectory entry i with the call's
+    ``interp_order`` (tools.xr_map_coordinates); without ``return_traj`` the last entry.  ``c.mean(propdim)`` is the
+    driver's ``c_int``.  Positions are bit-identical to the call without ``C``.
     """
     verboseprint = print if verbose else (lambda *a, **k: None)
     u, time, lat, lon = _sorted_tll(U, propdim)
     v, _, _, _ = _sorted_tll(V, propdim)
+    c = None if C is None else _check_tracer(C, U, time, lat, lon, propdim)
     times = time.tolist()                                   # trajectory.py:58
     if timestep < 0:
         times.reverse()                                     # labels only (Q6)
@@ -128,7 +144,16 @@ def parcel_propagation(U, V, timestep=1, propdim="time", verbose=True, return_tr
     # pack + advect in one call (large float64 order-3 series: the pack of chunk k+1 overlaps the advect of chunk k)
     res = eng.pack_and_advect(u, v, lat, lon, lat, lon, timestep, SETTLS_order=SETTLS_order, interp_order=interp_order,
                               cyclic_xboundary=cyclic_xboundary, return_traj=return_traj,
-                              fuse_levels=eng.f64_fuse_levels(common_dtype(u, v, lat, lon), lat.size * lon.size))[1:]
+                              fuse_levels=eng.f64_fuse_levels(common_dtype(u, v, lat, lon), lat.size * lon.size))
+    field, res = res[0], res[1:]
+    cs = None
+    if c is not None:
+        # the tracer in the field's compute dtype, sampled along the positions just computed (entry i at level i)
+        tracer = eng.prepare_tracer(c, None, lat, lon, interp_order, dtype=field.dtype)
+        if return_traj:
+            cs = eng.sample_tracer(tracer, res[2], res[3], 0, interp_order)[0][0]
+        else:
+            cs = eng.sample_tracer(tracer, res[0][None], res[1][None], field.nt - 1, interp_order)[0][0][0]
     coords2d = {"latitude": lat, "longitude": lon}
     if return_traj:
         assert type(times[0]).__name__ != "Datetime360Day", \
@@ -139,10 +164,14 @@ def parcel_propagation(U, V, timestep=1, propdim="time", verbose=True, return_tr
         dims = (propdim, "latitude", "longitude")
         px = _make(U, _to_np(res[2]), dims, {propdim: tcoord, **coords2d}, getattr(U, "name", None))
         py = _make(U, _to_np(res[3]), dims, {propdim: tcoord, **coords2d}, getattr(U, "name", None))
+        if cs is not None:
+            return px, py, _make(U, _to_np(cs), dims, {propdim: tcoord, **coords2d}, getattr(C, "name", None))
         return px, py
     dims = ("latitude", "longitude")
     px = _make(U, _to_np(res[0]), dims, {**coords2d, propdim: times[-1]}, getattr(U, "name", None))
     py = _make(U, _to_np(res[1]), dims, {**coords2d, propdim: times[-1]}, getattr(U, "name", None))
+    if cs is not None:
+        return px, py, _make(U, _to_np(cs), dims, {**coords2d, propdim: times[-1]}, getattr(C, "name", None))
     return px, py
 
 

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _capi
 
-__all__ = ["Engine", "PackedField", "lcs_host", "lcs_global_host", "common_dtype", "x_boundary_mode"]
+__all__ = ["Engine", "PackedField", "PackedTracer", "lcs_host", "lcs_global_host", "common_dtype", "x_boundary_mode"]
 
 _NP2LC = {np.dtype(np.float32): _capi.LC_F32, np.dtype(np.float64): _capi.LC_F64}
 _LAYOUTS = {"reference": _capi.LC_LAYOUT_REFERENCE, "physical": _capi.LC_LAYOUT_PHYSICAL}
@@ -78,6 +78,26 @@ class PackedField:
     u32: "torch.Tensor | None" = None      # wind_f32: the float32 planes as given (the float64 copies u, v are made when a call needs them)
     v32: "torch.Tensor | None" = None
     planes32_version: "tuple | None" = None  # (u32._version, v32._version) when the field was prepared: borrowed like u, v
+
+
+@dataclass
+class PackedTracer:
+    """One or two scalar tracers on a wind grid, ready for ``lc_tracer_sample``: the (C1, C2) pair in the (u, v) slots of
+    ``lc_field_pack``'s layout (one tracer is the pair (C, C))."""
+    lin: "torch.Tensor | None"     # order-1 image: float32 at order 1 only (float64 samples the planes)
+    cub: "torch.Tensor | None"     # B-spline coefficient image of order ``order`` (2..5), None for order 1
+    c1: "torch.Tensor"             # the planes (nt, ny_f, nx_f): the order-1 source of the pole rows, and of every row in float64
+    c2: "torch.Tensor"             # ... of the second tracer (``c1`` itself for one tracer)
+    two: bool                      # two tracers
+    nt: int
+    ny_f: int
+    nx_f: int
+    lat_min: float
+    lat_max: float
+    lon_min: float
+    lon_max: float
+    dtype: np.dtype
+    order: int = 1
 
 
 class Engine:
@@ -667,6 +687,149 @@ class Engine:
             self._ptr(px), self._ptr(py), ny, nx, int(row0), ny_global, int(interp_order), self._ptr(ou),
             self._ptr(ov)), self.lib)
         return ou, ov
+
+    # ------------------------------------------------------------------ tracers along trajectories
+    TRACER_RING_BYTES = 2 << 30   # cap of advect_tracer's scratch ring of positions (mean-only cyclic calls)
+
+    def last_tracer_kernel(self) -> str:
+        """Name of the kernel the last tracer sample launched (``lc_ctx_last_tracer_kernel``)."""
+        return self.lib.lc_ctx_last_tracer_kernel(self.ctx).decode()
+
+    def prepare_tracer(self, c1, c2=None, lat_f=None, lon_f=None, interp_order: int = 1, dtype=None) -> PackedTracer:
+        """Upload (if needed) and pack one or two tracers ``(nt, ny_f, nx_f)`` on the wind's grid for sampling along
+        trajectories.  Only what sampling reads is built: float32 at order 1 the order-1 image, float64 at order 1
+        nothing (the planes are sampled), orders 2..5 the coefficient image of that order (the planes serve the pole
+        rows).  ``dtype``: the wind field's compute dtype (``PackedField.dtype``); default float32 only if every input is."""
+        if interp_order not in (1, 2, 3, 4, 5):
+            raise ValueError(f"interp_order {interp_order} unsupported (scipy's spline orders 1..5)")
+        lat_f, lon_f = np.asarray(lat_f), np.asarray(lon_f)
+        dtype = np.dtype(dtype or common_dtype(c1, c2, lat_f, lon_f))
+        if len(c1.shape) != 3 or (c2 is not None and tuple(c2.shape) != tuple(c1.shape)):
+            raise ValueError("tracers must be (time, latitude, longitude), both of one shape")
+        nt, ny_f, nx_f = (int(s) for s in c1.shape)
+        if lat_f.shape != (ny_f,) or lon_f.shape != (nx_f,):
+            raise ValueError("coordinate lengths do not match the tracer")
+        if not (np.all(np.diff(lat_f) > 0) and np.all(np.diff(lon_f) > 0)):
+            raise ValueError("latitude and longitude must be ascending (sort first)")
+        d1 = self.to_device(c1, dtype)
+        d2 = self.to_device(c2, dtype) if c2 is not None else d1
+        n = self.lib.lc_packed_elems(nt, ny_f, nx_f)
+        lin = cub = None
+        self._use_current_stream()
+        if interp_order == 1 and dtype == np.dtype(np.float32):
+            lin = self._empty((n,), dtype)
+            _capi.check(self.lib.lc_field_pack(self.ctx, self._ptr(d1), self._ptr(d2), _capi.LC_F32, nt, ny_f, nx_f, 1,
+                                               self._ptr(lin), None), self.lib)
+        elif interp_order != 1:
+            cub = self._empty((n,), dtype)
+            _capi.check(self.lib.lc_field_pack(self.ctx, self._ptr(d1), self._ptr(d2), _NP2LC[dtype], nt, ny_f, nx_f,
+                                               int(interp_order), self._ptr(cub), None), self.lib)
+        la, lo = lat_f.astype(dtype), lon_f.astype(dtype)
+        return PackedTracer(lin, cub, d1, d2, c2 is not None, nt, ny_f, nx_f, float(la[0]), float(la[-1]), float(lo[0]),
+                            float(lo[-1]), dtype, int(interp_order))
+
+    def sample_tracer(self, tracer: PackedTracer, traj_x, traj_y, level0=0, interp_order=1, row0=0, ny_global=None,
+                      values=True, sums=None, mean_count=None):
+        """``lc_tracer_sample`` on trajectory entries ``traj_x / traj_y`` ``(n_levels, ny, nx)`` (device tensors of the
+        tracer's dtype): entry j at field level ``level0 + j``.  Returns ``(c1, c2)`` per-entry values (``values``; c2
+        None for one tracer) and ``(mean1, mean2)`` (when ``mean_count`` is given: sum / mean_count).  ``sums``: float64
+        ``(ntracers, ny, nx)`` running sums the entries are added to (carried between calls)."""
+        if interp_order != 1 and tracer.order != interp_order:
+            raise ValueError(f"tracer was prepared for interp_order={tracer.order}")
+        dtype = tracer.dtype
+        want = getattr(self.torch, dtype.name)
+        if traj_x.dtype != want or traj_y.dtype != want or tuple(traj_x.shape) != tuple(traj_y.shape) or traj_x.dim() != 3 \
+                or not (traj_x.is_contiguous() and traj_y.is_contiguous()):
+            raise ValueError(f"trajectories must be two contiguous (n_levels, ny, nx) {dtype.name} device tensors")
+        nl, ny, nx = (int(s) for s in traj_x.shape)
+        ny_global = ny if ny_global is None else int(ny_global)
+        c1 = self._empty((nl, ny, nx), dtype) if values else None
+        c2 = self._empty((nl, ny, nx), dtype) if values and tracer.two else None
+        m1 = m2 = None
+        if mean_count is not None:
+            m1 = self._empty((ny, nx), dtype)
+            m2 = self._empty((ny, nx), dtype) if tracer.two else None
+        p = lambda t: t.data_ptr() if t is not None else None
+        a = _capi.TracerArgs(
+            struct_size=C.sizeof(_capi.TracerArgs), tracer_lin=p(tracer.lin), tracer_cub=p(tracer.cub if interp_order != 1 else None),
+            c1_raw=p(tracer.c1), c2_raw=p(tracer.c2), dtype=_NP2LC[dtype], nt=tracer.nt, ny_f=tracer.ny_f, nx_f=tracer.nx_f,
+            lat_min=tracer.lat_min, lat_max=tracer.lat_max, lon_min=tracer.lon_min, lon_max=tracer.lon_max, ny=ny, nx=nx,
+            row0=int(row0), ny_global=ny_global, interp_order=int(interp_order), traj_x=p(traj_x), traj_y=p(traj_y),
+            level0=int(level0), n_levels=nl, c1_out=p(c1), c2_out=p(c2),
+            sum1=p(sums[0]) if sums is not None else None, sum2=p(sums[1]) if sums is not None and tracer.two else None,
+            mean1_out=p(m1), mean2_out=p(m2), mean_count=int(mean_count or 0))
+        if interp_order == 1 and dtype == np.dtype(np.float32) and tracer.lin is None:
+            raise ValueError("float32 at interp_order=1 samples the order-1 image: prepare the tracer at order 1")
+        self._use_current_stream()
+        _capi.check(self.lib.lc_tracer_sample(self.ctx, C.byref(a)), self.lib)
+        return (c1, c2), (m1, m2)
+
+    def advect_tracer(self, field: PackedField, tracer: PackedTracer, seed_lat, seed_lon, timestep, SETTLS_order=0,
+                      interp_order=1, cyclic_xboundary=True, t0=0, nsteps=None, return_traj=False, tracer_traj=False,
+                      row0=0, ny_global=None, noncyclic_clamp=None, ring_bytes=None):
+        """:meth:`advect` plus the tracer(s) sampled along the trajectories: entry i (i = 0 .. nsteps, entry 0 = the seed
+        grid) is the tracer at field level ``t0 + i`` at trajectory entry i, with the rule of tools.xr_map_coordinates at
+        ``interp_order``.  Returns a dict: ``x``, ``y`` (bit-identical to :meth:`advect` without a tracer), ``mean`` (and
+        ``mean2`` for two tracers): sum over the nsteps + 1 entries in float64, level order, divided by nsteps + 1 and
+        rounded once; with ``return_traj`` ``traj_x`` / ``traj_y``; with ``tracer_traj`` ``c`` (and ``c2``)
+        ``(nsteps + 1, ny, nx)``.
+
+        Without trajectories asked for, a cyclic call advects in level chunks into a scratch ring of at most
+        ``ring_bytes`` (default :attr:`TRACER_RING_BYTES`, 2 GiB) of positions (``lc_advect`` / ``lc_advect_from``: bit-
+        identical to one call) and samples each chunk, carrying float64 sums of 8 bytes per seed and tracer.  The
+        reference's non-cyclic clamp (``LC_X_CLAMP_REFERENCE_OUTER``) is decided over the whole series and cannot resume
+        from given positions, so such a call materialises all nsteps + 1 entries once."""
+        if tracer.dtype != field.dtype:
+            raise ValueError(f"tracer dtype {tracer.dtype} differs from the field's compute dtype {field.dtype}")
+        if (tracer.nt, tracer.ny_f, tracer.nx_f) != (field.nt, field.ny_f, field.nx_f) or \
+                (tracer.lat_min, tracer.lat_max, tracer.lon_min, tracer.lon_max) != (field.lat_min, field.lat_max, field.lon_min, field.lon_max):
+            raise ValueError("the tracer must lie on the wind's grid and time levels")
+        if interp_order != 1 and tracer.order != interp_order:
+            raise ValueError(f"tracer was prepared for interp_order={tracer.order}")
+        torch = self.torch
+        dtype = field.dtype
+        nsteps = field.nt - 1 - t0 if nsteps is None else int(nsteps)
+        slat = self.to_device(seed_lat, dtype)
+        slon = self.to_device(seed_lon, dtype)
+        ny, nx = int(slat.numel()), int(slon.numel())
+        ny_global = ny if ny_global is None else int(ny_global)
+        xmode = x_boundary_mode(cyclic_xboundary, noncyclic_clamp, int(row0) == 0 and ny == ny_global)
+        ring_bytes = self.TRACER_RING_BYTES if ring_bytes is None else int(ring_bytes)
+        entry_bytes = 2 * ny * nx * dtype.itemsize
+        chunk = max(ring_bytes // entry_bytes - 1, 1)          # steps per ring fill
+        res = {}
+        kw = dict(level0=t0, interp_order=interp_order, row0=row0, ny_global=ny_global)
+        if return_traj or tracer_traj or xmode == _capi.LC_X_CLAMP_REFERENCE_OUTER or nsteps <= chunk:
+            x, y, tx, ty = self.advect(field, slat, slon, timestep, SETTLS_order, interp_order, cyclic_xboundary, t0, nsteps,
+                                       return_traj=True, row0=row0, ny_global=ny_global, noncyclic_clamp=noncyclic_clamp)
+            (c1, c2), (m1, m2) = self.sample_tracer(tracer, tx, ty, values=tracer_traj, mean_count=nsteps + 1, **kw)
+            res.update(x=x, y=y, mean=m1, mean2=m2)
+            if return_traj:
+                res.update(traj_x=tx, traj_y=ty)
+            if tracer_traj:
+                res.update(c=c1, c2=c2)
+            return res
+        # mean only, cyclic: chunks of `chunk` steps through the ring; entry 0 of a later chunk is the previous chunk's
+        # last entry (its start positions), already counted
+        x, y = self._empty((ny, nx), dtype), self._empty((ny, nx), dtype)
+        ring_x, ring_y = self._empty((chunk + 1, ny, nx), dtype), self._empty((chunk + 1, ny, nx), dtype)
+        sums = torch.zeros((2 if tracer.two else 1, ny, nx), dtype=torch.float64, device=self.device)
+        s = 0
+        while s < nsteps:
+            k = min(chunk, nsteps - s)
+            start = (x, y) if s else (None, None)
+            self._use_current_stream()
+            a = self._advect_args(field, interp_order, slat, ny, slon, nx, row0, ny_global, start[0], start[1], timestep,
+                                  SETTLS_order, xmode, t0 + s, k, 1, 0, x, y, ring_x[:k + 1], ring_y[:k + 1])
+            _capi.check(self.lib.lc_advect_ex(self.ctx, C.byref(a)), self.lib)
+            first = 0 if s == 0 else 1
+            last = s + k == nsteps
+            kw["level0"] = t0 + s + first
+            _, (m1, m2) = self.sample_tracer(tracer, ring_x[first:k + 1], ring_y[first:k + 1], values=False, sums=sums,
+                                             mean_count=nsteps + 1 if last else None, **kw)
+            s += k
+        res.update(x=x, y=y, mean=m1, mean2=m2)
+        return res
 
     # ------------------------------------------------------------------ K3
     def sigma(self, x_dep, y_dep, seed_lat_rows, dlat, dlon, ny_global=None, in_row0=0, out_row0=None,
