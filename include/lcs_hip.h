@@ -38,7 +38,7 @@ extern "C" {
  * client built against 100 must be rebuilt), lc_ctx_get_level_chunk, lc_ctx_set/get_f64_fidelity, lc_advect_ex and
  * lc_sample_raw added, lc_field_pack accepts packed_dev == NULL at order 1 (fused-level image only).  lc_version() returns the value the LIBRARY
  * was built with: compare it with this macro before any other call (tests/c/abi_smoke.c, _capi.load do). */
-#define LC_VERSION 104 /* 0.1.4: + lc_tracer_sample, lc_ctx_last_tracer_kernel (additive: no argument list changed), + lc_ctx_set_host_pipeline, lc_copy_to_device, lc_copy_to_host, lc_ctx_set_host_cache, lc_ctx_trim, lc_ctx_last_host_marks, lc_ctx_set_xcd_split (0.1.3: + lc_ctx_last_pack_kernel; 0.1.2: + lc_ctx_set_verify, lc_ctx_read_verify, LC_F64_WIND_F32_LIN32) */
+#define LC_VERSION 104 /* 0.1.4: + lc_advect_series, lc_sigma_batch, + lc_tracer_sample, lc_ctx_last_tracer_kernel (additive: no argument list changed), + lc_ctx_set_host_pipeline, lc_copy_to_device, lc_copy_to_host, lc_ctx_set_host_cache, lc_ctx_trim, lc_ctx_last_host_marks, lc_ctx_set_xcd_split (0.1.3: + lc_ctx_last_pack_kernel; 0.1.2: + lc_ctx_set_verify, lc_ctx_read_verify, LC_F64_WIND_F32_LIN32) */
 
 typedef struct lc_ctx lc_ctx;
 
@@ -427,6 +427,18 @@ typedef struct lc_advect_args {
 } lc_advect_args;
 int lc_advect_ex(lc_ctx *ctx, const lc_advect_args *args);
 
+/* A sliding-window series of lc_advect_ex calls in one: lc_advect_ex's arguments and semantics for n_members >= 1 (member m
+ * integrates nsteps steps from time level t0 + m * t0_stride, its positions in the m-th [ny*nx] plane of x_out / y_out),
+ * whole seed grids only (row0 == 0, ny == ny_global), traj_x / traj_y NULL.  LC_X_CYCLIC and LC_X_CLAMP_POINT run as
+ * lc_advect_batch does.  LC_X_CLAMP_REFERENCE_OUTER (which lc_advect_batch refuses) runs lc_advect's rule for every member
+ * at once: the fused ensemble launch in chunks of 16 levels with one clamp flag PER MEMBER (all read back once per chunk),
+ * each member's positions saved before its current chunk; a member whose flag never fires keeps its fused result, the
+ * others re-run from the start of the chunk in which their own flag fired, sub-step by sub-step, all of them in one launch
+ * per sub-step (lc_ctx_last_advect_kernel: "outer_substep_batch_kernel").  Each member's result is, bit for bit, what
+ * lc_advect_ex(t0 + m * t0_stride, n_members = 1) gives.  No flag all-reduce is made (lc_ctx_set_flag_allreduce is for
+ * row blocks). */
+int lc_advect_series(lc_ctx *ctx, const lc_advect_args *args);
+
 /* One interpolation pass on its own: tools.xr_map_coordinates (LCS/tools.py:11-41) for the
  * u and v fields of time level `level` at the given positions (degrees), same index
  * scale, row classes and boundary modes as inside lc_advect.  pos_x/pos_y/out_u/out_v
@@ -499,6 +511,14 @@ int lc_sigma(lc_ctx *ctx, const void *x_dep, const void *y_dep, int dtype,
              const void *seed_lat_dev, double dlat, double dlon,
              int fd_fp32_cast, int tensor_layout,
              int out_row0, int n_out_rows, void *sigma_out);
+
+/* lc_sigma for n_members whole grids at once (in_row0 = out_row0 = 0, n_in_rows = n_out_rows = ny_global = ny): x_dep, y_dep
+ * and sigma_out are [n_members][ny*nx], seed_lat_dev [ny]; one launch covers every member, and every plane equals lc_sigma
+ * on that plane bit for bit (the same kernel choice per plane, under a batch name in lc_ctx_last_sigma_kernel:
+ * "sigma_march_batch_kernel_f32", "sigma_batch_kernel_f32", "sigma_batch_kernel<double, float|double>"). */
+int lc_sigma_batch(lc_ctx *ctx, const void *x_dep, const void *y_dep, int dtype, int ny, int nx,
+                   const void *seed_lat_dev, double dlat, double dlon, int fd_fp32_cast, int tensor_layout,
+                   int n_members, void *sigma_out);
 
 /* The 9-component "def_tensor" itself, for callers of LCS.flowmap_gradient
  * (LCS/LCS.py:171-225): planes dXdx,dXdy,dYdx,dYdy,dZdx,dZdy,dXdr,dYdr,dZdr (the last

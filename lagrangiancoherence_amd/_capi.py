@@ -72,6 +72,7 @@ PROTOTYPES = {
     "lc_sample": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _d, _d, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "lc_sample_raw": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _d, _d, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "lc_sigma": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _d, _d, _i, _i, _i, _i, _vp]),
+    "lc_sigma_batch": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _d, _d, _i, _i, _i, _vp]),
     "lc_flowmap_gradient": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _d, _d, _i, _vp]),
     "lc_fourth_order_derivative": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lc_gaussian_filter": (_i, [_vp, _vp, _i, _i, _i, _d, _vp, _vp]),
@@ -109,6 +110,7 @@ class AdvectArgs(C.Structure):
 
 
 PROTOTYPES["lc_advect_ex"] = (_i, [_vp, C.POINTER(AdvectArgs)])
+PROTOTYPES["lc_advect_series"] = (_i, [_vp, C.POINTER(AdvectArgs)])
 
 
 class TracerArgs(C.Structure):

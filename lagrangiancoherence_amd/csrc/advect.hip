@@ -21,6 +21,7 @@
 // always in range and its (u,v) pairs are contiguous along x, so one sample
 // position costs 2 (order 1, float) wide loads per level instead of 8 scalars.
 #include <type_traits>
+#include <vector>
 
 #include "lcs_common.h"
 #include "launch_plan.h"
@@ -87,6 +88,7 @@ struct AdvectArgs {
     int tile_order_two_seed;  // host side only: what the two-seed kernel's launch puts into tile_order
     int pole_blocks, pole_lo, pole_hi;  // leading workgroups that take the pole rows (first pole_lo / last pole_hi local rows); 0: the tiles do
     unsigned *clamp_flag;  // NULL, or set to 1 when the non-cyclic longitude clamp moves any parcel (Q9)
+    int clamp_stride;      // lc_advect_series: member m's flag is clamp_flag[m * clamp_stride] (0: one flag for the launch)
     unsigned *verify;      // NULL, or the context's 16 wave-state counters (lc_ctx_set_verify: the one-seed order-1 LDS kernel's VERIFY instances)
 };
 
@@ -142,6 +144,7 @@ __device__ __forceinline__ AdvectArgs<T> for_member(const AdvectArgs<T> &A0) {
             A.x_start = A0.x_start + off;
             A.y_start = A0.y_start + off;
         }
+        if (A0.clamp_stride) A.clamp_flag = A0.clamp_flag + (size_t)blockIdx.y * A0.clamp_stride;
     }
     return A;
 }
@@ -3909,11 +3912,12 @@ __device__ __forceinline__ T outer_applied(const AdvectArgs<T> &A, const unsigne
     return x;
 }
 
+// One seed's sub-step of the outer rule (outer_substep_kernel and, per member, outer_substep_batch_kernel).
 template <typename T, int ORDER>
-__global__ void outer_substep_kernel(const AdvectArgs<T> A, const OuterArgs<T> O, int level, int is_iter) {
+__device__ __forceinline__ void outer_substep_seed(const AdvectArgs<T> &A, const OuterArgs<T> &O, int level, int is_iter,
+                                                   size_t i) {
 #pragma clang fp contract(off)
-    const size_t n = (size_t)A.ny * A.nx;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    {
         const int iy = (int)(i / A.nx), ix = (int)(i - (size_t)iy * A.nx);
         T x = outer_applied<T>(A, O.p_rlo, O.p_clo, O.p_rhi, O.p_chi, iy, ix, O.x[i]);
         T y = O.y[i];
@@ -3969,6 +3973,13 @@ __global__ void outer_substep_kernel(const AdvectArgs<T> A, const OuterArgs<T> O
     }
 }
 
+template <typename T, int ORDER>
+__global__ void outer_substep_kernel(const AdvectArgs<T> A, const OuterArgs<T> O, int level, int is_iter) {
+    const size_t n = (size_t)A.ny * A.nx;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        outer_substep_seed<T, ORDER>(A, O, level, is_iter, i);
+}
+
 template <typename T>
 __global__ void outer_hi_kernel(const AdvectArgs<T> A, const OuterArgs<T> O) {
     const size_t n = (size_t)A.ny * A.nx;
@@ -3994,6 +4005,93 @@ __global__ void outer_store_kernel(const AdvectArgs<T> A, const OuterArgs<T> O, 
         } else {
             dst_x[i] = outer_applied<T>(A, O.rlo, O.clo, O.rhi, O.chi, iy, ix, O.x[i]);
             dst_y[i] = O.y[i];
+        }
+    }
+}
+
+// lc_advect_series with LC_X_CLAMP_REFERENCE_OUTER: the sub-step phase of every member whose parcels left the box, one
+// launch per sub-step for all of them.  Member m = blockIdx.y reads level t0 + m * member_t0_stride + s and keeps its own
+// positions (the m-th plane of x_out / y_out), Euler sample (the m-th plane of eu and of ev) and 2 (ny + nx) flag words
+// (rlo + m * nflag ...), double-buffered by sub-step like outer_substep_kernel's.  It enters at its own restart step (the
+// first step of the chunk in which its flag fired) from the positions saved before that chunk; a member whose flag never
+// fired (restart -1) keeps its fused result and its workgroups return at once.  Per member: the arithmetic, operation
+// order and flag sequence of advect_outer_impl, so each member equals its own lc_advect bit for bit.
+struct OuterSeries {
+    const int *restart;  // [n_members] (device): member m's first sub-step step, -1 = not in the sub-step phase
+    size_t plane;        // ny * nx
+    size_t nflag;        // 2 (ny + nx)
+};
+
+template <typename T>
+__device__ __forceinline__ OuterArgs<T> outer_member(const OuterArgs<T> &O0, const OuterSeries &S, int m, bool first) {
+    OuterArgs<T> O = O0;
+    const size_t p = (size_t)m * S.plane, f = (size_t)m * S.nflag;
+    O.x += p;
+    O.y += p;
+    O.eu += p;
+    O.ev += p;
+    O.rlo += f;
+    O.clo += f;
+    O.rhi += f;
+    O.chi += f;
+    if (first) {  // the member's first sub-step: no earlier flags to apply
+        O.p_rlo = O.p_clo = O.p_rhi = O.p_chi = nullptr;
+    } else {
+        O.p_rlo += f;
+        O.p_clo += f;
+        O.p_rhi += f;
+        O.p_chi += f;
+    }
+    return O;
+}
+
+template <typename T, int ORDER>
+__global__ void outer_substep_batch_kernel(const AdvectArgs<T> A, const OuterArgs<T> O0, const OuterSeries S, int s, int is_iter) {
+    const int m = (int)blockIdx.y;
+    const int r = S.restart[m];
+    if (r < 0 || s < r) return;
+    const OuterArgs<T> O = outer_member<T>(O0, S, m, !is_iter && s == r);
+    const int level = A.t0 + m * A.member_t0_stride + s;
+    const size_t n = (size_t)A.ny * A.nx;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        outer_substep_seed<T, ORDER>(A, O, level, is_iter, i);
+}
+
+template <typename T>
+__global__ void outer_hi_batch_kernel(const AdvectArgs<T> A, const OuterArgs<T> O0, const OuterSeries S, int s) {
+    const int m = (int)blockIdx.y;
+    const int r = S.restart[m];
+    if (r < 0 || s < r) return;
+    const OuterArgs<T> O = outer_member<T>(O0, S, m, true);
+    const size_t n = (size_t)A.ny * A.nx;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int iy = (int)(i / A.nx), ix = (int)(i - (size_t)iy * A.nx);
+        T x = O.x[i];
+        if (O.rlo[iy] && O.clo[ix]) x = A.x_min;  // as outer_hi_kernel
+        if (x > A.x_max) {
+            O.rhi[iy] = 1u;
+            O.chi[ix] = 1u;
+        }
+    }
+}
+
+// start = 1: the member's positions at its restart step (saved_x / saved_y planes [n_members][ny*nx], or the seed grid
+// for restart 0); start = 0: the last sub-step's flags applied (outer_store_kernel's final store).
+template <typename T>
+__global__ void outer_store_batch_kernel(const AdvectArgs<T> A, const OuterArgs<T> O0, const OuterSeries S, const T *saved_x,
+                                         const T *saved_y, int start) {
+    const int m = (int)blockIdx.y;
+    const int r = S.restart[m];
+    if (r < 0) return;
+    const OuterArgs<T> O = outer_member<T>(O0, S, m, true);
+    const size_t n = (size_t)A.ny * A.nx, p = (size_t)m * S.plane;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int iy = (int)(i / A.nx), ix = (int)(i - (size_t)iy * A.nx);
+        if (start) {
+            O.x[i] = r > 0 ? saved_x[p + i] : A.seed_lon[ix];
+            O.y[i] = r > 0 ? saved_y[p + i] : A.seed_lat[iy];
+        } else {
+            O.x[i] = outer_applied<T>(A, O.rlo, O.clo, O.rhi, O.chi, iy, ix, O.x[i]);
         }
     }
 }
@@ -4072,6 +4170,83 @@ reduce_failed:
     return LC_ERCCL;
 }
 
+// The sub-step phase of lc_advect_series (LC_X_CLAMP_REFERENCE_OUTER, n_members > 1): every member with restart[m] >= 0
+// runs advect_outer_impl's sequence from step restart[m] (positions: saved planes [2][n_members][ny*nx], or the seed grid
+// for 0), all of them in one launch per sub-step.  Sub-steps are counted from the earliest restart: the flag buffers
+// alternate with that count, which alternates for every member too (each member's steps are a suffix of the same range).
+template <typename T>
+int advect_outer_series_impl(lc_ctx *ctx, AdvectArgs<T> A, const std::vector<int> &restart, const T *saved) {
+    hipStream_t st = ctx->stream;
+    const int nm = A.n_members;
+    const size_t n = (size_t)A.ny * A.nx;
+    const size_t nflag = 2 * ((size_t)A.ny + A.nx);
+    int s_first = A.nsteps;
+    for (int r : restart)
+        if (r >= 0 && r < s_first) s_first = r;
+    T *e = nullptr;
+    unsigned *flags = nullptr;  // [2][n_members][nflag] flag words, then n_members restart steps
+    LC_HIP_CHECK(hipMallocAsync((void **)&e, 2 * (size_t)nm * n * sizeof(T), st));
+    hipError_t er = hipMallocAsync((void **)&flags, (2 * (size_t)nm * nflag + nm) * sizeof(unsigned), st);
+    if (er != hipSuccess) {
+        (void)hipFreeAsync(e, st);
+        LC_HIP_CHECK(er);
+    }
+    int *rs = (int *)(flags + 2 * (size_t)nm * nflag);
+    er = hipMemcpyAsync(rs, restart.data(), nm * sizeof(int), hipMemcpyHostToDevice, st);
+    if (er == hipSuccess) er = hipStreamSynchronize(st);  // (restart is the caller's host vector)
+    if (er != hipSuccess) {
+        (void)hipFreeAsync(e, st);
+        (void)hipFreeAsync(flags, st);
+        LC_HIP_CHECK(er);
+    }
+    const int blocks = (int)((n + 255) / 256 < 16384 ? (n + 255) / 256 : 16384);
+    const dim3 grid(blocks, nm);
+    const OuterSeries S = {rs, n, nflag};
+    OuterArgs<T> O = {};
+    O.x = A.x_out;
+    O.y = A.y_out;
+    O.eu = e;
+    O.ev = e + (size_t)nm * n;
+    const size_t fbuf = (size_t)nm * nflag;
+    auto point = [&](unsigned *cur, unsigned *prev) {
+        O.rlo = cur;
+        O.clo = cur + A.ny;
+        O.rhi = O.clo + A.nx;
+        O.chi = O.rhi + A.ny;
+        O.p_rlo = prev;
+        O.p_clo = prev + A.ny;
+        O.p_rhi = O.p_clo + A.nx;
+        O.p_chi = O.p_rhi + A.ny;
+    };
+    point(flags, flags + fbuf);
+    hipLaunchKernelGGL((outer_store_batch_kernel<T>), grid, dim3(256), 0, st, A, O, S, saved, saved ? saved + (size_t)nm * n : nullptr, 1);
+    int sub = 0;
+    for (int s = s_first; s < A.nsteps; ++s) {
+        for (int k = 0; k <= A.K; ++k, ++sub) {
+            unsigned *cur = flags + (size_t)(sub & 1) * fbuf, *prev = flags + (size_t)((sub & 1) ^ 1) * fbuf;
+            (void)hipMemsetAsync(cur, 0, fbuf * sizeof(unsigned), st);
+            point(cur, prev);
+#define LC_OUTER_B(ORD) hipLaunchKernelGGL((outer_substep_batch_kernel<T, ORD>), grid, dim3(256), 0, st, A, O, S, s, k > 0)
+            switch (A.order) {
+                case 2: LC_OUTER_B(2); break;
+                case 3: LC_OUTER_B(3); break;
+                case 4: LC_OUTER_B(4); break;
+                case 5: LC_OUTER_B(5); break;
+                default: LC_OUTER_B(1); break;
+            }
+#undef LC_OUTER_B
+            hipLaunchKernelGGL((outer_hi_batch_kernel<T>), grid, dim3(256), 0, st, A, O, S, s);
+        }
+    }
+    if (sub) hipLaunchKernelGGL((outer_store_batch_kernel<T>), grid, dim3(256), 0, st, A, O, S, (const T *)nullptr, (const T *)nullptr, 0);
+    const hipError_t le = hipGetLastError();
+    (void)hipFreeAsync(e, st);
+    (void)hipFreeAsync(flags, st);
+    LC_HIP_CHECK(le);
+    ctx->last_advect_kernel = "outer_substep_batch_kernel";
+    return LC_OK;
+}
+
 template <typename T>
 int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, const void *packed_ext, const void *u_raw,
                 const void *v_raw, int nt, int ny_f, int nx_f,
@@ -4079,7 +4254,7 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
                 const void *seed_lon, int nx, int row0, int ny_global, double timestep, int K, int order, int cyclic,
                 int t0, int nsteps, void *x_out, void *y_out, void *traj_x, void *traj_y, const void *x_start,
                 const void *y_start, int wind_f32 = 0, int n_members = 1, int t0_stride = 0, int fuse_levels_raw = 0,
-                const void *lin32 = nullptr, const void *lin32_v = nullptr) {
+                const void *lin32 = nullptr, const void *lin32_v = nullptr, bool series = false) {
     AdvectArgs<T> A{};
     A.wind_f32 = wind_f32;
     A.n_members = n_members;
@@ -4137,12 +4312,16 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
     A.clamp_flag = nullptr;
     A.verify = sizeof(T) == 4 ? ctx->verify_dev : nullptr;
     unsigned *clamp_flag = nullptr;
+    // lc_advect_series: one flag per member, decided per member (each keeps its fused result, or restarts at its own chunk)
+    const bool per_member = outer && series && n_members > 1;
+    const int n_flags = per_member ? n_members : 1;
     if (outer) {
         // fused kernel first, with a flag that says whether the clamp ever moved a parcel; if not, per-point and
         // outer-product clamps coincide (both are no-ops) and the fused result IS the reference's
-        LC_HIP_CHECK(hipMallocAsync((void **)&clamp_flag, sizeof(unsigned), ctx->stream));
-        (void)hipMemsetAsync(clamp_flag, 0, sizeof(unsigned), ctx->stream);
+        LC_HIP_CHECK(hipMallocAsync((void **)&clamp_flag, n_flags * sizeof(unsigned), ctx->stream));
+        (void)hipMemsetAsync(clamp_flag, 0, n_flags * sizeof(unsigned), ctx->stream);
         A.clamp_flag = clamp_flag;
+        A.clamp_stride = per_member ? 1 : 0;
     }
     A.t0 = t0;
     A.nsteps = nsteps;
@@ -4294,6 +4473,12 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
     int n_launches = 0;
     T *saved = nullptr;   // [2][ny*nx]: positions at the start of the current chunk (outer mode, from the second chunk on)
     int restart = -1;
+    // per_member: saved is [2][n_members][ny*nx] (each member's positions at the start of ITS current chunk: a member whose flag
+    // fired keeps the plane of that chunk), restarts[m] = the step member m re-enters at in the sub-step phase, -1 = not fired
+    std::vector<int> restarts(per_member ? n_members : 0, -1);
+    std::vector<unsigned> moved_m(per_member ? n_members : 0, 0u);
+    int n_fired = 0;
+    const size_t saved_planes = per_member ? (size_t)n_members : 1;
     auto flag_error = [&]() {
         lc_set_error("lc_advect: the flag all-reduce of LC_X_CLAMP_REFERENCE_OUTER failed (lc_ctx_set_flag_allreduce callback returned non-zero)");
         return LC_ERCCL;
@@ -4314,11 +4499,26 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
                 C.traj_y = A.traj_y + (size_t)s0 * plane_elems;
             }
             if (outer) {
-                if (!saved && hipMallocAsync((void **)&saved, 2 * plane_elems * sizeof(T), ctx->stream) != hipSuccess) {
+                if (!saved && hipMallocAsync((void **)&saved, 2 * saved_planes * plane_elems * sizeof(T), ctx->stream) != hipSuccess) {
                     saved = nullptr;          // no room for the saved positions: the restart is from the seed grid, as before
                     (void)hipGetLastError();  // ... and the refusal is not this call's error
                 }
-                if (saved) {
+                if (saved && per_member) {
+                    // the members still in the fused phase, in runs of consecutive members (one copy per run and plane)
+                    for (int m0 = 0; m0 < n_members;) {
+                        if (restarts[m0] >= 0) {
+                            ++m0;
+                            continue;
+                        }
+                        int m1 = m0;
+                        while (m1 < n_members && restarts[m1] < 0) ++m1;
+                        const size_t off = (size_t)m0 * plane_elems, len = (size_t)(m1 - m0) * plane_elems * sizeof(T);
+                        (void)hipMemcpyAsync(saved + off, A.x_out + off, len, hipMemcpyDeviceToDevice, ctx->stream);
+                        (void)hipMemcpyAsync(saved + saved_planes * plane_elems + off, A.y_out + off, len, hipMemcpyDeviceToDevice,
+                                             ctx->stream);
+                        m0 = m1;
+                    }
+                } else if (saved) {
                     (void)hipMemcpyAsync(saved, A.x_out, plane_elems * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream);
                     (void)hipMemcpyAsync(saved + plane_elems, A.y_out, plane_elems * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream);
                 }
@@ -4326,7 +4526,24 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
         }
         launch(C);
         ++n_launches;
-        if (outer) {
+        if (per_member) {
+            // every member's flag in one read-back (whole grids only: no flag all-reduce, lc_advect_series refuses row blocks)
+            hipError_t e1 = hipGetLastError();
+            if (e1 == hipSuccess)
+                e1 = hipMemcpyAsync(moved_m.data(), clamp_flag, n_members * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream);
+            if (e1 == hipSuccess) e1 = hipStreamSynchronize(ctx->stream);
+            if (e1 != hipSuccess) {
+                (void)hipFreeAsync(clamp_flag, ctx->stream);
+                if (saved) (void)hipFreeAsync(saved, ctx->stream);
+                LC_HIP_CHECK(e1);
+            }
+            for (int m = 0; m < n_members; ++m)
+                if (restarts[m] < 0 && moved_m[m]) {
+                    restarts[m] = lcplan::outer_restart(s0, saved != nullptr);
+                    ++n_fired;
+                }
+            if (n_fired == n_members) break;
+        } else if (outer) {
             unsigned moved = 0;
             hipError_t e1 = hipGetLastError();
             // row-sharded: "did a parcel leave the box ANYWHERE" -- every rank must take the same path below
@@ -4350,14 +4567,18 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
     if (outer) {
         (void)hipFreeAsync(clamp_flag, ctx->stream);
         A.clamp_flag = nullptr;
+        A.clamp_stride = 0;
         int rc = LC_OK;
-        if (restart >= 0) {
+        if (restart >= 0 || n_fired > 0) {
             A.ext = nullptr;  // the exact path keeps the reference's two-sample form
             A.ext_raw = 0;
             A.ext_cub = 0;
+        }
+        if (restart >= 0)
             rc = advect_outer_impl<T>(ctx, A, restart, restart > 0 ? saved : (const T *)A.x_start,
                                       restart > 0 ? saved + plane_elems : (const T *)A.y_start);
-        }
+        else if (n_fired > 0)
+            rc = advect_outer_series_impl<T>(ctx, A, restarts, saved);
         if (saved) (void)hipFreeAsync(saved, ctx->stream);
         if (rc != LC_OK) return rc;
     }
@@ -4732,7 +4953,9 @@ extern "C" int lc_advect_batch(lc_ctx *ctx, const void *packed_lin, const void *
     return lc_advect_ex(ctx, &a);
 }
 
-extern "C" int lc_advect_ex(lc_ctx *ctx, const lc_advect_args *args) {
+// lc_advect_ex, and with series = true lc_advect_series: the reference's outer clamp for n_members > 1 (a flag per member,
+// advect_outer_series_impl), whole grids only.
+static int advect_ex_checked(lc_ctx *ctx, const lc_advect_args *args, bool series) {
     LC_REQUIRE(args, "lc_advect_ex: null arguments");
     LC_REQUIRE(args->struct_size == sizeof(lc_advect_args), "lc_advect_ex: struct_size %zu, this library's lc_advect_args has %zu bytes",
                args->struct_size, sizeof(lc_advect_args));
@@ -4747,7 +4970,13 @@ extern "C" int lc_advect_ex(lc_ctx *ctx, const lc_advect_args *args) {
     const double lat_min = a.lat_min, lat_max = a.lat_max, lon_min = a.lon_min, lon_max = a.lon_max, timestep = a.timestep;
     LC_REQUIRE(n_members >= 1 && n_members <= 65535 && t0_stride >= 0, "lc_advect_batch: bad n_members %d / t0_stride %d", n_members,
                t0_stride);
-    if (n_members > 1) {
+    if (series) {
+        LC_REQUIRE(!traj_x && !traj_y, "lc_advect_series: traj_x / traj_y must be NULL");
+        if (row0 != 0 || ny != ny_global) {
+            lc_set_error("lc_advect_series: whole seed grids only (rows [%d,%d) of %d given)", row0, row0 + ny, ny_global);
+            return LC_EUNSUPPORTED;
+        }
+    } else if (n_members > 1) {
         LC_REQUIRE(!traj_x && !traj_y, "lc_advect_batch: trajectories are per member: call lc_advect for each");
         if (cyclic_x == LC_X_CLAMP_REFERENCE_OUTER) {
             lc_set_error("lc_advect_batch: LC_X_CLAMP_REFERENCE_OUTER is decided per member: call lc_advect for each");
@@ -4814,14 +5043,19 @@ extern "C" int lc_advect_ex(lc_ctx *ctx, const lc_advect_args *args) {
         return advect_impl<float>(ctx, packed_lin, packed_cub, packed_ext, u_raw, v_raw, nt, ny_f, nx_f, lat_min, lat_max, lon_min,
                                   lon_max, seed_lat_dev, ny, seed_lon_dev, nx, row0, ny_global, timestep, settls_order,
                                   interp_order, cyclic_x, t0, nsteps, x_out, y_out, traj_x, traj_y, x_start, y_start, 0,
-                                  n_members, t0_stride, 0);
+                                  n_members, t0_stride, 0, nullptr, nullptr, series);
     if (dtype == LC_F64_WIND_F32_LIN32)   // (order 1: the float32 image; order 3: the float64 coefficients + the float32 planes)
         return advect_impl<double>(ctx, nullptr, interp_order == 3 ? packed_cub : nullptr, nullptr, nullptr, nullptr, nt, ny_f, nx_f, lat_min, lat_max, lon_min,
                                    lon_max, seed_lat_dev, ny, seed_lon_dev, nx, row0, ny_global, timestep, settls_order,
                                    interp_order, cyclic_x, t0, nsteps, x_out, y_out, traj_x, traj_y, x_start, y_start,
-                                   1, n_members, t0_stride, 0, interp_order == 1 ? packed_lin : u_raw, interp_order == 3 ? v_raw : nullptr);
+                                   1, n_members, t0_stride, 0, interp_order == 1 ? packed_lin : u_raw, interp_order == 3 ? v_raw : nullptr,
+                                   series);
     return advect_impl<double>(ctx, packed_lin, packed_cub, packed_ext, u_raw, v_raw, nt, ny_f, nx_f, lat_min, lat_max, lon_min,
                                lon_max, seed_lat_dev, ny, seed_lon_dev, nx, row0, ny_global, timestep, settls_order,
                                interp_order, cyclic_x, t0, nsteps, x_out, y_out, traj_x, traj_y, x_start, y_start,
-                               dtype == LC_F64_WIND_F32, n_members, t0_stride, a.fuse_levels_raw);
+                               dtype == LC_F64_WIND_F32, n_members, t0_stride, a.fuse_levels_raw, nullptr, nullptr, series);
 }
+
+extern "C" int lc_advect_ex(lc_ctx *ctx, const lc_advect_args *args) { return advect_ex_checked(ctx, args, false); }
+
+extern "C" int lc_advect_series(lc_ctx *ctx, const lc_advect_args *args) { return advect_ex_checked(ctx, args, true); }

@@ -41,9 +41,20 @@ struct SigmaArgs {
     T *tensor;  // null, or 9 planes [n_out_rows*nx] in the reference's merge order (LCS.py:220)
 };
 
+// lc_sigma_batch: the arguments as plane blockIdx.y sees them (whole grids: [n_members][ny*nx] inputs and outputs).
+template <typename T>
+__device__ __forceinline__ SigmaArgs<T> sigma_member(const SigmaArgs<T> &A0, size_t plane) {
+    SigmaArgs<T> A = A0;
+    const size_t off = (size_t)blockIdx.y * plane;
+    A.x_dep += off;
+    A.y_dep += off;
+    A.sigma += off;
+    return A;
+}
+
 // T: arithmetic type of positions; S: type X,Y,Z are differenced in
 template <typename T, typename S>
-__global__ void __launch_bounds__(SBLOCK) sigma_kernel(const SigmaArgs<T> A) {
+__device__ __forceinline__ void sigma_body(const SigmaArgs<T> &A) {
 #pragma clang fp contract(off)
     __shared__ S sX[LH][LW + 1];
     __shared__ S sY[LH][LW + 1];
@@ -138,6 +149,15 @@ __global__ void __launch_bounds__(SBLOCK) sigma_kernel(const SigmaArgs<T> A) {
         const double lam = 0.5 * ((p + q) + disc);
         A.sigma[oidx] = (T)sqrt(lam);  // NaN in -> NaN out (Q14)
     }
+}
+template <typename T, typename S>
+__global__ void __launch_bounds__(SBLOCK) sigma_kernel(const SigmaArgs<T> A) {
+    sigma_body<T, S>(A);
+}
+// lc_sigma_batch: plane blockIdx.y of [n_members][ny*nx] inputs and outputs, the same per-cell arithmetic (sigma only).
+template <typename T, typename S>
+__global__ void __launch_bounds__(SBLOCK) sigma_batch_kernel(const SigmaArgs<T> A, size_t plane) {
+    sigma_body<T, S>(sigma_member(A, plane));
 }
 
 // ======================================================================================
@@ -234,7 +254,7 @@ __device__ __forceinline__ float sigma_from_derivatives_f32(int layout, float a_
 }
 
 // general float kernel (any width, any alignment): X, Y, Z of a 64 x 16 tile + halo through LDS
-__global__ void __launch_bounds__(SBLOCK) sigma_kernel_f32(const SigmaArgs<float> A) {
+__device__ __forceinline__ void sigma_f32_body(const SigmaArgs<float> &A) {
     __shared__ float sX[FLH][FLW + 1];
     __shared__ float sY[FLH][FLW + 1];
     __shared__ float sZ[FLH][FLW + 1];
@@ -286,6 +306,10 @@ __global__ void __launch_bounds__(SBLOCK) sigma_kernel_f32(const SigmaArgs<float
         A.sigma[(size_t)(gy - A.out_row0) * A.nx + gx] = sigma_from_derivatives_f32(A.layout, a_, b_, c_, d_, e_, f_);
     }
 }
+__global__ void __launch_bounds__(SBLOCK) sigma_kernel_f32(const SigmaArgs<float> A) { sigma_f32_body(A); }
+__global__ void __launch_bounds__(SBLOCK) sigma_batch_kernel_f32(const SigmaArgs<float> A, size_t plane) {
+    sigma_f32_body(sigma_member(A, plane));
+}
 
 // ======================================================================================
 // float, sigma only, even width: the marching kernel.  A WAVE owns a span of 128 columns (two per lane, one 8-byte
@@ -303,7 +327,7 @@ constexpr int MCOLS = 2;                 // columns per lane
 constexpr int MSPAN_OUT = 62 * MCOLS;    // columns written per wave
 
 template <int MROWS, int LAYOUT>
-__global__ void __launch_bounds__(MBLOCK) sigma_march_kernel_f32(const SigmaArgs<float> A, int nspans, int nstrips) {
+__device__ __forceinline__ void sigma_march_body(const SigmaArgs<float> &A, int nspans, int nstrips) {
     static_assert(MROWS <= 64, "row metrics live one per lane");
     const int lane = threadIdx.x & 63;
     const int w = blockIdx.x * (MBLOCK / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform
@@ -392,6 +416,14 @@ __global__ void __launch_bounds__(MBLOCK) sigma_march_kernel_f32(const SigmaArgs
         }
     }
 }
+template <int MROWS, int LAYOUT>
+__global__ void __launch_bounds__(MBLOCK) sigma_march_kernel_f32(const SigmaArgs<float> A, int nspans, int nstrips) {
+    sigma_march_body<MROWS, LAYOUT>(A, nspans, nstrips);
+}
+template <int MROWS, int LAYOUT>
+__global__ void __launch_bounds__(MBLOCK) sigma_march_batch_kernel_f32(const SigmaArgs<float> A, int nspans, int nstrips, size_t plane) {
+    sigma_march_body<MROWS, LAYOUT>(sigma_member(A, plane), nspans, nstrips);
+}
 
 template <typename T>
 int sigma_impl(lc_ctx *ctx, const void *x_dep, const void *y_dep, int in_row0, int n_in_rows, int nx, int ny_global,
@@ -448,6 +480,61 @@ int sigma_impl(lc_ctx *ctx, const void *x_dep, const void *y_dep, int in_row0, i
         hipLaunchKernelGGL((sigma_kernel<T, float>), dim3(ntx * nty), dim3(SBLOCK), 0, ctx->stream, A);
     else
         hipLaunchKernelGGL((sigma_kernel<T, double>), dim3(ntx * nty), dim3(SBLOCK), 0, ctx->stream, A);
+    LC_HIP_CHECK(hipGetLastError());
+    return LC_OK;
+}
+
+// lc_sigma_batch: n_members whole grids [n_members][ny*nx] in one launch (grid.y = member), each plane through the kernel
+// and the arithmetic lc_sigma would choose for it alone (same size rule, same alignment test).
+template <typename T>
+int sigma_batch_impl(lc_ctx *ctx, const void *x_dep, const void *y_dep, int ny, int nx, const void *seed_lat, double dlat, double dlon,
+                     int fd_fp32_cast, int layout, int n_members, void *sigma_out) {
+    SigmaArgs<T> A;
+    A.x_dep = (const T *)x_dep;
+    A.y_dep = (const T *)y_dep;
+    A.seed_lat = (const T *)seed_lat;
+    A.in_row0 = 0;
+    A.n_in_rows = ny;
+    A.nx = nx;
+    A.ny_global = ny;
+    A.dlat = (T)dlat;
+    A.dlon = (T)dlon;
+    A.layout = layout;
+    A.out_row0 = 0;
+    A.n_out_rows = ny;
+    A.sigma = (T *)sigma_out;
+    A.tensor = nullptr;
+    const size_t plane = (size_t)ny * nx;
+    if constexpr (sizeof(T) == 4) {
+        const bool march = ctx->sigma_march == 1 || (ctx->sigma_march == 2 && (long long)nx * ny >= (1ll << 23));
+        // (plane is even with nx: every member's planes keep the base's 8-byte alignment)
+        if (nx % MCOLS == 0 && nx >= 2 * MCOLS && march && (((uintptr_t)x_dep | (uintptr_t)y_dep | (uintptr_t)sigma_out) & 7) == 0) {
+            constexpr int MROWS = LCS_SIGMA_MROWS;
+            const int nspans = (nx + MSPAN_OUT - 1) / MSPAN_OUT, nstrips = (ny + MROWS - 1) / MROWS;
+            const int waves = nspans * nstrips;
+            const dim3 grid((waves + MBLOCK / 64 - 1) / (MBLOCK / 64), n_members);
+            ctx->last_sigma_kernel = "sigma_march_batch_kernel_f32";
+            if (layout == LC_LAYOUT_REFERENCE)
+                hipLaunchKernelGGL((sigma_march_batch_kernel_f32<MROWS, LC_LAYOUT_REFERENCE>), grid, dim3(MBLOCK), 0, ctx->stream, A,
+                                   nspans, nstrips, plane);
+            else
+                hipLaunchKernelGGL((sigma_march_batch_kernel_f32<MROWS, LC_LAYOUT_PHYSICAL>), grid, dim3(MBLOCK), 0, ctx->stream, A,
+                                   nspans, nstrips, plane);
+            LC_HIP_CHECK(hipGetLastError());
+            return LC_OK;
+        }
+        const int fx = (nx + FW - 1) / FW, fy = (ny + FH - 1) / FH;
+        ctx->last_sigma_kernel = "sigma_batch_kernel_f32";
+        hipLaunchKernelGGL(sigma_batch_kernel_f32, dim3(fx * fy, n_members), dim3(SBLOCK), 0, ctx->stream, A, plane);
+        LC_HIP_CHECK(hipGetLastError());
+        return LC_OK;
+    }
+    const int ntx = (nx + SW - 1) / SW, nty = (ny + SH - 1) / SH;
+    ctx->last_sigma_kernel = fd_fp32_cast ? "sigma_batch_kernel<double, float>" : "sigma_batch_kernel<double, double>";
+    if (fd_fp32_cast)
+        hipLaunchKernelGGL((sigma_batch_kernel<T, float>), dim3(ntx * nty, n_members), dim3(SBLOCK), 0, ctx->stream, A, plane);
+    else
+        hipLaunchKernelGGL((sigma_batch_kernel<T, double>), dim3(ntx * nty, n_members), dim3(SBLOCK), 0, ctx->stream, A, plane);
     LC_HIP_CHECK(hipGetLastError());
     return LC_OK;
 }
@@ -532,6 +619,22 @@ extern "C" int lc_sigma(lc_ctx *ctx, const void *x_dep, const void *y_dep, int d
                                  fd_fp32_cast, tensor_layout, out_row0, n_out_rows, sigma_out);
     return sigma_impl<double>(ctx, x_dep, y_dep, in_row0, n_in_rows, nx, ny_global, seed_lat_dev, dlat, dlon,
                               fd_fp32_cast, tensor_layout, out_row0, n_out_rows, sigma_out);
+}
+
+extern "C" int lc_sigma_batch(lc_ctx *ctx, const void *x_dep, const void *y_dep, int dtype, int ny, int nx, const void *seed_lat_dev,
+                              double dlat, double dlon, int fd_fp32_cast, int tensor_layout, int n_members, void *sigma_out) {
+    LC_REQUIRE(ctx, "lc_sigma_batch: null context");
+    LC_REQUIRE(dtype == LC_F32 || dtype == LC_F64, "lc_sigma_batch: bad dtype %d", dtype);
+    LC_REQUIRE(x_dep && y_dep && seed_lat_dev && sigma_out, "lc_sigma_batch: null pointer");
+    LC_REQUIRE(nx >= 5 && ny >= 5, "lc_sigma_batch: grid %dx%d too small for the 5-point stencil", ny, nx);
+    LC_REQUIRE(tensor_layout == LC_LAYOUT_REFERENCE || tensor_layout == LC_LAYOUT_PHYSICAL, "lc_sigma_batch: bad layout");
+    LC_REQUIRE(n_members >= 1 && n_members <= 65535, "lc_sigma_batch: bad n_members %d", n_members);
+    LC_HIP_CHECK(hipSetDevice(ctx->device));
+    if (dtype == LC_F32)
+        return sigma_batch_impl<float>(ctx, x_dep, y_dep, ny, nx, seed_lat_dev, dlat, dlon, fd_fp32_cast, tensor_layout, n_members,
+                                       sigma_out);
+    return sigma_batch_impl<double>(ctx, x_dep, y_dep, ny, nx, seed_lat_dev, dlat, dlon, fd_fp32_cast, tensor_layout, n_members,
+                                    sigma_out);
 }
 
 extern "C" int lc_flowmap_gradient(lc_ctx *ctx, const void *x_dep, const void *y_dep, int dtype, int ny, int nx,

@@ -317,3 +317,118 @@ class LCS:
         elif return_traj:
             return eigenvalues, traj("traj_x"), traj("traj_y")
         return eigenvalues
+
+    def series(self, ds=None, u=None, v=None, window=None, stride=1, verbose=True, s=None, resample=None, s_is_error=False,
+               isglobal=False, interp_to_common_grid=True, traj_interp_order=3, truncation=20):
+        """sigma_max over sliding windows of one record in one call: what the loop of LCS/area_of_influence.py:168-181 makes
+        of ``LCS(...)(ds.isel(time=np.arange(w * stride, w * stride + window)), ...)``.
+
+        ``window`` and ``stride`` count time levels of the record as given (before ``resample``); window ``w`` is the levels
+        ``[w * stride, w * stride + window)`` and there are ``(nt - window) // stride + 1`` of them.  Entry ``w`` of the result
+        is what the call on that slice returns (its time label included: the window's last time going forward, its first
+        going backward); the result has dims ``(timedim, latitude, longitude)``, and with ``return_dpts`` ``x_dep`` / ``y_dep``
+        get the same leading time dimension.  Sorting, ``resample`` (linear in time between original levels, so resampling
+        the record and slicing it gives what resampling each slice gives, except at a slice's first level: see below), the 0.5 degree regrid and the T20 truncation
+        (both level by level) run once on the whole record; the record is packed once and every window is advected in one
+        batched call (``Engine.lcs_series``).  Two places where the windows agree with the per-window calls to rounding,
+        not bit for bit: float64 at order 3 on grids of 256 rows or more (a level packed with the whole record may differ
+        in its last bits from the same level packed inside one window: the pack cuts levels into row pieces by the number
+        of levels), and -- with ``resample`` -- the first level of every window after the first: the per-window call's
+        interpolation returns the original level there, the record's the left interval's value, which can differ in the
+        last bit of the input."""
+        verboseprint = print if verbose else (lambda *a, **k: None)
+        timedim = self.timedim
+        self.verbose = verbose
+        if window is None or isinstance(window, bool) or int(window) != window or int(window) < 2:
+            raise ValueError(f"window {window!r}: at least 2 time levels")
+        if isinstance(stride, bool) or int(stride) != stride or int(stride) < 1:
+            raise ValueError(f"stride {stride!r}: at least 1 time level")
+        window, stride = int(window), int(stride)
+        if isinstance(ds, str):                                            # LCS.py:84-87
+            import xarray as xr
+            ds = xr.open_dataset(ds)
+        if ds is not None and not isinstance(ds, str):                     # LCS.py:81-83
+            u = ds.u.copy()
+            v = ds.v.copy()
+        assert set(u.dims) == set(v.dims), "u and v dims are different"                     # LCS.py:95
+        assert set(u.dims) == {'latitude', 'longitude', timedim}, \
+            'array dims should be latitude and longitude only'                             # LCS.py:96
+        t_orig = np.asarray(u[timedim].values)
+        nt = t_orig.size
+        if window > nt:
+            raise ValueError(f"window {window} is longer than the record ({nt} time levels)")
+        n_windows = (nt - window) // stride + 1
+        timestep = self.timestep
+        r = 1
+        if isinstance(resample, str):                                      # LCS.py:88-91, on the whole record
+            if _is_xarray(u):
+                u = u.resample({timedim: resample}).interpolate('linear')
+                v = v.resample({timedim: resample}).interpolate('linear')
+            else:
+                u = _resample_linear(u, timedim, resample)
+                v = _resample_linear(v, timedim, resample)
+            t_new = np.asarray(u[timedim].values)
+            r = _resample_ratio(t_orig, t_new)
+            timestep = np.sign(timestep) * (t_new[1] - t_new[0]).astype('timedelta64[s]').astype('float')
+        wlen, wstep = (window - 1) * r + 1, stride * r                    # a window and the distance between two, in levels
+
+        uu, time, lat, lon = _sorted_tll(u, timedim)                       # LCS.py:101-104
+        vv, _, _, _ = _sorted_tll(v, timedim)
+        eng = get_engine()
+        if isglobal:
+            from . import preprocess
+            if interp_to_common_grid:                                      # LCS.py:106-114
+                uu, lat_new, lon_new = preprocess.regrid_common_grid(eng, uu, lat, lon)
+                vv, _, _ = preprocess.regrid_common_grid(eng, vv, lat, lon)
+                lat, lon = lat_new, lon_new
+            if truncation is not None:                                     # LCS.py:115-118
+                gridtype = preprocess.inspect_gridtype(lat)
+                uu = preprocess.spectral_truncate(eng, uu, truncation, gridtype)
+                vv = preprocess.spectral_truncate(eng, vv, truncation, gridtype)
+            cyclic_xboundary = True                                        # LCS.py:119-120
+            self.subdomain = None
+        else:
+            cyclic_xboundary = False
+
+        verboseprint(f"*---- Parcel propagation: {n_windows} windows ----*")
+        dtype = common_dtype(uu, vv, lat, lon)
+        lat_t, lon_t = lat.astype(dtype), lon.astype(dtype)
+        # the pack of the per-window call (Engine.lcs_wind -> pack_and_advect), once for the whole record
+        fuse, ext_image = eng._pack_options(dtype, self.SETTLS_order, eng.f64_fuse_levels(dtype, lat.size * lon.size), None)
+        field = eng.prepare_field(uu, vv, lat, lon, traj_interp_order, fuse_levels=fuse, ext_image=ext_image)
+        res = eng.lcs_series(field, lat_t, lon_t, timestep, wlen - 1, n_windows, 0, wstep, SETTLS_order=self.SETTLS_order,
+                             interp_order=traj_interp_order, cyclic_xboundary=cyclic_xboundary, gauss_sigma=self.gauss_sigma)
+        verboseprint("*---- Done eigenvalues ----*")
+
+        sig = _to_np(res["sigma"])
+        slat, slon = lat, lon
+        if isinstance(self.subdomain, dict):                               # LCS.py:143-144
+            mlat, mlon = _crop_strict(lat, lon, self.subdomain)
+            sig, slat, slon = sig[:, mlat][:, :, mlon], lat[mlat], lon[mlon]
+        first = np.arange(n_windows) * wstep
+        labels = time[first + wlen - 1] if np.sign(timestep) == 1 else time[first]     # LCS.py:158, per window
+        eigenvalues = _make(u, sig, (timedim, "latitude", "longitude"),
+                            {timedim: np.asarray(labels), "latitude": slat, "longitude": slon}, getattr(u, "name", None))
+        if self.return_dpts:                                               # LCS.py:161-168
+            c3 = {timedim: np.asarray(labels), "latitude": lat, "longitude": lon}
+            return (eigenvalues, _make(u, _to_np(res["x_dep"]), (timedim, "latitude", "longitude"), c3),
+                    _make(u, _to_np(res["y_dep"]), (timedim, "latitude", "longitude"), c3))
+        return eigenvalues
+
+
+def _resample_ratio(t_orig, t_new) -> int:
+    """Resampled levels per original level: the resampled times must be uniformly spaced and hold every original time at
+    index ``i * r`` -- then each original level is a resampled one and a window of the record is a slice of the resampled
+    record (linear interpolation between two original levels reads those two only)."""
+    t_orig = np.asarray(t_orig).astype("datetime64[ns]")
+    t_new = np.asarray(t_new).astype("datetime64[ns]")
+    if t_new.size < 2 or t_orig.size < 2:
+        raise ValueError("resample: fewer than two time levels")
+    d = np.diff(t_new.astype("int64"))
+    if not np.all(d == d[0]) or d[0] <= 0:
+        raise ValueError("resample: the resampled time spacing is not uniform")
+    r, rem = divmod(int((t_orig[1] - t_orig[0]).astype("int64")), int(d[0]))
+    if rem or r < 1 or t_new.size != (t_orig.size - 1) * r + 1 or not np.array_equal(t_new[::r], t_orig):
+        raise ValueError("resample: the original levels are not every r-th level of a uniform resampled axis "
+                         "(the record's own spacing is not uniform, or the resampling frequency does not divide it)")
+    return r

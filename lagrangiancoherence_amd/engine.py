@@ -963,6 +963,23 @@ class Engine:
         form stays available (``pack_and_advect(pipeline=True)``, bit-identical)."""
         return False
 
+    @staticmethod
+    def _pack_options(dtype, SETTLS_order, fuse_levels, ext_image):
+        """``(fuse_levels, ext_image)`` that :meth:`pack_and_advect` hands :meth:`prepare_field` for a call of this SETTLS order."""
+        if fuse_levels is None:
+            fuse_levels = True
+        if int(SETTLS_order) == 0 and fuse_levels and ext_image is None:
+            # SETTLS_order = 0 (the library default, LCS/trajectory.py:14) takes one Euler sample per level and never reads the
+            # fused-level image: it is not built.  float64: the kernels' no-image forms (the same Euler sample, bit for bit --
+            # at order 1 no packed image at all, at order 3 the coefficients only); float32: the order-1 / coefficient image only.
+            # configs[1] at K = 0: pack 1.29 -> 0 ms (order 1), 3.17 -> 1.85 ms (order 3).  The field returned holds what THIS
+            # call needed: advected again with SETTLS_order > 0 it takes the two-sample form.
+            if np.dtype(dtype) != np.dtype(np.float32):
+                ext_image = False
+            else:
+                fuse_levels = False
+        return fuse_levels, ext_image
+
     def pack_and_advect(self, u, v, lat_f, lon_f, seed_lat, seed_lon, timestep, SETTLS_order=0, interp_order=1,
                         cyclic_xboundary=True, fuse_levels=None, pipeline=None, chunk=None, return_traj=False,
                         noncyclic_clamp=None, ext_image=None):
@@ -977,18 +994,7 @@ class Engine:
         torch = self.torch
         lat_f, lon_f = np.asarray(lat_f), np.asarray(lon_f)
         dtype = common_dtype(u, v, lat_f, lon_f)
-        if fuse_levels is None:
-            fuse_levels = True
-        if int(SETTLS_order) == 0 and fuse_levels and ext_image is None:
-            # SETTLS_order = 0 (the library default, LCS/trajectory.py:14) takes one Euler sample per level and never reads the
-            # fused-level image: it is not built.  float64: the kernels' no-image forms (the same Euler sample, bit for bit --
-            # at order 1 no packed image at all, at order 3 the coefficients only); float32: the order-1 / coefficient image only.
-            # configs[1] at K = 0: pack 1.29 -> 0 ms (order 1), 3.17 -> 1.85 ms (order 3).  The field returned holds what THIS
-            # call needed: advected again with SETTLS_order > 0 it takes the two-sample form.
-            if dtype != np.dtype(np.float32):
-                ext_image = False
-            else:
-                fuse_levels = False
+        fuse_levels, ext_image = self._pack_options(dtype, SETTLS_order, fuse_levels, ext_image)
         nt = int(u.shape[0])
         ny, nx = len(seed_lat), len(seed_lon)
         if pipeline is None:
@@ -1095,6 +1101,79 @@ class Engine:
         if return_traj:
             out["traj_x"], out["traj_y"] = res[2], res[3]
         return out
+
+    # device memory one lcs_series group may hold (positions, saved positions and Euler samples of the outer rule, sigma)
+    SERIES_MEM_CAP = 2 << 30
+
+    def series_group(self, dtype, n_seeds: int, n_windows: int, cyclic_xboundary=True) -> int:
+        """Windows per :meth:`lcs_series` group: as many as fit ``SERIES_MEM_CAP`` (at least one).  Per window: x, y and sigma,
+        plus -- under the reference's non-cyclic clamp -- the positions saved before each chunk and the Euler sample of the
+        sub-step phase (two planes each), and the smoothing's two scratch planes."""
+        planes = 5 if cyclic_xboundary else 9
+        per = planes * int(n_seeds) * np.dtype(dtype).itemsize
+        return max(1, min(int(n_windows), int(self.SERIES_MEM_CAP) // max(per, 1)))
+
+    def lcs_series(self, field: PackedField, seed_lat, seed_lon, timestep, nsteps: int, n_windows: int, t0=0, t0_stride=1,
+                   SETTLS_order=0, interp_order=1, cyclic_xboundary=True, gauss_sigma=None, fd_fp32_cast=True,
+                   tensor_layout="reference", noncyclic_clamp=None):
+        """:meth:`lcs` over ``n_windows`` sliding windows of one packed field: window ``m`` runs ``nsteps`` steps from level
+        ``t0 + m * t0_stride``.  Returns ``{"sigma", "x_dep", "y_dep"}`` as ``(n_windows, ny, nx)`` device tensors; entry ``m``
+        equals ``lcs(field, ..., t0=t0 + m * t0_stride, nsteps=nsteps)`` bit for bit.
+
+        One ``lc_advect_series`` call (every window in one launch per level chunk; with the reference's non-cyclic clamp each
+        window decides on its own whether and from which chunk it re-runs sub-step by sub-step) and one ``lc_sigma_batch``
+        call per group of windows; groups are as large as ``SERIES_MEM_CAP`` allows (:meth:`series_group`), and the results
+        do not depend on the grouping."""
+        if interp_order != 1 and field.order != interp_order:
+            raise ValueError(f"field was prepared for interp_order={field.order}")
+        n_windows, nsteps, t0, t0_stride = int(n_windows), int(nsteps), int(t0), int(t0_stride)
+        if n_windows < 1 or nsteps < 0 or t0 < 0 or t0_stride < 0:
+            raise ValueError(f"lcs_series: n_windows {n_windows}, nsteps {nsteps}, t0 {t0}, t0_stride {t0_stride}")
+        dtype = field.dtype
+        seed_lat = np.asarray(seed_lat, dtype=dtype)
+        seed_lon = np.asarray(seed_lon, dtype=dtype)
+        slat, slon = self.to_device(seed_lat, dtype), self.to_device(seed_lon, dtype)
+        ny, nx = int(slat.numel()), int(slon.numel())
+        x, y, sig = (self._empty((n_windows, ny, nx), dtype) for _ in range(3))
+        xmode = x_boundary_mode(cyclic_xboundary, noncyclic_clamp, True)
+        smooth = isinstance(gauss_sigma, (float, int)) and not isinstance(gauss_sigma, bool) and gauss_sigma > 1e-15
+        dlat = float(seed_lat[1] - seed_lat[0])     # as _sigma_of: the spacing in the coordinate dtype (tools.py:255-256)
+        dlon = float(seed_lon[1] - seed_lon[0])
+        g = self.series_group(dtype, ny * nx, n_windows, cyclic_xboundary)
+        for m0 in range(0, n_windows, g):
+            n = min(g, n_windows - m0)
+            xg, yg = x[m0:m0 + n], y[m0:m0 + n]
+            self._use_current_stream()
+            a = self._advect_args(field, interp_order, slat, ny, slon, nx, 0, ny, None, None, timestep, SETTLS_order, xmode,
+                                  t0 + m0 * t0_stride, nsteps, n, t0_stride, xg, yg, None, None)
+            _capi.check(self.lib.lc_advect_series(self.ctx, C.byref(a)), self.lib)
+            xs, ys = xg, yg
+            if smooth:     # scipy's gaussian_filter of each window's departure points (LCS/LCS.py:187-190), as _sigma_of
+                xs = self.torch.stack([self.gaussian_filter(xg[i], gauss_sigma) for i in range(n)])
+                ys = self.torch.stack([self.gaussian_filter(yg[i], gauss_sigma) for i in range(n)])
+            self._use_current_stream()
+            _capi.check(self.lib.lc_sigma_batch(self.ctx, self._ptr(xs), self._ptr(ys), _NP2LC[dtype], ny, nx, self._ptr(slat),
+                                                dlat, dlon, int(bool(fd_fp32_cast)), _LAYOUTS[tensor_layout], n,
+                                                self._ptr(sig[m0:m0 + n])), self.lib)
+        return {"sigma": sig, "x_dep": x, "y_dep": y}
+
+    def sigma_batch(self, x_dep, y_dep, seed_lat, dlat, dlon, fd_fp32_cast=True, tensor_layout="reference"):
+        """sigma_max of ``n`` whole grids at once (``lc_sigma_batch``): ``x_dep``, ``y_dep`` ``(n, ny, nx)``; plane ``m`` of the
+        result equals :meth:`sigma` of plane ``m`` bit for bit."""
+        torch = self.torch
+        dtype = np.dtype(str(x_dep.dtype).replace("torch.", "")) if isinstance(x_dep, torch.Tensor) else common_dtype(x_dep, y_dep)
+        xd, yd = self.to_device(x_dep, dtype), self.to_device(y_dep, dtype)
+        if xd.dim() != 3 or tuple(yd.shape) != tuple(xd.shape):
+            raise ValueError("x_dep and y_dep must both be (n, ny, nx)")
+        n, ny, nx = (int(s) for s in xd.shape)
+        slat = self.to_device(seed_lat, dtype)
+        if slat.numel() != ny:
+            raise ValueError("seed_lat must have one latitude per row")
+        sig = self._empty((n, ny, nx), dtype)
+        self._use_current_stream()
+        _capi.check(self.lib.lc_sigma_batch(self.ctx, self._ptr(xd), self._ptr(yd), _NP2LC[dtype], ny, nx, self._ptr(slat), float(dlat),
+                                            float(dlon), int(bool(fd_fp32_cast)), _LAYOUTS[tensor_layout], n, self._ptr(sig)), self.lib)
+        return sig
 
     def synchronize(self):
         self.torch.cuda.synchronize(self.device)
