@@ -38,7 +38,7 @@ extern "C" {
  * client built against 100 must be rebuilt), lc_ctx_get_level_chunk, lc_ctx_set/get_f64_fidelity, lc_advect_ex and
  * lc_sample_raw added, lc_field_pack accepts packed_dev == NULL at order 1 (fused-level image only).  lc_version() returns the value the LIBRARY
  * was built with: compare it with this macro before any other call (tests/c/abi_smoke.c, _capi.load do). */
-#define LC_VERSION 104 /* 0.1.4: + lc_advect_series, lc_sigma_batch, + lc_tracer_sample, lc_ctx_last_tracer_kernel (additive: no argument list changed), + lc_ctx_set_host_pipeline, lc_copy_to_device, lc_copy_to_host, lc_ctx_set_host_cache, lc_ctx_trim, lc_ctx_last_host_marks, lc_ctx_set_xcd_split (0.1.3: + lc_ctx_last_pack_kernel; 0.1.2: + lc_ctx_set_verify, lc_ctx_read_verify, LC_F64_WIND_F32_LIN32) */
+#define LC_VERSION 104 /* 0.1.4: + lc_advect_series_dirs, + lc_advect_series, lc_sigma_batch, + lc_tracer_sample, lc_ctx_last_tracer_kernel (additive: no argument list changed), + lc_ctx_set_host_pipeline, lc_copy_to_device, lc_copy_to_host, lc_ctx_set_host_cache, lc_ctx_trim, lc_ctx_last_host_marks, lc_ctx_set_xcd_split (0.1.3: + lc_ctx_last_pack_kernel; 0.1.2: + lc_ctx_set_verify, lc_ctx_read_verify, LC_F64_WIND_F32_LIN32) */
 
 typedef struct lc_ctx lc_ctx;
 
@@ -438,6 +438,20 @@ int lc_advect_ex(lc_ctx *ctx, const lc_advect_args *args);
  * lc_advect_ex(t0 + m * t0_stride, n_members = 1) gives.  No flag all-reduce is made (lc_ctx_set_flag_allreduce is for
  * row blocks). */
 int lc_advect_series(lc_ctx *ctx, const lc_advect_args *args);
+
+/* lc_advect_series in both directions of time at once: the reference example's pair of calls
+ * LCS(timestep=+dt)(ds) and LCS(timestep=-dt)(ds) (examples/ideal_vortex.py:280-288) on one packed record.  Quirk Q6: the
+ * reference reads the levels in stored order whatever the sign of timestep (LCS/trajectory.py:58-60,80-84,105-108), so both
+ * directions read the same levels.
+ * n_dirs = 1 is lc_advect_series.  n_dirs = 2: x_out / y_out hold 2 * n_members planes [2 * n_members][ny*nx]; plane
+ * 2w + d is window w (nsteps steps from level t0 + w * t0_stride), with args->timestep for d = 0 and -args->timestep for
+ * d = 1, and equals lc_advect_ex(t0 + w * t0_stride, +-timestep, n_members = 1) bit for bit (T(-x) == -T(x): each plane's
+ * kernel sees the four step constants that call forms).  The outer clamp
+ * (LC_X_CLAMP_REFERENCE_OUTER) is decided per plane, as lc_advect_series decides it per window.  Each level chunk makes
+ * one fused launch per direction, the launches lc_advect_series makes for the same windows (lc_ctx_last_advect_kernel
+ * names the same kernel).  Refused before any HIP call: what lc_advect_series refuses (row blocks, traj_x / traj_y), and
+ * n_dirs other than 1 or 2 (LC_EINVAL).  The level range is checked in windows. */
+int lc_advect_series_dirs(lc_ctx *ctx, const lc_advect_args *args, int n_dirs);
 
 /* One interpolation pass on its own: tools.xr_map_coordinates (LCS/tools.py:11-41) for the
  * u and v fields of time level `level` at the given positions (degrees), same index

@@ -111,6 +111,7 @@ class AdvectArgs(C.Structure):
 
 PROTOTYPES["lc_advect_ex"] = (_i, [_vp, C.POINTER(AdvectArgs)])
 PROTOTYPES["lc_advect_series"] = (_i, [_vp, C.POINTER(AdvectArgs)])
+PROTOTYPES["lc_advect_series_dirs"] = (_i, [_vp, C.POINTER(AdvectArgs), _i])
 
 
 class TracerArgs(C.Structure):

@@ -90,6 +90,8 @@ struct AdvectArgs {
     unsigned *clamp_flag;  // NULL, or set to 1 when the non-cyclic longitude clamp moves any parcel (Q9)
     int clamp_stride;      // lc_advect_series: member m's flag is clamp_flag[m * clamp_stride] (0: one flag for the launch)
     unsigned *verify;      // NULL, or the context's 16 wave-state counters (lc_ctx_set_verify: the one-seed order-1 LDS kernel's VERIFY instances)
+    int member_dirs;       // lc_advect_series_dirs, sub-step kernels of the outer clamp: 1 = member 2w + d is window w (level
+                           // t0 + w * member_t0_stride), d = 1 with -timestep (member_direction)
 };
 
 // Tile of a workgroup.  Hardware deals workgroups to the 8 XCDs round-robin (blockIdx % 8), each with its own L2.
@@ -127,6 +129,22 @@ __device__ __forceinline__ T start_x(const AdvectArgs<T> &A, int iy, int ix) {
 template <typename T>
 __device__ __forceinline__ T start_y(const AdvectArgs<T> &A, int iy, int ix) {
     return A.y_start ? A.y_start[(size_t)iy * A.nx + ix] : A.seed_lat[iy];
+}
+
+// lc_advect_series_dirs: plane m = 2w + d is window w, and d = 1 integrates with -timestep.  The host forms dt, half_dt,
+// dtcy and hdtcy as T(c * timestep); under round-to-nearest T(-x) == -T(x), so negating them is exactly what a call with
+// -timestep is given (and every product the kernels form from them, dtcx = dt * cx_conv included, is odd in them too).
+// The fused launches get direction d's constants from the host (advect_impl: one ensemble launch per direction); the
+// sub-step kernels of the outer clamp, which cover every plane in one launch, apply this per member.
+template <typename T>
+__host__ __device__ __forceinline__ void member_direction(AdvectArgs<T> &A, const AdvectArgs<T> &A0, int m) {
+    A.t0 = A0.t0 + (m >> 1) * A0.member_t0_stride;
+    if (m & 1) {
+        A.dt = -A0.dt;
+        A.half_dt = -A0.half_dt;
+        A.dtcy = -A0.dtcy;
+        A.hdtcy = -A0.hdtcy;
+    }
 }
 
 // lc_advect_batch: the arguments as ensemble member blockIdx.y sees them (a no-op for every other call: gridDim.y == 1).
@@ -4010,7 +4028,8 @@ __global__ void outer_store_kernel(const AdvectArgs<T> A, const OuterArgs<T> O, 
 }
 
 // lc_advect_series with LC_X_CLAMP_REFERENCE_OUTER: the sub-step phase of every member whose parcels left the box, one
-// launch per sub-step for all of them.  Member m = blockIdx.y reads level t0 + m * member_t0_stride + s and keeps its own
+// launch per sub-step for all of them.  Member m = blockIdx.y reads level t0 + m * member_t0_stride + s (lc_advect_series_dirs:
+// t0 + (m >> 1) * member_t0_stride + s, odd members with -timestep) and keeps its own
 // positions (the m-th plane of x_out / y_out), Euler sample (the m-th plane of eu and of ev) and 2 (ny + nx) flag words
 // (rlo + m * nflag ...), double-buffered by sub-step like outer_substep_kernel's.  It enters at its own restart step (the
 // first step of the chunk in which its flag fired) from the positions saved before that chunk; a member whose flag never
@@ -4051,10 +4070,15 @@ __global__ void outer_substep_batch_kernel(const AdvectArgs<T> A, const OuterArg
     const int r = S.restart[m];
     if (r < 0 || s < r) return;
     const OuterArgs<T> O = outer_member<T>(O0, S, m, !is_iter && s == r);
-    const int level = A.t0 + m * A.member_t0_stride + s;
+    AdvectArgs<T> Am = A;
+    int level = A.t0 + m * A.member_t0_stride + s;
+    if (A.member_dirs) {  // lc_advect_series_dirs: window m >> 1, odd members with -timestep
+        member_direction(Am, A, m);
+        level = Am.t0 + s;
+    }
     const size_t n = (size_t)A.ny * A.nx;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        outer_substep_seed<T, ORDER>(A, O, level, is_iter, i);
+        outer_substep_seed<T, ORDER>(Am, O, level, is_iter, i);
 }
 
 template <typename T>
@@ -4254,8 +4278,9 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
                 const void *seed_lon, int nx, int row0, int ny_global, double timestep, int K, int order, int cyclic,
                 int t0, int nsteps, void *x_out, void *y_out, void *traj_x, void *traj_y, const void *x_start,
                 const void *y_start, int wind_f32 = 0, int n_members = 1, int t0_stride = 0, int fuse_levels_raw = 0,
-                const void *lin32 = nullptr, const void *lin32_v = nullptr, bool series = false) {
+                const void *lin32 = nullptr, const void *lin32_v = nullptr, bool series = false, int dirs = 1) {
     AdvectArgs<T> A{};
+    A.member_dirs = dirs == 2;  // lc_advect_series_dirs: n_members = 2 x windows, plane 2w + d (see the level chunks below)
     A.wind_f32 = wind_f32;
     A.n_members = n_members;
     A.member_t0_stride = t0_stride;
@@ -4456,21 +4481,50 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
     // (d = t0_stride), so the group shares its tiles for nsteps - (g - 1) d of them; continuation in place as for any chunk.
     // (four members per lane -- 99 VGPRs, the members of a lane up to 3 d levels of travel apart -- measured 480 ms on
     // config 5 against 280 for pairs: in the jets three steps are 6 cells, nearly every wave-sample has a lane outside the tile)
-    const bool pairs_ok = n_members > 1 && order == 1 && !outer && !traj_x && use_lds &&
+    // lc_advect_series_dirs: each level chunk makes one ensemble launch per direction over the n_members / 2 windows, with
+    // direction d's step constants (member_direction) and its planes 2w + d (x_out + d planes, member_plane = 2 planes), so
+    // the fused kernels are the ones lc_advect_series launches, unchanged; the member-pair grouping then pairs windows of
+    // one direction, t0_stride apart, as it does for lc_advect_series.
+    const int n_dir = A.member_dirs ? 2 : 1;
+    const int n_launch = n_members / n_dir;  // members of one fused launch
+    A.n_members = n_launch;  // (the kernel choice by size counts a launch's members: lc_advect_series's for the same windows)
+    const bool pairs_ok = n_launch > 1 && order == 1 && !outer && !traj_x && use_lds &&
                           (ctx->patch_mode < 0 || ctx->patch_mode == PATCH_PAIR) && K > 0 && order1_two_seed_applies(A, ctx->lds_tiles);
-    const lcplan::Groups G = lcplan::member_groups(n_members, t0_stride, nsteps, pairs_ok);
+    const lcplan::Groups G = lcplan::member_groups(n_launch, t0_stride, nsteps, pairs_ok);
     const int total = G.total;
+    A.member_plane = (size_t)n_dir * plane_elems;
     if (G.g) {
         A.pair_d = t0_stride;
         A.pair_n = nsteps;
-        A.pair_plane = plane_elems;
+        A.pair_plane = (size_t)n_dir * plane_elems;
         A.pair_g = G.g;
         A.pair_last = G.last;
         A.n_members = G.n_groups;
         A.member_t0_stride = G.group_stride;
-        A.member_plane = (size_t)G.g * plane_elems;
+        A.member_plane = (size_t)G.g * n_dir * plane_elems;
     }
+    if (per_member) A.clamp_stride = n_dir;  // plane 2w + d's flag: clamp_flag + d + w * 2
     int n_launches = 0;
+    auto launch_dirs = [&](const AdvectArgs<T> &C) {
+        if (n_dir == 1) {
+            launch(C);
+            ++n_launches;
+            return;
+        }
+        for (int d = 0; d < 2; ++d) {
+            AdvectArgs<T> D = C;
+            member_direction(D, C, d);  // (d < 2: t0 unchanged)
+            D.x_out = C.x_out + (size_t)d * plane_elems;
+            D.y_out = C.y_out + (size_t)d * plane_elems;
+            if (C.x_start) {
+                D.x_start = C.x_start + (size_t)d * plane_elems;
+                D.y_start = C.y_start + (size_t)d * plane_elems;
+            }
+            if (C.clamp_flag) D.clamp_flag = C.clamp_flag + d;
+            launch(D);
+            ++n_launches;
+        }
+    };
     T *saved = nullptr;   // [2][ny*nx]: positions at the start of the current chunk (outer mode, from the second chunk on)
     int restart = -1;
     // per_member: saved is [2][n_members][ny*nx] (each member's positions at the start of ITS current chunk: a member whose flag
@@ -4483,7 +4537,7 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
         lc_set_error("lc_advect: the flag all-reduce of LC_X_CLAMP_REFERENCE_OUTER failed (lc_ctx_set_flag_allreduce callback returned non-zero)");
         return LC_ERCCL;
     };
-    const int chunk = lcplan::level_chunk(ctx->level_chunk, outer, (long long)ny * nx, n_members, K, total, sizeof(T) == 8 && order == 1);
+    const int chunk = lcplan::level_chunk(ctx->level_chunk, outer, (long long)ny * nx, n_launch, K, total, sizeof(T) == 8 && order == 1);
     for (int ci = 0, nci = lcplan::n_chunks(total, chunk); ci < nci; ++ci) {
         const int s0 = lcplan::chunk_first(ci, chunk);
         AdvectArgs<T> C = A;
@@ -4524,8 +4578,7 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
                 }
             }
         }
-        launch(C);
-        ++n_launches;
+        launch_dirs(C);
         if (per_member) {
             // every member's flag in one read-back (whole grids only: no flag all-reduce, lc_advect_series refuses row blocks)
             hipError_t e1 = hipGetLastError();
@@ -4568,6 +4621,8 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
         (void)hipFreeAsync(clamp_flag, ctx->stream);
         A.clamp_flag = nullptr;
         A.clamp_stride = 0;
+        A.n_members = n_members;  // the sub-step phase: every plane, one member each (outer: no member groups)
+        A.member_plane = plane_elems;
         int rc = LC_OK;
         if (restart >= 0 || n_fired > 0) {
             A.ext = nullptr;  // the exact path keeps the reference's two-sample form
@@ -4954,11 +5009,13 @@ extern "C" int lc_advect_batch(lc_ctx *ctx, const void *packed_lin, const void *
 }
 
 // lc_advect_ex, and with series = true lc_advect_series: the reference's outer clamp for n_members > 1 (a flag per member,
-// advect_outer_series_impl), whole grids only.
-static int advect_ex_checked(lc_ctx *ctx, const lc_advect_args *args, bool series) {
+// advect_outer_series_impl), whole grids only.  dirs = 2 (lc_advect_series_dirs): every window in both directions of time,
+// 2 x n_members planes, plane 2w + d with -timestep for d = 1.
+static int advect_ex_checked(lc_ctx *ctx, const lc_advect_args *args, bool series, int dirs = 1) {
     LC_REQUIRE(args, "lc_advect_ex: null arguments");
     LC_REQUIRE(args->struct_size == sizeof(lc_advect_args), "lc_advect_ex: struct_size %zu, this library's lc_advect_args has %zu bytes",
                args->struct_size, sizeof(lc_advect_args));
+    LC_REQUIRE(dirs == 1 || dirs == 2, "lc_advect_series_dirs: n_dirs %d (1 or 2)", dirs);
     LC_REQUIRE(ctx, "lc_advect: null context");
     const lc_advect_args &a = *args;
     const void *packed_lin = a.packed_lin, *packed_cub = a.packed_cub, *packed_ext = a.packed_ext, *u_raw = a.u_raw, *v_raw = a.v_raw;
@@ -4968,7 +5025,7 @@ static int advect_ex_checked(lc_ctx *ctx, const lc_advect_args *args, bool serie
     const void *x_start = a.x_start, *y_start = a.y_start, *seed_lat_dev = a.seed_lat_dev, *seed_lon_dev = a.seed_lon_dev;
     void *x_out = a.x_out, *y_out = a.y_out, *traj_x = a.traj_x, *traj_y = a.traj_y;
     const double lat_min = a.lat_min, lat_max = a.lat_max, lon_min = a.lon_min, lon_max = a.lon_max, timestep = a.timestep;
-    LC_REQUIRE(n_members >= 1 && n_members <= 65535 && t0_stride >= 0, "lc_advect_batch: bad n_members %d / t0_stride %d", n_members,
+    LC_REQUIRE(n_members >= 1 && n_members * dirs <= 65535 && t0_stride >= 0, "lc_advect_batch: bad n_members %d / t0_stride %d", n_members,
                t0_stride);
     if (series) {
         LC_REQUIRE(!traj_x && !traj_y, "lc_advect_series: traj_x / traj_y must be NULL");
@@ -5043,19 +5100,23 @@ static int advect_ex_checked(lc_ctx *ctx, const lc_advect_args *args, bool serie
         return advect_impl<float>(ctx, packed_lin, packed_cub, packed_ext, u_raw, v_raw, nt, ny_f, nx_f, lat_min, lat_max, lon_min,
                                   lon_max, seed_lat_dev, ny, seed_lon_dev, nx, row0, ny_global, timestep, settls_order,
                                   interp_order, cyclic_x, t0, nsteps, x_out, y_out, traj_x, traj_y, x_start, y_start, 0,
-                                  n_members, t0_stride, 0, nullptr, nullptr, series);
+                                  n_members * dirs, t0_stride, 0, nullptr, nullptr, series, dirs);
     if (dtype == LC_F64_WIND_F32_LIN32)   // (order 1: the float32 image; order 3: the float64 coefficients + the float32 planes)
         return advect_impl<double>(ctx, nullptr, interp_order == 3 ? packed_cub : nullptr, nullptr, nullptr, nullptr, nt, ny_f, nx_f, lat_min, lat_max, lon_min,
                                    lon_max, seed_lat_dev, ny, seed_lon_dev, nx, row0, ny_global, timestep, settls_order,
                                    interp_order, cyclic_x, t0, nsteps, x_out, y_out, traj_x, traj_y, x_start, y_start,
-                                   1, n_members, t0_stride, 0, interp_order == 1 ? packed_lin : u_raw, interp_order == 3 ? v_raw : nullptr,
-                                   series);
+                                   1, n_members * dirs, t0_stride, 0, interp_order == 1 ? packed_lin : u_raw, interp_order == 3 ? v_raw : nullptr,
+                                   series, dirs);
     return advect_impl<double>(ctx, packed_lin, packed_cub, packed_ext, u_raw, v_raw, nt, ny_f, nx_f, lat_min, lat_max, lon_min,
                                lon_max, seed_lat_dev, ny, seed_lon_dev, nx, row0, ny_global, timestep, settls_order,
                                interp_order, cyclic_x, t0, nsteps, x_out, y_out, traj_x, traj_y, x_start, y_start,
-                               dtype == LC_F64_WIND_F32, n_members, t0_stride, a.fuse_levels_raw, nullptr, nullptr, series);
+                               dtype == LC_F64_WIND_F32, n_members * dirs, t0_stride, a.fuse_levels_raw, nullptr, nullptr, series, dirs);
 }
 
 extern "C" int lc_advect_ex(lc_ctx *ctx, const lc_advect_args *args) { return advect_ex_checked(ctx, args, false); }
 
 extern "C" int lc_advect_series(lc_ctx *ctx, const lc_advect_args *args) { return advect_ex_checked(ctx, args, true); }
+
+extern "C" int lc_advect_series_dirs(lc_ctx *ctx, const lc_advect_args *args, int n_dirs) {
+    return advect_ex_checked(ctx, args, true, n_dirs);
+}

@@ -415,6 +415,115 @@ class LCS:
                     _make(u, _to_np(res["y_dep"]), (timedim, "latitude", "longitude"), c3))
         return eigenvalues
 
+    def bidirectional(self, ds=None, u=None, v=None, window=None, stride=1, verbose=True, s=None, resample=None,
+                      s_is_error=False, isglobal=False, interp_to_common_grid=True, traj_interp_order=3, truncation=20):
+        """The attracting and the repelling field of one record in one call: ``(attracting, repelling)``, what the reference's
+        example computes with two calls (examples/ideal_vortex.py:280-288).
+
+        ``window=None``: ``attracting`` is what ``LCS(timestep=-abs(timestep), same ctor args)(ds, same call args)`` returns
+        and ``repelling`` the same with ``+abs(timestep)`` (values, dims, the time labels of LCS.py:158 and the tuple of
+        ``return_dpts``).  ``window=k``: the same against ``.series(ds, window=k, stride=stride, ...)`` for each sign.
+        Sorting, ``resample``, the regrid and T20 and the pack run once; then one ``lc_advect_series_dirs`` call and one
+        ``lc_sigma_batch`` call per memory group (``Engine.lcs_bidirectional``).  The levels are read in stored order in
+        both directions, so both directions advect over the same packed record.  Bit-identical to the
+        single-direction calls except where :meth:`series` is not (its docstring): with ``window=None`` only float64 order 3
+        on grids of 256 rows or more can differ, to rounding."""
+        verboseprint = print if verbose else (lambda *a, **k: None)
+        timedim = self.timedim
+        self.verbose = verbose
+        if not self.timestep:
+            raise ValueError(f"timestep {self.timestep!r}: bidirectional needs a non-zero step (its sign is ignored)")
+        if window is not None:                                             # as series
+            if isinstance(window, bool) or int(window) != window or int(window) < 2:
+                raise ValueError(f"window {window!r}: at least 2 time levels")
+            if isinstance(stride, bool) or int(stride) != stride or int(stride) < 1:
+                raise ValueError(f"stride {stride!r}: at least 1 time level")
+            window, stride = int(window), int(stride)
+        if isinstance(ds, str):                                            # LCS.py:84-87
+            import xarray as xr
+            ds = xr.open_dataset(ds)
+        if ds is not None and not isinstance(ds, str):                     # LCS.py:81-83
+            u = ds.u.copy()
+            v = ds.v.copy()
+        assert set(u.dims) == set(v.dims), "u and v dims are different"                     # LCS.py:95
+        assert set(u.dims) == {'latitude', 'longitude', timedim}, \
+            'array dims should be latitude and longitude only'                             # LCS.py:96
+        t_orig = np.asarray(u[timedim].values)
+        nt = t_orig.size
+        if window is not None and window > nt:
+            raise ValueError(f"window {window} is longer than the record ({nt} time levels)")
+        step = abs(self.timestep)
+        r = 1
+        if isinstance(resample, str):                                      # LCS.py:88-91, on the whole record
+            if _is_xarray(u):
+                u = u.resample({timedim: resample}).interpolate('linear')
+                v = v.resample({timedim: resample}).interpolate('linear')
+            else:
+                u = _resample_linear(u, timedim, resample)
+                v = _resample_linear(v, timedim, resample)
+            t_new = np.asarray(u[timedim].values)
+            if window is not None:
+                r = _resample_ratio(t_orig, t_new)
+            step = (t_new[1] - t_new[0]).astype('timedelta64[s]').astype('float')
+        if window is None:                                                 # one window: the whole (resampled) record
+            n_windows, wlen, wstep = 1, int(np.asarray(u[timedim].values).size), 1
+        else:
+            n_windows = (nt - window) // stride + 1
+            wlen, wstep = (window - 1) * r + 1, stride * r
+
+        uu, time, lat, lon = _sorted_tll(u, timedim)                       # LCS.py:101-104
+        vv, _, _, _ = _sorted_tll(v, timedim)
+        eng = get_engine()
+        if isglobal:
+            from . import preprocess
+            if interp_to_common_grid:                                      # LCS.py:106-114
+                uu, lat_new, lon_new = preprocess.regrid_common_grid(eng, uu, lat, lon)
+                vv, _, _ = preprocess.regrid_common_grid(eng, vv, lat, lon)
+                lat, lon = lat_new, lon_new
+            if truncation is not None:                                     # LCS.py:115-118
+                gridtype = preprocess.inspect_gridtype(lat)
+                uu = preprocess.spectral_truncate(eng, uu, truncation, gridtype)
+                vv = preprocess.spectral_truncate(eng, vv, truncation, gridtype)
+            cyclic_xboundary = True                                        # LCS.py:119-120
+            self.subdomain = None
+        else:
+            cyclic_xboundary = False
+
+        verboseprint(f"*---- Parcel propagation: {n_windows} window(s), both directions ----*")
+        dtype = common_dtype(uu, vv, lat, lon)
+        lat_t, lon_t = lat.astype(dtype), lon.astype(dtype)
+        # the pack of the single-direction call (Engine.lcs_wind -> pack_and_advect), once for both directions
+        fuse, ext_image = eng._pack_options(dtype, self.SETTLS_order, eng.f64_fuse_levels(dtype, lat.size * lon.size), None)
+        field = eng.prepare_field(uu, vv, lat, lon, traj_interp_order, fuse_levels=fuse, ext_image=ext_image)
+        res = eng.lcs_bidirectional(field, lat_t, lon_t, step, wlen - 1, n_windows, 0, wstep, SETTLS_order=self.SETTLS_order,
+                                    interp_order=traj_interp_order, cyclic_xboundary=cyclic_xboundary,
+                                    gauss_sigma=self.gauss_sigma)
+        verboseprint("*---- Done eigenvalues ----*")
+
+        sig_all, x_all, y_all = (_to_np(res[k]) for k in ("sigma", "x_dep", "y_dep"))
+        slat, slon = lat, lon
+        if isinstance(self.subdomain, dict):                               # LCS.py:143-144
+            mlat, mlon = _crop_strict(lat, lon, self.subdomain)
+            sig_all, slat, slon = sig_all[:, :, mlat][:, :, :, mlon], lat[mlat], lon[mlon]
+        first = np.arange(n_windows) * wstep
+        name = getattr(u, "name", None)
+        dims3 = (timedim, "latitude", "longitude")
+        out = []
+        for d, forward in ((0, False), (1, True)):
+            labels = time[first + wlen - 1] if forward else time[first]    # LCS.py:158, per window
+            eigenvalues = _make(u, sig_all[d], dims3, {timedim: np.asarray(labels), "latitude": slat, "longitude": slon}, name)
+            if not self.return_dpts:
+                out.append(eigenvalues)
+            elif window is None:                                           # as __call__: (lat, lon) with a scalar time label
+                times = time.tolist()
+                c2 = {"latitude": lat, "longitude": lon, timedim: times[-1] if forward else times[0]}
+                out.append((eigenvalues, _make(u, x_all[d, 0], ("latitude", "longitude"), c2),
+                            _make(u, y_all[d, 0], ("latitude", "longitude"), c2)))
+            else:                                                          # as series
+                c3 = {timedim: np.asarray(labels), "latitude": lat, "longitude": lon}
+                out.append((eigenvalues, _make(u, x_all[d], dims3, c3), _make(u, y_all[d], dims3, c3)))
+        return tuple(out)
+
 
 def _resample_ratio(t_orig, t_new) -> int:
     """Resampled levels per original level: the resampled times must be uniformly spaced and hold every original time at

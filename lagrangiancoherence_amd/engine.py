@@ -1157,6 +1157,54 @@ class Engine:
                                                 self._ptr(sig[m0:m0 + n])), self.lib)
         return {"sigma": sig, "x_dep": x, "y_dep": y}
 
+    def lcs_bidirectional(self, field: PackedField, seed_lat, seed_lon, timestep, nsteps: int, n_windows: int = 1, t0=0,
+                          t0_stride=1, SETTLS_order=0, interp_order=1, cyclic_xboundary=True, gauss_sigma=None,
+                          fd_fp32_cast=True, tensor_layout="reference", noncyclic_clamp=None):
+        """:meth:`lcs_series` in both directions of time: the attracting (backward, ``-|timestep|``) and the repelling
+        (forward, ``+|timestep|``) field of every window.  Returns ``{"sigma", "x_dep", "y_dep"}`` as ``(2, n_windows, ny, nx)``
+        device tensors; entry ``[d, w]`` equals ``lcs(field, ..., timestep=(-1, +1)[d] * |timestep|, t0=t0 + w * t0_stride,
+        nsteps=nsteps)`` bit for bit.
+
+        One ``lc_advect_series_dirs`` call (both directions of every window in one launch per level chunk) and one
+        ``lc_sigma_batch`` call per group of windows; a group counts two planes per window against ``SERIES_MEM_CAP``, and the
+        results do not depend on the grouping."""
+        if interp_order != 1 and field.order != interp_order:
+            raise ValueError(f"field was prepared for interp_order={field.order}")
+        timestep = float(timestep)
+        if not timestep or not np.isfinite(timestep):
+            raise ValueError(f"lcs_bidirectional: timestep {timestep} (non-zero: its sign is taken from the direction)")
+        n_windows, nsteps, t0, t0_stride = int(n_windows), int(nsteps), int(t0), int(t0_stride)
+        if n_windows < 1 or nsteps < 0 or t0 < 0 or t0_stride < 0:
+            raise ValueError(f"lcs_bidirectional: n_windows {n_windows}, nsteps {nsteps}, t0 {t0}, t0_stride {t0_stride}")
+        dtype = field.dtype
+        seed_lat = np.asarray(seed_lat, dtype=dtype)
+        seed_lon = np.asarray(seed_lon, dtype=dtype)
+        slat, slon = self.to_device(seed_lat, dtype), self.to_device(seed_lon, dtype)
+        ny, nx = int(slat.numel()), int(slon.numel())
+        # the library's plane order: window-major, [n_windows][2][ny][nx], plane 2w + d with -timestep for d = 1
+        x, y, sig = (self._empty((n_windows, 2, ny, nx), dtype) for _ in range(3))
+        xmode = x_boundary_mode(cyclic_xboundary, noncyclic_clamp, True)
+        smooth = isinstance(gauss_sigma, (float, int)) and not isinstance(gauss_sigma, bool) and gauss_sigma > 1e-15
+        dlat = float(seed_lat[1] - seed_lat[0])     # as _sigma_of: the spacing in the coordinate dtype (tools.py:255-256)
+        dlon = float(seed_lon[1] - seed_lon[0])
+        g = self.series_group(dtype, 2 * ny * nx, n_windows, cyclic_xboundary)
+        for m0 in range(0, n_windows, g):
+            n = min(g, n_windows - m0)
+            xg, yg = x[m0:m0 + n], y[m0:m0 + n]
+            self._use_current_stream()
+            a = self._advect_args(field, interp_order, slat, ny, slon, nx, 0, ny, None, None, -abs(timestep), SETTLS_order,
+                                  xmode, t0 + m0 * t0_stride, nsteps, n, t0_stride, xg, yg, None, None)
+            _capi.check(self.lib.lc_advect_series_dirs(self.ctx, C.byref(a), 2), self.lib)
+            xs, ys = xg.reshape(2 * n, ny, nx), yg.reshape(2 * n, ny, nx)
+            if smooth:     # scipy's gaussian_filter of each plane's departure points (LCS/LCS.py:187-190), as _sigma_of
+                xs = self.torch.stack([self.gaussian_filter(xs[i], gauss_sigma) for i in range(2 * n)])
+                ys = self.torch.stack([self.gaussian_filter(ys[i], gauss_sigma) for i in range(2 * n)])
+            self._use_current_stream()
+            _capi.check(self.lib.lc_sigma_batch(self.ctx, self._ptr(xs), self._ptr(ys), _NP2LC[dtype], ny, nx, self._ptr(slat),
+                                                dlat, dlon, int(bool(fd_fp32_cast)), _LAYOUTS[tensor_layout], 2 * n,
+                                                self._ptr(sig[m0:m0 + n])), self.lib)
+        return {k: t.transpose(0, 1).contiguous() for k, t in (("sigma", sig), ("x_dep", x), ("y_dep", y))}
+
     def sigma_batch(self, x_dep, y_dep, seed_lat, dlat, dlon, fd_fp32_cast=True, tensor_layout="reference"):
         """sigma_max of ``n`` whole grids at once (``lc_sigma_batch``): ``x_dep``, ``y_dep`` ``(n, ny, nx)``; plane ``m`` of the
         result equals :meth:`sigma` of plane ``m`` bit for bit."""
