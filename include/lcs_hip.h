@@ -38,7 +38,7 @@ extern "C" {
  * client built against 100 must be rebuilt), lc_ctx_get_level_chunk, lc_ctx_set/get_f64_fidelity, lc_advect_ex and
  * lc_sample_raw added, lc_field_pack accepts packed_dev == NULL at order 1 (fused-level image only).  lc_version() returns the value the LIBRARY
  * was built with: compare it with this macro before any other call (tests/c/abi_smoke.c, _capi.load do). */
-#define LC_VERSION 104 /* 0.1.4: + lc_advect_series_dirs, + lc_advect_series, lc_sigma_batch, + lc_tracer_sample, lc_ctx_last_tracer_kernel (additive: no argument list changed), + lc_ctx_set_host_pipeline, lc_copy_to_device, lc_copy_to_host, lc_ctx_set_host_cache, lc_ctx_trim, lc_ctx_last_host_marks, lc_ctx_set_xcd_split (0.1.3: + lc_ctx_last_pack_kernel; 0.1.2: + lc_ctx_set_verify, lc_ctx_read_verify, LC_F64_WIND_F32_LIN32) */
+#define LC_VERSION 104 /* 0.1.4: + lc_strain, lc_ctx_last_strain_kernel, + lc_advect_series_dirs, + lc_advect_series, lc_sigma_batch, + lc_tracer_sample, lc_ctx_last_tracer_kernel (additive: no argument list changed), + lc_ctx_set_host_pipeline, lc_copy_to_device, lc_copy_to_host, lc_ctx_set_host_cache, lc_ctx_trim, lc_ctx_last_host_marks, lc_ctx_set_xcd_split (0.1.3: + lc_ctx_last_pack_kernel; 0.1.2: + lc_ctx_set_verify, lc_ctx_read_verify, LC_F64_WIND_F32_LIN32) */
 
 typedef struct lc_ctx lc_ctx;
 
@@ -533,6 +533,23 @@ int lc_sigma(lc_ctx *ctx, const void *x_dep, const void *y_dep, int dtype,
 int lc_sigma_batch(lc_ctx *ctx, const void *x_dep, const void *y_dep, int dtype, int ny, int nx,
                    const void *seed_lat_dev, double dlat, double dlon, int fd_fp32_cast, int tensor_layout,
                    int n_members, void *sigma_out);
+
+/* Both singular values of the 3x2 flow-map Jacobian F = [[dXdx, dXdy], [dYdx, dYdy], [dZdx, dZdy]] (LC_LAYOUT_PHYSICAL; NOT the
+ * reference's 3x3 reshape, LCS/LCS.py:153) and its leading right singular vector, for n_members whole grids in one launch.  No
+ * reference counterpart: the reference keeps the largest singular value only (LCS/LCS.py:154).  Geometry, stencil and
+ * fd_fp32_cast as lc_sigma; inputs and outputs [n_members][ny*nx] dtype elements, seed_lat_dev [ny].
+ *   s1_out      largest singular value; in LC_F64 equal to lc_sigma(LC_LAYOUT_PHYSICAL) bit for bit
+ *   s2_out      smallest singular value, as |col1 x col2| / s1 (0 where s1 == 0): s1 * s2 is the area change of the flow map
+ *   e_lon_out, e_lat_out   unit eigenvector of F^T F for s1^2 in local (east, north) components at the seed, the direction
+ *               that is stretched by s1; sign: e_lon > 0, or e_lon == 0 and e_lat > 0; (1, 0) where F^T F is a multiple of
+ *               the identity
+ * s2_out, e_lon_out, e_lat_out may each be NULL (that plane is not written).  A NaN departure point gives NaN in every output
+ * of every cell whose stencil touches it.  lc_ctx_last_strain_kernel: the kernel the context's last lc_strain launched (""
+ * before any): "strain_kernel_f32", "strain_kernel<double, float>" (fd_fp32_cast) or "strain_kernel<double, double>". */
+int lc_strain(lc_ctx *ctx, const void *x_dep, const void *y_dep, int dtype, int ny, int nx,
+              const void *seed_lat_dev, double dlat, double dlon, int fd_fp32_cast, int n_members,
+              void *s1_out, void *s2_out, void *e_lon_out, void *e_lat_out);
+const char *lc_ctx_last_strain_kernel(const lc_ctx *ctx);
 
 /* The 9-component "def_tensor" itself, for callers of LCS.flowmap_gradient
  * (LCS/LCS.py:171-225): planes dXdx,dXdy,dYdx,dYdy,dZdx,dZdy,dXdr,dYdr,dZdr (the last

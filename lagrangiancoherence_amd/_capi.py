@@ -73,6 +73,8 @@ PROTOTYPES = {
     "lc_sample_raw": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _d, _d, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "lc_sigma": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _d, _d, _i, _i, _i, _i, _vp]),
     "lc_sigma_batch": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _d, _d, _i, _i, _i, _vp]),
+    "lc_strain": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _d, _d, _i, _i, _vp, _vp, _vp, _vp]),
+    "lc_ctx_last_strain_kernel": (C.c_char_p, [_vp]),
     "lc_flowmap_gradient": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _d, _d, _i, _vp]),
     "lc_fourth_order_derivative": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lc_gaussian_filter": (_i, [_vp, _vp, _i, _i, _i, _d, _vp, _vp]),

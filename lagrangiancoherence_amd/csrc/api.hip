@@ -83,6 +83,7 @@ extern "C" int lc_ctx_create(int device, lc_ctx **out) {
     c->last_sigma_kernel = "";
     c->last_pack_kernel = "";
     c->last_tracer_kernel = "";
+    c->last_strain_kernel = "";
     c->verify_dev = nullptr;
     c->trunc = nullptr;
     c->xfer = nullptr;

@@ -45,6 +45,7 @@ struct lc_ctx {
     int host_threads;           // staging ring: worker threads beside the caller (-1: by the host's core count; LCS_HOST_THREADS at creation)
     int host_piece_mb;          // staging ring: piece size in MB (0: 32; LCS_HOST_PIECE_MB at creation)
     int host_pipeline;          // lc_lcs_host: 1 (default) staged transfers, upload cut into level chunks and overlapped with pack + advect; 0 the serial round-5 form (LCS_HOST_PIPELINE at creation)
+    const char *last_strain_kernel;  // what the last lc_strain launched (lc_ctx_last_strain_kernel)
 };
 
 void lc_set_error(const char *fmt, ...);

@@ -524,6 +524,121 @@ class LCS:
                 out.append((eigenvalues, _make(u, x_all[d], dims3, c3), _make(u, y_all[d], dims3, c3)))
         return tuple(out)
 
+    def _record_intake(self, ds, u, v, window, stride, resample, isglobal, interp_to_common_grid, truncation, verbose):
+        """The steps :meth:`series` takes before it packs, for one record: intake (LCS.py:81-96), the window / stride checks,
+        ``resample`` on the whole record (LCS.py:88-91), sort (LCS.py:101-104), the 0.5 degree regrid and the T20 truncation
+        (LCS.py:106-118).  ``window=None``: one window, the whole (resampled) record, as ``__call__``.  Returns the sorted
+        arrays and coordinates, the signed timestep, the window geometry in levels of the sorted record and the label source."""
+        timedim = self.timedim
+        self.verbose = verbose
+        if window is not None:
+            if isinstance(window, bool) or int(window) != window or int(window) < 2:
+                raise ValueError(f"window {window!r}: at least 2 time levels")
+            if isinstance(stride, bool) or int(stride) != stride or int(stride) < 1:
+                raise ValueError(f"stride {stride!r}: at least 1 time level")
+            window, stride = int(window), int(stride)
+        if isinstance(ds, str):                                            # LCS.py:84-87
+            import xarray as xr
+            ds = xr.open_dataset(ds)
+        if ds is not None and not isinstance(ds, str):                     # LCS.py:81-83
+            u = ds.u.copy()
+            v = ds.v.copy()
+        assert set(u.dims) == set(v.dims), "u and v dims are different"                     # LCS.py:95
+        assert set(u.dims) == {'latitude', 'longitude', timedim}, \
+            'array dims should be latitude and longitude only'                             # LCS.py:96
+        t_orig = np.asarray(u[timedim].values)
+        nt = t_orig.size
+        if window is not None and window > nt:
+            raise ValueError(f"window {window} is longer than the record ({nt} time levels)")
+        timestep = self.timestep
+        r = 1
+        if isinstance(resample, str):                                      # LCS.py:88-91, on the whole record
+            if _is_xarray(u):
+                u = u.resample({timedim: resample}).interpolate('linear')
+                v = v.resample({timedim: resample}).interpolate('linear')
+            else:
+                u = _resample_linear(u, timedim, resample)
+                v = _resample_linear(v, timedim, resample)
+            t_new = np.asarray(u[timedim].values)
+            if window is not None:
+                r = _resample_ratio(t_orig, t_new)
+            timestep = np.sign(timestep) * (t_new[1] - t_new[0]).astype('timedelta64[s]').astype('float')
+        if window is None:                                                 # one window: the whole (resampled) record
+            n_windows, wlen, wstep = 1, int(np.asarray(u[timedim].values).size), 1
+        else:
+            n_windows = (nt - window) // stride + 1
+            wlen, wstep = (window - 1) * r + 1, stride * r                # a window and the distance between two, in levels
+
+        uu, time, lat, lon = _sorted_tll(u, timedim)                       # LCS.py:101-104
+        vv, _, _, _ = _sorted_tll(v, timedim)
+        eng = get_engine()
+        if isglobal:
+            from . import preprocess
+            if interp_to_common_grid:                                      # LCS.py:106-114
+                uu, lat_new, lon_new = preprocess.regrid_common_grid(eng, uu, lat, lon)
+                vv, _, _ = preprocess.regrid_common_grid(eng, vv, lat, lon)
+                lat, lon = lat_new, lon_new
+            if truncation is not None:                                     # LCS.py:115-118
+                gridtype = preprocess.inspect_gridtype(lat)
+                uu = preprocess.spectral_truncate(eng, uu, truncation, gridtype)
+                vv = preprocess.spectral_truncate(eng, vv, truncation, gridtype)
+            self.subdomain = None                                          # LCS.py:119-120
+        return dict(like=u, uu=uu, vv=vv, time=time, lat=lat, lon=lon, timestep=timestep, cyclic_xboundary=bool(isglobal),
+                    n_windows=n_windows, wlen=wlen, wstep=wstep)
+
+    def strain(self, ds=None, u=None, v=None, window=None, stride=1, verbose=True, s=None, resample=None, s_is_error=False,
+               isglobal=False, interp_to_common_grid=True, traj_interp_order=3, truncation=20):
+        """Both stretch factors of the flow map and its stretching direction: ``(s1, s2, direction)``.
+
+        ``s1 >= s2`` are the singular values of the 3 x 2 Jacobian ``[[dXdx, dXdy], [dYdx, dYdy], [dZdx, dZdy]]`` of
+        :func:`flowmap_gradient` -- the PHYSICAL layout, so ``s1`` is not ``__call__``'s value, which takes the 2-norm of the
+        reference's row-major 3 x 3 reshape (LCS.py:152-153) --, dims ``(timedim, latitude, longitude)``; ``s1 * s2`` is the
+        Lagrangian area change.  ``direction`` has dims ``("component", timedim, latitude, longitude)`` with ``component =
+        ["east", "north"]``: the unit vector at the seed that the flow map stretches by ``s1`` (the leading right singular
+        vector), signed so that east > 0, or east == 0 and north > 0; ``(1, 0)`` where the cell is isotropic.  A NaN departure
+        point gives NaN in all three on the cells whose stencil touches it.
+
+        ``window=None``: one entry, the whole record as ``__call__`` takes it; ``window=k``: the sliding windows of
+        :meth:`series` (same ``stride``, same time labels: LCS.py:158 per window).  Intake, ``resample``, sort, regrid / T20 and
+        the one pack are :meth:`series`'; the direction of integration is the sign of ``timestep``.  Then one
+        ``lc_advect_series`` call and one ``lc_strain`` call per memory group (``Engine.lcs_strain``).  With ``return_dpts``
+        ``x_dep`` and ``y_dep`` are appended, dims ``(timedim, latitude, longitude)``, as :meth:`series` appends them."""
+        verboseprint = print if verbose else (lambda *a, **k: None)
+        timedim = self.timedim
+        rec = self._record_intake(ds, u, v, window, stride, resample, isglobal, interp_to_common_grid, truncation, verbose)
+        like, time, lat, lon, timestep = rec["like"], rec["time"], rec["lat"], rec["lon"], rec["timestep"]
+        n_windows, wlen, wstep = rec["n_windows"], rec["wlen"], rec["wstep"]
+        eng = get_engine()
+
+        verboseprint(f"*---- Parcel propagation: {n_windows} window(s) ----*")
+        dtype = common_dtype(rec["uu"], rec["vv"], lat, lon)
+        lat_t, lon_t = lat.astype(dtype), lon.astype(dtype)
+        # the pack of the per-window call (Engine.lcs_wind -> pack_and_advect), once for the whole record
+        fuse, ext_image = eng._pack_options(dtype, self.SETTLS_order, eng.f64_fuse_levels(dtype, lat.size * lon.size), None)
+        field = eng.prepare_field(rec["uu"], rec["vv"], lat, lon, traj_interp_order, fuse_levels=fuse, ext_image=ext_image)
+        res = eng.lcs_strain(field, lat_t, lon_t, timestep, wlen - 1, n_windows, 0, wstep, SETTLS_order=self.SETTLS_order,
+                             interp_order=traj_interp_order, cyclic_xboundary=rec["cyclic_xboundary"],
+                             gauss_sigma=self.gauss_sigma)
+        verboseprint("*---- Done stretch factors ----*")
+
+        s1, s2 = _to_np(res["s1"]), _to_np(res["s2"])
+        e = np.stack([_to_np(res["e_lon"]), _to_np(res["e_lat"])])
+        slat, slon = lat, lon
+        if isinstance(self.subdomain, dict):                               # LCS.py:143-144
+            mlat, mlon = _crop_strict(lat, lon, self.subdomain)
+            s1, s2, e = s1[:, mlat][:, :, mlon], s2[:, mlat][:, :, mlon], e[:, :, mlat][:, :, :, mlon]
+            slat, slon = lat[mlat], lon[mlon]
+        first = np.arange(n_windows) * wstep
+        labels = time[first + wlen - 1] if np.sign(timestep) == 1 else time[first]     # LCS.py:158, per window
+        dims3 = (timedim, "latitude", "longitude")
+        c3 = {timedim: np.asarray(labels), "latitude": slat, "longitude": slon}
+        out = (_make(like, s1, dims3, c3, "s1"), _make(like, s2, dims3, c3, "s2"),
+               _make(like, e, ("component",) + dims3, {"component": np.array(["east", "north"]), **c3}, "direction"))
+        if self.return_dpts:                                               # LCS.py:161-168
+            c3 = {timedim: np.asarray(labels), "latitude": lat, "longitude": lon}
+            out += (_make(like, _to_np(res["x_dep"]), dims3, c3), _make(like, _to_np(res["y_dep"]), dims3, c3))
+        return out
+
 
 def _resample_ratio(t_orig, t_new) -> int:
     """Resampled levels per original level: the resampled times must be uniformly spaced and hold every original time at

@@ -1223,6 +1223,84 @@ class Engine:
                                             float(dlon), int(bool(fd_fp32_cast)), _LAYOUTS[tensor_layout], n, self._ptr(sig)), self.lib)
         return sig
 
+    # ------------------------------------------------------------------ stretch factors and direction
+    _STRAIN_PLANES = ("s1", "s2", "e_lon", "e_lat")
+
+    def last_strain_kernel(self) -> str:
+        """Name of the kernel the last :meth:`strain` call launched (``lc_ctx_last_strain_kernel``)."""
+        return self.lib.lc_ctx_last_strain_kernel(self.ctx).decode()
+
+    def strain(self, x_dep, y_dep, seed_lat, dlat, dlon, fd_fp32_cast=True, want=("s1", "s2", "e_lon", "e_lat")) -> dict:
+        """Both singular values ``s1 >= s2`` of the 3 x 2 flow-map Jacobian (the physical layout, not the reference's 3 x 3
+        reshape: ``s1`` is :meth:`sigma` with ``tensor_layout="physical"``, bit for bit in float64) and the unit direction
+        ``(e_lon, e_lat)`` at the seed that is stretched by ``s1`` (east, north components; ``e_lon > 0``, or ``e_lon == 0``
+        and ``e_lat > 0``; ``(1, 0)`` in an isotropic cell), in one launch (``lc_strain``).  ``x_dep``, ``y_dep``: ``(ny, nx)``
+        or ``(n, ny, nx)`` whole grids; the result maps each name in ``want`` (``"s1"`` is always computed) to a device tensor
+        of the input's shape and dtype.  ``s1 * s2`` is the area change of the flow map."""
+        torch = self.torch
+        want = tuple(want)
+        bad = [w for w in want if w not in self._STRAIN_PLANES]
+        if bad or not want:
+            raise ValueError(f"want {want!r}: a non-empty subset of {self._STRAIN_PLANES}")
+        dtype = np.dtype(str(x_dep.dtype).replace("torch.", "")) if isinstance(x_dep, torch.Tensor) else common_dtype(x_dep, y_dep)
+        xd, yd = self.to_device(x_dep, dtype), self.to_device(y_dep, dtype)
+        if xd.dim() not in (2, 3) or tuple(yd.shape) != tuple(xd.shape):
+            raise ValueError("x_dep and y_dep must both be (ny, nx) or (n, ny, nx)")
+        shape = tuple(int(s) for s in xd.shape)
+        ny, nx = shape[-2:]
+        n = shape[0] if len(shape) == 3 else 1
+        slat = self.to_device(seed_lat, dtype)
+        if slat.numel() != ny:
+            raise ValueError("seed_lat must have one latitude per row")
+        out = {k: self._empty(shape, dtype) for k in self._STRAIN_PLANES if k in want or k == "s1"}
+        self._use_current_stream()
+        _capi.check(self.lib.lc_strain(self.ctx, self._ptr(xd), self._ptr(yd), _NP2LC[dtype], ny, nx, self._ptr(slat), float(dlat),
+                                       float(dlon), int(bool(fd_fp32_cast)), n,
+                                       *(self._ptr(out.get(k)) for k in self._STRAIN_PLANES)), self.lib)
+        return {k: out[k] for k in want}
+
+    def lcs_strain(self, field: PackedField, seed_lat, seed_lon, timestep, nsteps: int, n_windows: int = 1, t0=0, t0_stride=1,
+                   SETTLS_order=0, interp_order=1, cyclic_xboundary=True, gauss_sigma=None, fd_fp32_cast=True,
+                   noncyclic_clamp=None):
+        """:meth:`lcs_series`' advection (same arguments, same kernels: window ``m`` runs ``nsteps`` steps from level
+        ``t0 + m * t0_stride``) followed by :meth:`strain` instead of sigma: one ``lc_advect_series`` call and one ``lc_strain``
+        call per memory group.  Returns ``{"s1", "s2", "e_lon", "e_lat", "x_dep", "y_dep"}`` as ``(n_windows, ny, nx)`` device
+        tensors; ``x_dep`` / ``y_dep`` equal :meth:`lcs_series`' bit for bit.  ``gauss_sigma`` smooths the departure fields
+        first, as there."""
+        if interp_order != 1 and field.order != interp_order:
+            raise ValueError(f"field was prepared for interp_order={field.order}")
+        n_windows, nsteps, t0, t0_stride = int(n_windows), int(nsteps), int(t0), int(t0_stride)
+        if n_windows < 1 or nsteps < 0 or t0 < 0 or t0_stride < 0:
+            raise ValueError(f"lcs_strain: n_windows {n_windows}, nsteps {nsteps}, t0 {t0}, t0_stride {t0_stride}")
+        dtype = field.dtype
+        seed_lat = np.asarray(seed_lat, dtype=dtype)
+        seed_lon = np.asarray(seed_lon, dtype=dtype)
+        slat, slon = self.to_device(seed_lat, dtype), self.to_device(seed_lon, dtype)
+        ny, nx = int(slat.numel()), int(slon.numel())
+        x, y, s1, s2, ex, ey = (self._empty((n_windows, ny, nx), dtype) for _ in range(6))
+        xmode = x_boundary_mode(cyclic_xboundary, noncyclic_clamp, True)
+        smooth = isinstance(gauss_sigma, (float, int)) and not isinstance(gauss_sigma, bool) and gauss_sigma > 1e-15
+        dlat = float(seed_lat[1] - seed_lat[0])     # as _sigma_of: the spacing in the coordinate dtype (tools.py:255-256)
+        dlon = float(seed_lon[1] - seed_lon[0])
+        # series_group's count with the three planes a window holds here on top of lcs_series' (s2, e_lon, e_lat)
+        per = (8 if cyclic_xboundary else 12) * ny * nx * np.dtype(dtype).itemsize
+        g = max(1, min(n_windows, int(self.SERIES_MEM_CAP) // per))
+        for m0 in range(0, n_windows, g):
+            n = min(g, n_windows - m0)
+            xg, yg = x[m0:m0 + n], y[m0:m0 + n]
+            self._use_current_stream()
+            a = self._advect_args(field, interp_order, slat, ny, slon, nx, 0, ny, None, None, timestep, SETTLS_order, xmode,
+                                  t0 + m0 * t0_stride, nsteps, n, t0_stride, xg, yg, None, None)
+            _capi.check(self.lib.lc_advect_series(self.ctx, C.byref(a)), self.lib)
+            xs, ys = xg, yg
+            if smooth:     # scipy's gaussian_filter of each window's departure points (LCS/LCS.py:187-190), as _sigma_of
+                xs = self.torch.stack([self.gaussian_filter(xg[i], gauss_sigma) for i in range(n)])
+                ys = self.torch.stack([self.gaussian_filter(yg[i], gauss_sigma) for i in range(n)])
+            self._use_current_stream()
+            _capi.check(self.lib.lc_strain(self.ctx, self._ptr(xs), self._ptr(ys), _NP2LC[dtype], ny, nx, self._ptr(slat), dlat, dlon,
+                                           int(bool(fd_fp32_cast)), n, *(self._ptr(t[m0:m0 + n]) for t in (s1, s2, ex, ey))), self.lib)
+        return {"s1": s1, "s2": s2, "e_lon": ex, "e_lat": ey, "x_dep": x, "y_dep": y}
+
     def synchronize(self):
         self.torch.cuda.synchronize(self.device)
 
