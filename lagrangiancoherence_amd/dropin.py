@@ -30,6 +30,8 @@ Deliberate differences from the reference (all outside the arithmetic):
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import numpy as np
 
 from .engine import Engine, common_dtype
@@ -216,6 +218,21 @@ def _crop_strict(lat, lon, sub):
     return mlat, mlon
 
 
+class _Record(NamedTuple):
+    """One record as :meth:`LCS._record_intake` hands it to the engine calls and to the labelling of their results."""
+    like: object            # the caller's u (resampled): results come back in its class
+    uu: np.ndarray          # (time, latitude, longitude), latitude and longitude ascending
+    vv: np.ndarray
+    time: np.ndarray
+    lat: np.ndarray
+    lon: np.ndarray
+    timestep: float         # signed; with ``resample`` the resampled spacing in seconds
+    cyclic_xboundary: bool
+    n_windows: int
+    wlen: int               # levels of the sorted record in one window
+    wstep: int              # levels between the starts of two windows
+
+
 class LCS:
     """API to compute the Finite-time Lyapunov exponent in 2D wind fields (LCS/LCS.py:19-46).
 
@@ -236,79 +253,35 @@ class LCS:
     def __call__(self, ds=None, u=None, v=None, verbose=True, s=None, resample=None, s_is_error=False,
                  isglobal=False, return_traj=False, interp_to_common_grid=True, traj_interp_order=3, truncation=20):
         verboseprint = print if verbose else (lambda *a, **k: None)
-        timestep = self.timestep
         timedim = self.timedim
-        self.verbose = verbose
-
-        if isinstance(ds, str):                                            # LCS.py:84-87
-            import xarray as xr
-            ds = xr.open_dataset(ds)
-        if ds is not None and not isinstance(ds, str):                     # LCS.py:81-83
-            u = ds.u.copy()
-            v = ds.v.copy()
-        if isinstance(resample, str):                                      # LCS.py:88-91
-            if _is_xarray(u):
-                u = u.resample({timedim: resample}).interpolate('linear')
-                v = v.resample({timedim: resample}).interpolate('linear')
-            else:
-                u = _resample_linear(u, timedim, resample)
-                v = _resample_linear(v, timedim, resample)
-            timestep = np.sign(timestep) * (u[timedim].values[1] - u[timedim].values[0]) \
-                .astype('timedelta64[s]').astype('float')
-        assert set(u.dims) == set(v.dims), "u and v dims are different"                     # LCS.py:95
-        assert set(u.dims) == {'latitude', 'longitude', timedim}, \
-            'array dims should be latitude and longitude only'                             # LCS.py:96
-
-        uu, time, lat, lon = _sorted_tll(u, timedim)                       # LCS.py:101-104
-        vv, _, _, _ = _sorted_tll(v, timedim)
+        rec = self._record_intake(ds, u, v, None, 1, resample, isglobal, interp_to_common_grid, truncation, verbose)
+        lat, lon = rec.lat, rec.lon
         eng = get_engine()
-        if isglobal:
-            from . import preprocess
-            if interp_to_common_grid:                                      # LCS.py:106-114
-                uu, lat_new, lon_new = preprocess.regrid_common_grid(eng, uu, lat, lon)
-                vv, _, _ = preprocess.regrid_common_grid(eng, vv, lat, lon)
-                lat, lon = lat_new, lon_new
-            if truncation is not None:                                     # LCS.py:115-118
-                gridtype = preprocess.inspect_gridtype(lat)              # windspharm's: equally spaced global, or Gaussian
-                uu = preprocess.spectral_truncate(eng, uu, truncation, gridtype)
-                vv = preprocess.spectral_truncate(eng, vv, truncation, gridtype)
-            cyclic_xboundary = True                                        # LCS.py:119-120
-            self.subdomain = None
-        else:
-            cyclic_xboundary = False
 
         verboseprint("*---- Parcel propagation ----*")
-        dtype = common_dtype(uu, vv, lat, lon)
+        dtype = common_dtype(rec.uu, rec.vv, lat, lon)
         lat_t, lon_t = lat.astype(dtype), lon.astype(dtype)
-        res = eng.lcs_wind(uu, vv, lat, lon, lat_t, lon_t, timestep, SETTLS_order=self.SETTLS_order,
-                           interp_order=traj_interp_order, cyclic_xboundary=cyclic_xboundary,
+        res = eng.lcs_wind(rec.uu, rec.vv, lat, lon, lat_t, lon_t, rec.timestep, SETTLS_order=self.SETTLS_order,
+                           interp_order=traj_interp_order, cyclic_xboundary=rec.cyclic_xboundary,
                            fuse_levels=eng.f64_fuse_levels(dtype, lat.size * lon.size),
                            gauss_sigma=self.gauss_sigma, return_traj=return_traj)          # LCS.py:129-154
         verboseprint("*---- Done eigenvalues ----*")
 
-        sig = _to_np(res["sigma"])
-        slat, slon = lat, lon
-        if isinstance(self.subdomain, dict):                               # LCS.py:143-144
-            mlat, mlon = _crop_strict(lat, lon, self.subdomain)
-            sig, slat, slon = sig[mlat][:, mlon], lat[mlat], lon[mlon]
-        timestamp = time[-1] if np.sign(timestep) == 1 else time[0]        # LCS.py:158
-        eigenvalues = _make(u, sig[None], (timedim, "latitude", "longitude"),
-                            {timedim: np.asarray([timestamp]), "latitude": slat, "longitude": slon},
-                            getattr(u, "name", None))                      # LCS.py:159-160
-
-        times = time.tolist()
-        if timestep < 0:
+        forward = np.sign(rec.timestep) == 1
+        eigenvalues = self._windows_out(rec, forward, _to_np(res["sigma"])[None], getattr(rec.like, "name", None))  # LCS.py:159-160
+        times = rec.time.tolist()
+        if rec.timestep < 0:
             times.reverse()
-        c2 = {"latitude": lat, "longitude": lon}
 
         def dep(k):
-            return _make(u, _to_np(res[k]), ("latitude", "longitude"), {**c2, timedim: times[-1]})
+            return self._departure_out(rec, _to_np(res[k]), rec.timestep < 0)
 
         def traj(k):
             import pandas as pd
             tindex = pd.Index(pd.to_datetime(times), name=timedim)
-            tcoord = tindex if _is_xarray(u) else np.asarray(tindex.values)
-            return _make(u, _to_np(res[k]), (timedim, "latitude", "longitude"), {timedim: tcoord, **c2})
+            tcoord = tindex if _is_xarray(rec.like) else np.asarray(tindex.values)
+            return _make(rec.like, _to_np(res[k]), (timedim, "latitude", "longitude"),
+                         {timedim: tcoord, "latitude": lat, "longitude": lon})
 
         if self.return_dpts and return_traj:                               # LCS.py:161-168
             return eigenvalues, dep("x_dep"), dep("y_dep"), traj("traj_x"), traj("traj_y")
@@ -329,90 +302,26 @@ class LCS:
         going backward); the result has dims ``(timedim, latitude, longitude)``, and with ``return_dpts`` ``x_dep`` / ``y_dep``
         get the same leading time dimension.  Sorting, ``resample`` (linear in time between original levels, so resampling
         the record and slicing it gives what resampling each slice gives, except at a slice's first level: see below), the 0.5 degree regrid and the T20 truncation
-        (both level by level) run once on the whole record; the record is packed once and every window is advected in one
-        batched call (``Engine.lcs_series``).  Two places where the windows agree with the per-window calls to rounding,
-        not bit for bit: float64 at order 3 on grids of 256 rows or more (a level packed with the whole record may differ
+        (both level by level) run once on the whole record (:meth:`_record_intake`); the record is packed once and every window
+        is advected in one batched call (``Engine.lcs_series``).  Two places where the windows agree with the per-window calls
+        to rounding, not bit for bit: float64 at order 3 on grids of 256 rows or more (a level packed with the whole record may differ
         in its last bits from the same level packed inside one window: the pack cuts levels into row pieces by the number
         of levels), and -- with ``resample`` -- the first level of every window after the first: the per-window call's
         interpolation returns the original level there, the record's the left interval's value, which can differ in the
         last bit of the input."""
         verboseprint = print if verbose else (lambda *a, **k: None)
-        timedim = self.timedim
-        self.verbose = verbose
-        if window is None or isinstance(window, bool) or int(window) != window or int(window) < 2:
+        if window is None:                                                 # (the intake's one-window form is not a series)
             raise ValueError(f"window {window!r}: at least 2 time levels")
-        if isinstance(stride, bool) or int(stride) != stride or int(stride) < 1:
-            raise ValueError(f"stride {stride!r}: at least 1 time level")
-        window, stride = int(window), int(stride)
-        if isinstance(ds, str):                                            # LCS.py:84-87
-            import xarray as xr
-            ds = xr.open_dataset(ds)
-        if ds is not None and not isinstance(ds, str):                     # LCS.py:81-83
-            u = ds.u.copy()
-            v = ds.v.copy()
-        assert set(u.dims) == set(v.dims), "u and v dims are different"                     # LCS.py:95
-        assert set(u.dims) == {'latitude', 'longitude', timedim}, \
-            'array dims should be latitude and longitude only'                             # LCS.py:96
-        t_orig = np.asarray(u[timedim].values)
-        nt = t_orig.size
-        if window > nt:
-            raise ValueError(f"window {window} is longer than the record ({nt} time levels)")
-        n_windows = (nt - window) // stride + 1
-        timestep = self.timestep
-        r = 1
-        if isinstance(resample, str):                                      # LCS.py:88-91, on the whole record
-            if _is_xarray(u):
-                u = u.resample({timedim: resample}).interpolate('linear')
-                v = v.resample({timedim: resample}).interpolate('linear')
-            else:
-                u = _resample_linear(u, timedim, resample)
-                v = _resample_linear(v, timedim, resample)
-            t_new = np.asarray(u[timedim].values)
-            r = _resample_ratio(t_orig, t_new)
-            timestep = np.sign(timestep) * (t_new[1] - t_new[0]).astype('timedelta64[s]').astype('float')
-        wlen, wstep = (window - 1) * r + 1, stride * r                    # a window and the distance between two, in levels
-
-        uu, time, lat, lon = _sorted_tll(u, timedim)                       # LCS.py:101-104
-        vv, _, _, _ = _sorted_tll(v, timedim)
-        eng = get_engine()
-        if isglobal:
-            from . import preprocess
-            if interp_to_common_grid:                                      # LCS.py:106-114
-                uu, lat_new, lon_new = preprocess.regrid_common_grid(eng, uu, lat, lon)
-                vv, _, _ = preprocess.regrid_common_grid(eng, vv, lat, lon)
-                lat, lon = lat_new, lon_new
-            if truncation is not None:                                     # LCS.py:115-118
-                gridtype = preprocess.inspect_gridtype(lat)
-                uu = preprocess.spectral_truncate(eng, uu, truncation, gridtype)
-                vv = preprocess.spectral_truncate(eng, vv, truncation, gridtype)
-            cyclic_xboundary = True                                        # LCS.py:119-120
-            self.subdomain = None
-        else:
-            cyclic_xboundary = False
-
-        verboseprint(f"*---- Parcel propagation: {n_windows} windows ----*")
-        dtype = common_dtype(uu, vv, lat, lon)
-        lat_t, lon_t = lat.astype(dtype), lon.astype(dtype)
-        # the pack of the per-window call (Engine.lcs_wind -> pack_and_advect), once for the whole record
-        fuse, ext_image = eng._pack_options(dtype, self.SETTLS_order, eng.f64_fuse_levels(dtype, lat.size * lon.size), None)
-        field = eng.prepare_field(uu, vv, lat, lon, traj_interp_order, fuse_levels=fuse, ext_image=ext_image)
-        res = eng.lcs_series(field, lat_t, lon_t, timestep, wlen - 1, n_windows, 0, wstep, SETTLS_order=self.SETTLS_order,
-                             interp_order=traj_interp_order, cyclic_xboundary=cyclic_xboundary, gauss_sigma=self.gauss_sigma)
+        rec = self._record_intake(ds, u, v, window, stride, resample, isglobal, interp_to_common_grid, truncation, verbose)
+        verboseprint(f"*---- Parcel propagation: {rec.n_windows} windows ----*")
+        res = self._run_windows("lcs_series", rec, rec.timestep, traj_interp_order)
         verboseprint("*---- Done eigenvalues ----*")
 
-        sig = _to_np(res["sigma"])
-        slat, slon = lat, lon
-        if isinstance(self.subdomain, dict):                               # LCS.py:143-144
-            mlat, mlon = _crop_strict(lat, lon, self.subdomain)
-            sig, slat, slon = sig[:, mlat][:, :, mlon], lat[mlat], lon[mlon]
-        first = np.arange(n_windows) * wstep
-        labels = time[first + wlen - 1] if np.sign(timestep) == 1 else time[first]     # LCS.py:158, per window
-        eigenvalues = _make(u, sig, (timedim, "latitude", "longitude"),
-                            {timedim: np.asarray(labels), "latitude": slat, "longitude": slon}, getattr(u, "name", None))
+        forward = np.sign(rec.timestep) == 1
+        eigenvalues = self._windows_out(rec, forward, _to_np(res["sigma"]), getattr(rec.like, "name", None))
         if self.return_dpts:                                               # LCS.py:161-168
-            c3 = {timedim: np.asarray(labels), "latitude": lat, "longitude": lon}
-            return (eigenvalues, _make(u, _to_np(res["x_dep"]), (timedim, "latitude", "longitude"), c3),
-                    _make(u, _to_np(res["y_dep"]), (timedim, "latitude", "longitude"), c3))
+            return (eigenvalues, self._windows_out(rec, forward, _to_np(res["x_dep"]), crop=False),
+                    self._windows_out(rec, forward, _to_np(res["y_dep"]), crop=False))
         return eigenvalues
 
     def bidirectional(self, ds=None, u=None, v=None, window=None, stride=1, verbose=True, s=None, resample=None,
@@ -423,112 +332,37 @@ class LCS:
         ``window=None``: ``attracting`` is what ``LCS(timestep=-abs(timestep), same ctor args)(ds, same call args)`` returns
         and ``repelling`` the same with ``+abs(timestep)`` (values, dims, the time labels of LCS.py:158 and the tuple of
         ``return_dpts``).  ``window=k``: the same against ``.series(ds, window=k, stride=stride, ...)`` for each sign.
-        Sorting, ``resample``, the regrid and T20 and the pack run once; then one ``lc_advect_series_dirs`` call and one
-        ``lc_sigma_batch`` call per memory group (``Engine.lcs_bidirectional``).  The levels are read in stored order in
-        both directions, so both directions advect over the same packed record.  Bit-identical to the
+        Sorting, ``resample``, the regrid and T20 (:meth:`_record_intake`) and the pack run once; then one
+        ``lc_advect_series_dirs`` call and one ``lc_sigma_batch`` call per memory group (``Engine.lcs_bidirectional``).  The levels
+        are read in stored order in both directions, so both directions advect over the same packed record.  Bit-identical to the
         single-direction calls except where :meth:`series` is not (its docstring): with ``window=None`` only float64 order 3
         on grids of 256 rows or more can differ, to rounding."""
         verboseprint = print if verbose else (lambda *a, **k: None)
-        timedim = self.timedim
-        self.verbose = verbose
         if not self.timestep:
             raise ValueError(f"timestep {self.timestep!r}: bidirectional needs a non-zero step (its sign is ignored)")
-        if window is not None:                                             # as series
-            if isinstance(window, bool) or int(window) != window or int(window) < 2:
-                raise ValueError(f"window {window!r}: at least 2 time levels")
-            if isinstance(stride, bool) or int(stride) != stride or int(stride) < 1:
-                raise ValueError(f"stride {stride!r}: at least 1 time level")
-            window, stride = int(window), int(stride)
-        if isinstance(ds, str):                                            # LCS.py:84-87
-            import xarray as xr
-            ds = xr.open_dataset(ds)
-        if ds is not None and not isinstance(ds, str):                     # LCS.py:81-83
-            u = ds.u.copy()
-            v = ds.v.copy()
-        assert set(u.dims) == set(v.dims), "u and v dims are different"                     # LCS.py:95
-        assert set(u.dims) == {'latitude', 'longitude', timedim}, \
-            'array dims should be latitude and longitude only'                             # LCS.py:96
-        t_orig = np.asarray(u[timedim].values)
-        nt = t_orig.size
-        if window is not None and window > nt:
-            raise ValueError(f"window {window} is longer than the record ({nt} time levels)")
-        step = abs(self.timestep)
-        r = 1
-        if isinstance(resample, str):                                      # LCS.py:88-91, on the whole record
-            if _is_xarray(u):
-                u = u.resample({timedim: resample}).interpolate('linear')
-                v = v.resample({timedim: resample}).interpolate('linear')
-            else:
-                u = _resample_linear(u, timedim, resample)
-                v = _resample_linear(v, timedim, resample)
-            t_new = np.asarray(u[timedim].values)
-            if window is not None:
-                r = _resample_ratio(t_orig, t_new)
-            step = (t_new[1] - t_new[0]).astype('timedelta64[s]').astype('float')
-        if window is None:                                                 # one window: the whole (resampled) record
-            n_windows, wlen, wstep = 1, int(np.asarray(u[timedim].values).size), 1
-        else:
-            n_windows = (nt - window) // stride + 1
-            wlen, wstep = (window - 1) * r + 1, stride * r
-
-        uu, time, lat, lon = _sorted_tll(u, timedim)                       # LCS.py:101-104
-        vv, _, _, _ = _sorted_tll(v, timedim)
-        eng = get_engine()
-        if isglobal:
-            from . import preprocess
-            if interp_to_common_grid:                                      # LCS.py:106-114
-                uu, lat_new, lon_new = preprocess.regrid_common_grid(eng, uu, lat, lon)
-                vv, _, _ = preprocess.regrid_common_grid(eng, vv, lat, lon)
-                lat, lon = lat_new, lon_new
-            if truncation is not None:                                     # LCS.py:115-118
-                gridtype = preprocess.inspect_gridtype(lat)
-                uu = preprocess.spectral_truncate(eng, uu, truncation, gridtype)
-                vv = preprocess.spectral_truncate(eng, vv, truncation, gridtype)
-            cyclic_xboundary = True                                        # LCS.py:119-120
-            self.subdomain = None
-        else:
-            cyclic_xboundary = False
-
-        verboseprint(f"*---- Parcel propagation: {n_windows} window(s), both directions ----*")
-        dtype = common_dtype(uu, vv, lat, lon)
-        lat_t, lon_t = lat.astype(dtype), lon.astype(dtype)
-        # the pack of the single-direction call (Engine.lcs_wind -> pack_and_advect), once for both directions
-        fuse, ext_image = eng._pack_options(dtype, self.SETTLS_order, eng.f64_fuse_levels(dtype, lat.size * lon.size), None)
-        field = eng.prepare_field(uu, vv, lat, lon, traj_interp_order, fuse_levels=fuse, ext_image=ext_image)
-        res = eng.lcs_bidirectional(field, lat_t, lon_t, step, wlen - 1, n_windows, 0, wstep, SETTLS_order=self.SETTLS_order,
-                                    interp_order=traj_interp_order, cyclic_xboundary=cyclic_xboundary,
-                                    gauss_sigma=self.gauss_sigma)
+        rec = self._record_intake(ds, u, v, window, stride, resample, isglobal, interp_to_common_grid, truncation, verbose)
+        verboseprint(f"*---- Parcel propagation: {rec.n_windows} window(s), both directions ----*")
+        res = self._run_windows("lcs_bidirectional", rec, abs(rec.timestep), traj_interp_order)
         verboseprint("*---- Done eigenvalues ----*")
 
         sig_all, x_all, y_all = (_to_np(res[k]) for k in ("sigma", "x_dep", "y_dep"))
-        slat, slon = lat, lon
-        if isinstance(self.subdomain, dict):                               # LCS.py:143-144
-            mlat, mlon = _crop_strict(lat, lon, self.subdomain)
-            sig_all, slat, slon = sig_all[:, :, mlat][:, :, :, mlon], lat[mlat], lon[mlon]
-        first = np.arange(n_windows) * wstep
-        name = getattr(u, "name", None)
-        dims3 = (timedim, "latitude", "longitude")
         out = []
         for d, forward in ((0, False), (1, True)):
-            labels = time[first + wlen - 1] if forward else time[first]    # LCS.py:158, per window
-            eigenvalues = _make(u, sig_all[d], dims3, {timedim: np.asarray(labels), "latitude": slat, "longitude": slon}, name)
+            eigenvalues = self._windows_out(rec, forward, sig_all[d], getattr(rec.like, "name", None))
             if not self.return_dpts:
                 out.append(eigenvalues)
             elif window is None:                                           # as __call__: (lat, lon) with a scalar time label
-                times = time.tolist()
-                c2 = {"latitude": lat, "longitude": lon, timedim: times[-1] if forward else times[0]}
-                out.append((eigenvalues, _make(u, x_all[d, 0], ("latitude", "longitude"), c2),
-                            _make(u, y_all[d, 0], ("latitude", "longitude"), c2)))
+                out.append((eigenvalues, self._departure_out(rec, x_all[d, 0], not forward),
+                            self._departure_out(rec, y_all[d, 0], not forward)))
             else:                                                          # as series
-                c3 = {timedim: np.asarray(labels), "latitude": lat, "longitude": lon}
-                out.append((eigenvalues, _make(u, x_all[d], dims3, c3), _make(u, y_all[d], dims3, c3)))
+                out.append((eigenvalues, self._windows_out(rec, forward, x_all[d], crop=False),
+                            self._windows_out(rec, forward, y_all[d], crop=False)))
         return tuple(out)
 
-    def _record_intake(self, ds, u, v, window, stride, resample, isglobal, interp_to_common_grid, truncation, verbose):
-        """The steps :meth:`series` takes before it packs, for one record: intake (LCS.py:81-96), the window / stride checks,
-        ``resample`` on the whole record (LCS.py:88-91), sort (LCS.py:101-104), the 0.5 degree regrid and the T20 truncation
-        (LCS.py:106-118).  ``window=None``: one window, the whole (resampled) record, as ``__call__``.  Returns the sorted
-        arrays and coordinates, the signed timestep, the window geometry in levels of the sorted record and the label source."""
+    def _record_intake(self, ds, u, v, window, stride, resample, isglobal, interp_to_common_grid, truncation, verbose) -> _Record:
+        """What every call form does with its record before the engine sees it: intake (LCS.py:81-96), the window / stride
+        checks, ``resample`` on the whole record (LCS.py:88-91), sort (LCS.py:101-104), the 0.5 degree regrid and the T20
+        truncation (LCS.py:106-118).  ``window=None``: one window, the whole (resampled) record, as ``__call__`` takes it."""
         timedim = self.timedim
         self.verbose = verbose
         if window is not None:
@@ -546,10 +380,11 @@ class LCS:
         assert set(u.dims) == set(v.dims), "u and v dims are different"                     # LCS.py:95
         assert set(u.dims) == {'latitude', 'longitude', timedim}, \
             'array dims should be latitude and longitude only'                             # LCS.py:96
-        t_orig = np.asarray(u[timedim].values)
-        nt = t_orig.size
-        if window is not None and window > nt:
-            raise ValueError(f"window {window} is longer than the record ({nt} time levels)")
+        if window is not None:
+            t_orig = np.asarray(u[timedim].values)
+            nt = t_orig.size
+            if window > nt:
+                raise ValueError(f"window {window} is longer than the record ({nt} time levels)")
         timestep = self.timestep
         r = 1
         if isinstance(resample, str):                                      # LCS.py:88-91, on the whole record
@@ -563,14 +398,14 @@ class LCS:
             if window is not None:
                 r = _resample_ratio(t_orig, t_new)
             timestep = np.sign(timestep) * (t_new[1] - t_new[0]).astype('timedelta64[s]').astype('float')
-        if window is None:                                                 # one window: the whole (resampled) record
-            n_windows, wlen, wstep = 1, int(np.asarray(u[timedim].values).size), 1
-        else:
-            n_windows = (nt - window) // stride + 1
-            wlen, wstep = (window - 1) * r + 1, stride * r                # a window and the distance between two, in levels
 
         uu, time, lat, lon = _sorted_tll(u, timedim)                       # LCS.py:101-104
         vv, _, _, _ = _sorted_tll(v, timedim)
+        if window is None:                                                 # one window: the whole (resampled) record
+            n_windows, wlen, wstep = 1, int(time.size), 1
+        else:
+            n_windows = (nt - window) // stride + 1
+            wlen, wstep = (window - 1) * r + 1, stride * r                # a window and the distance between two, in levels
         eng = get_engine()
         if isglobal:
             from . import preprocess
@@ -579,12 +414,45 @@ class LCS:
                 vv, _, _ = preprocess.regrid_common_grid(eng, vv, lat, lon)
                 lat, lon = lat_new, lon_new
             if truncation is not None:                                     # LCS.py:115-118
-                gridtype = preprocess.inspect_gridtype(lat)
+                gridtype = preprocess.inspect_gridtype(lat)              # windspharm's: equally spaced global, or Gaussian
                 uu = preprocess.spectral_truncate(eng, uu, truncation, gridtype)
                 vv = preprocess.spectral_truncate(eng, vv, truncation, gridtype)
             self.subdomain = None                                          # LCS.py:119-120
-        return dict(like=u, uu=uu, vv=vv, time=time, lat=lat, lon=lon, timestep=timestep, cyclic_xboundary=bool(isglobal),
-                    n_windows=n_windows, wlen=wlen, wstep=wstep)
+        return _Record(u, uu, vv, time, lat, lon, timestep, bool(isglobal), n_windows, wlen, wstep)
+
+    def _run_windows(self, method, rec: _Record, timestep, traj_interp_order):
+        """Pack the record once -- the pack of the per-window call (Engine.lcs_wind -> pack_and_advect) -- and run the engine's
+        ``method`` (``lcs_series``, ``lcs_bidirectional`` or ``lcs_strain``) over its windows."""
+        eng = get_engine()
+        lat, lon = rec.lat, rec.lon
+        dtype = common_dtype(rec.uu, rec.vv, lat, lon)
+        lat_t, lon_t = lat.astype(dtype), lon.astype(dtype)
+        fuse, ext_image = eng._pack_options(dtype, self.SETTLS_order, eng.f64_fuse_levels(dtype, lat.size * lon.size), None)
+        field = eng.prepare_field(rec.uu, rec.vv, lat, lon, traj_interp_order, fuse_levels=fuse, ext_image=ext_image)
+        return getattr(eng, method)(field, lat_t, lon_t, timestep, rec.wlen - 1, rec.n_windows, 0, rec.wstep,
+                                    SETTLS_order=self.SETTLS_order, interp_order=traj_interp_order,
+                                    cyclic_xboundary=rec.cyclic_xboundary, gauss_sigma=self.gauss_sigma)
+
+    def _windows_out(self, rec: _Record, forward, a, name=None, crop=True, lead=None):
+        """One result of an engine call, ``a`` with trailing axes (window, latitude, longitude), as a labelled array: the strict
+        ``subdomain`` crop over the last two axes (LCS.py:143-144; ``crop=False``: departure points, which keep the whole grid),
+        the time label of LCS.py:158 per window (its last time going forward, its first going backward) and dims
+        ``(*lead, timedim, latitude, longitude)``, ``lead`` mapping the dims in front to their coordinates."""
+        lat, lon = rec.lat, rec.lon
+        if crop and isinstance(self.subdomain, dict):
+            mlat, mlon = _crop_strict(lat, lon, self.subdomain)
+            a, lat, lon = a[..., mlat, :][..., mlon], lat[mlat], lon[mlon]
+        first = np.arange(rec.n_windows) * rec.wstep
+        labels = rec.time[first + rec.wlen - 1] if forward else rec.time[first]
+        lead = lead or {}
+        return _make(rec.like, a, (*lead, self.timedim, "latitude", "longitude"),
+                     {**lead, self.timedim: np.asarray(labels), "latitude": lat, "longitude": lon}, name)
+
+    def _departure_out(self, rec: _Record, a, backward):
+        """``__call__``'s form of ``x_dep`` / ``y_dep``: ``(latitude, longitude)`` with a scalar time, the last entry of the
+        (backward: reversed) time list (LCS.py:161-168 through trajectory.py:141-142)."""
+        return _make(rec.like, a, ("latitude", "longitude"),
+                     {"latitude": rec.lat, "longitude": rec.lon, self.timedim: rec.time.tolist()[0 if backward else -1]})
 
     def strain(self, ds=None, u=None, v=None, window=None, stride=1, verbose=True, s=None, resample=None, s_is_error=False,
                isglobal=False, interp_to_common_grid=True, traj_interp_order=3, truncation=20):
@@ -599,44 +467,24 @@ class LCS:
         point gives NaN in all three on the cells whose stencil touches it.
 
         ``window=None``: one entry, the whole record as ``__call__`` takes it; ``window=k``: the sliding windows of
-        :meth:`series` (same ``stride``, same time labels: LCS.py:158 per window).  Intake, ``resample``, sort, regrid / T20 and
-        the one pack are :meth:`series`'; the direction of integration is the sign of ``timestep``.  Then one
-        ``lc_advect_series`` call and one ``lc_strain`` call per memory group (``Engine.lcs_strain``).  With ``return_dpts``
-        ``x_dep`` and ``y_dep`` are appended, dims ``(timedim, latitude, longitude)``, as :meth:`series` appends them."""
+        :meth:`series` (same ``stride``, same time labels: LCS.py:158 per window).  Intake, ``resample``, sort, regrid / T20
+        (:meth:`_record_intake`) and the one pack are shared with :meth:`series`; the direction of integration is the sign of
+        ``timestep``.  Then one ``lc_advect_series`` call and one ``lc_strain`` call per memory group (``Engine.lcs_strain``).
+        With ``return_dpts`` ``x_dep`` and ``y_dep`` are appended, dims ``(timedim, latitude, longitude)``, as :meth:`series`
+        appends them."""
         verboseprint = print if verbose else (lambda *a, **k: None)
-        timedim = self.timedim
         rec = self._record_intake(ds, u, v, window, stride, resample, isglobal, interp_to_common_grid, truncation, verbose)
-        like, time, lat, lon, timestep = rec["like"], rec["time"], rec["lat"], rec["lon"], rec["timestep"]
-        n_windows, wlen, wstep = rec["n_windows"], rec["wlen"], rec["wstep"]
-        eng = get_engine()
-
-        verboseprint(f"*---- Parcel propagation: {n_windows} window(s) ----*")
-        dtype = common_dtype(rec["uu"], rec["vv"], lat, lon)
-        lat_t, lon_t = lat.astype(dtype), lon.astype(dtype)
-        # the pack of the per-window call (Engine.lcs_wind -> pack_and_advect), once for the whole record
-        fuse, ext_image = eng._pack_options(dtype, self.SETTLS_order, eng.f64_fuse_levels(dtype, lat.size * lon.size), None)
-        field = eng.prepare_field(rec["uu"], rec["vv"], lat, lon, traj_interp_order, fuse_levels=fuse, ext_image=ext_image)
-        res = eng.lcs_strain(field, lat_t, lon_t, timestep, wlen - 1, n_windows, 0, wstep, SETTLS_order=self.SETTLS_order,
-                             interp_order=traj_interp_order, cyclic_xboundary=rec["cyclic_xboundary"],
-                             gauss_sigma=self.gauss_sigma)
+        verboseprint(f"*---- Parcel propagation: {rec.n_windows} window(s) ----*")
+        res = self._run_windows("lcs_strain", rec, rec.timestep, traj_interp_order)
         verboseprint("*---- Done stretch factors ----*")
 
-        s1, s2 = _to_np(res["s1"]), _to_np(res["s2"])
+        forward = np.sign(rec.timestep) == 1
         e = np.stack([_to_np(res["e_lon"]), _to_np(res["e_lat"])])
-        slat, slon = lat, lon
-        if isinstance(self.subdomain, dict):                               # LCS.py:143-144
-            mlat, mlon = _crop_strict(lat, lon, self.subdomain)
-            s1, s2, e = s1[:, mlat][:, :, mlon], s2[:, mlat][:, :, mlon], e[:, :, mlat][:, :, :, mlon]
-            slat, slon = lat[mlat], lon[mlon]
-        first = np.arange(n_windows) * wstep
-        labels = time[first + wlen - 1] if np.sign(timestep) == 1 else time[first]     # LCS.py:158, per window
-        dims3 = (timedim, "latitude", "longitude")
-        c3 = {timedim: np.asarray(labels), "latitude": slat, "longitude": slon}
-        out = (_make(like, s1, dims3, c3, "s1"), _make(like, s2, dims3, c3, "s2"),
-               _make(like, e, ("component",) + dims3, {"component": np.array(["east", "north"]), **c3}, "direction"))
+        out = (self._windows_out(rec, forward, _to_np(res["s1"]), "s1"), self._windows_out(rec, forward, _to_np(res["s2"]), "s2"),
+               self._windows_out(rec, forward, e, "direction", lead={"component": np.array(["east", "north"])}))
         if self.return_dpts:                                               # LCS.py:161-168
-            c3 = {timedim: np.asarray(labels), "latitude": lat, "longitude": lon}
-            out += (_make(like, _to_np(res["x_dep"]), dims3, c3), _make(like, _to_np(res["y_dep"]), dims3, c3))
+            out += (self._windows_out(rec, forward, _to_np(res["x_dep"]), crop=False),
+                    self._windows_out(rec, forward, _to_np(res["y_dep"]), crop=False))
         return out
 
 

@@ -1102,16 +1102,75 @@ class Engine:
             out["traj_x"], out["traj_y"] = res[2], res[3]
         return out
 
-    # device memory one lcs_series group may hold (positions, saved positions and Euler samples of the outer rule, sigma)
+    # device memory one group of windows may hold (positions, saved positions and Euler samples of the outer rule, results)
     SERIES_MEM_CAP = 2 << 30
 
-    def series_group(self, dtype, n_seeds: int, n_windows: int, cyclic_xboundary=True) -> int:
-        """Windows per :meth:`lcs_series` group: as many as fit ``SERIES_MEM_CAP`` (at least one).  Per window: x, y and sigma,
-        plus -- under the reference's non-cyclic clamp -- the positions saved before each chunk and the Euler sample of the
-        sub-step phase (two planes each), and the smoothing's two scratch planes."""
-        planes = 5 if cyclic_xboundary else 9
+    def series_group(self, dtype, n_seeds: int, n_windows: int, cyclic_xboundary=True, extra_planes: int = 0) -> int:
+        """Windows per group of :meth:`lcs_series`, :meth:`lcs_bidirectional` and :meth:`lcs_strain`: as many as fit
+        ``SERIES_MEM_CAP`` (at least one).  Per window: x, y and sigma, plus -- under the reference's non-cyclic clamp -- the
+        positions saved before each chunk and the Euler sample of the sub-step phase (two planes each), and the smoothing's two
+        scratch planes.  ``extra_planes``: the result planes of a window beyond the first (:meth:`lcs_strain`: three)."""
+        planes = (5 if cyclic_xboundary else 9) + int(extra_planes)
         per = planes * int(n_seeds) * np.dtype(dtype).itemsize
         return max(1, min(int(n_windows), int(self.SERIES_MEM_CAP) // max(per, 1)))
+
+    def _windowed(self, name, reduce, field: PackedField, seed_lat, seed_lon, timestep, nsteps, n_windows, t0, t0_stride,
+                  SETTLS_order, interp_order, cyclic_xboundary, gauss_sigma, fd_fp32_cast, noncyclic_clamp, n_dirs=1,
+                  extra_planes=0):
+        """The loop of :meth:`lcs_series`, :meth:`lcs_bidirectional` and :meth:`lcs_strain` (``name``: the caller, for its
+        errors): the argument checks, the seeds on the device, then per memory group (:meth:`series_group`) one advect call
+        over the group's windows -- ``lc_advect_series``, or ``lc_advect_series_dirs`` for ``n_dirs = 2`` --, the optional
+        smoothing plane by plane, and one reduction of the group's departure planes.
+
+        ``reduce(head, planes, outs)`` calls the library and returns its status: ``head`` is the argument list that
+        ``lc_sigma_batch`` and ``lc_strain`` begin with (context, x, y, dtype, ny, nx, seed latitudes, dlat, dlon,
+        fd_fp32_cast) for ``planes`` whole grids, ``outs`` the group's part of each of the ``1 + extra_planes`` results.
+        Returns ``(x_dep, y_dep, results)``, every tensor ``(n_windows, ny, nx)``, or ``(n_windows, 2, ny, nx)`` for
+        ``n_dirs = 2``."""
+        if interp_order != 1 and field.order != interp_order:
+            raise ValueError(f"field was prepared for interp_order={field.order}")
+        if n_dirs == 2:
+            timestep = float(timestep)
+            if not timestep or not np.isfinite(timestep):
+                raise ValueError(f"{name}: timestep {timestep} (non-zero: its sign is taken from the direction)")
+            timestep = -abs(timestep)
+        n_windows, nsteps, t0, t0_stride = int(n_windows), int(nsteps), int(t0), int(t0_stride)
+        if n_windows < 1 or nsteps < 0 or t0 < 0 or t0_stride < 0:
+            raise ValueError(f"{name}: n_windows {n_windows}, nsteps {nsteps}, t0 {t0}, t0_stride {t0_stride}")
+        dtype = field.dtype
+        seed_lat = np.asarray(seed_lat, dtype=dtype)
+        seed_lon = np.asarray(seed_lon, dtype=dtype)
+        slat, slon = self.to_device(seed_lat, dtype), self.to_device(seed_lon, dtype)
+        ny, nx = int(slat.numel()), int(slon.numel())
+        # two directions in the library's plane order: window-major, [n_windows][2][ny][nx], plane 2w + d with -timestep for d = 1
+        shape = (n_windows, ny, nx) if n_dirs == 1 else (n_windows, n_dirs, ny, nx)
+        x, y, *outs = (self._empty(shape, dtype) for _ in range(3 + extra_planes))
+        xmode = x_boundary_mode(cyclic_xboundary, noncyclic_clamp, True)
+        smooth = isinstance(gauss_sigma, (float, int)) and not isinstance(gauss_sigma, bool) and gauss_sigma > 1e-15
+        dlat = float(seed_lat[1] - seed_lat[0])     # as _sigma_of: the spacing in the coordinate dtype (tools.py:255-256)
+        dlon = float(seed_lon[1] - seed_lon[0])
+        g = self.series_group(dtype, n_dirs * ny * nx, n_windows, cyclic_xboundary, extra_planes)
+        for m0 in range(0, n_windows, g):
+            n = min(g, n_windows - m0)
+            xg, yg = x[m0:m0 + n], y[m0:m0 + n]
+            self._use_current_stream()
+            a = self._advect_args(field, interp_order, slat, ny, slon, nx, 0, ny, None, None, timestep, SETTLS_order, xmode,
+                                  t0 + m0 * t0_stride, nsteps, n, t0_stride, xg, yg, None, None)
+            _capi.check(self.lib.lc_advect_series(self.ctx, C.byref(a)) if n_dirs == 1 else
+                        self.lib.lc_advect_series_dirs(self.ctx, C.byref(a), n_dirs), self.lib)
+            planes = n_dirs * n
+            xs, ys = xg.reshape(planes, ny, nx), yg.reshape(planes, ny, nx)
+            if smooth:     # scipy's gaussian_filter of each plane's departure points (LCS/LCS.py:187-190), as _sigma_of
+                xs = self.torch.stack([self.gaussian_filter(xs[i], gauss_sigma) for i in range(planes)])
+                ys = self.torch.stack([self.gaussian_filter(ys[i], gauss_sigma) for i in range(planes)])
+            self._use_current_stream()
+            head = (self.ctx, self._ptr(xs), self._ptr(ys), _NP2LC[dtype], ny, nx, self._ptr(slat), dlat, dlon, int(bool(fd_fp32_cast)))
+            _capi.check(reduce(head, planes, [self._ptr(t[m0:m0 + n]) for t in outs]), self.lib)
+        return x, y, outs
+
+    def _sigma_planes(self, tensor_layout):
+        """:meth:`_windowed`'s reduction to sigma_max (``lc_sigma_batch``)."""
+        return lambda head, planes, outs: self.lib.lc_sigma_batch(*head, _LAYOUTS[tensor_layout], planes, *outs)
 
     def lcs_series(self, field: PackedField, seed_lat, seed_lon, timestep, nsteps: int, n_windows: int, t0=0, t0_stride=1,
                    SETTLS_order=0, interp_order=1, cyclic_xboundary=True, gauss_sigma=None, fd_fp32_cast=True,
@@ -1124,37 +1183,9 @@ class Engine:
         window decides on its own whether and from which chunk it re-runs sub-step by sub-step) and one ``lc_sigma_batch``
         call per group of windows; groups are as large as ``SERIES_MEM_CAP`` allows (:meth:`series_group`), and the results
         do not depend on the grouping."""
-        if interp_order != 1 and field.order != interp_order:
-            raise ValueError(f"field was prepared for interp_order={field.order}")
-        n_windows, nsteps, t0, t0_stride = int(n_windows), int(nsteps), int(t0), int(t0_stride)
-        if n_windows < 1 or nsteps < 0 or t0 < 0 or t0_stride < 0:
-            raise ValueError(f"lcs_series: n_windows {n_windows}, nsteps {nsteps}, t0 {t0}, t0_stride {t0_stride}")
-        dtype = field.dtype
-        seed_lat = np.asarray(seed_lat, dtype=dtype)
-        seed_lon = np.asarray(seed_lon, dtype=dtype)
-        slat, slon = self.to_device(seed_lat, dtype), self.to_device(seed_lon, dtype)
-        ny, nx = int(slat.numel()), int(slon.numel())
-        x, y, sig = (self._empty((n_windows, ny, nx), dtype) for _ in range(3))
-        xmode = x_boundary_mode(cyclic_xboundary, noncyclic_clamp, True)
-        smooth = isinstance(gauss_sigma, (float, int)) and not isinstance(gauss_sigma, bool) and gauss_sigma > 1e-15
-        dlat = float(seed_lat[1] - seed_lat[0])     # as _sigma_of: the spacing in the coordinate dtype (tools.py:255-256)
-        dlon = float(seed_lon[1] - seed_lon[0])
-        g = self.series_group(dtype, ny * nx, n_windows, cyclic_xboundary)
-        for m0 in range(0, n_windows, g):
-            n = min(g, n_windows - m0)
-            xg, yg = x[m0:m0 + n], y[m0:m0 + n]
-            self._use_current_stream()
-            a = self._advect_args(field, interp_order, slat, ny, slon, nx, 0, ny, None, None, timestep, SETTLS_order, xmode,
-                                  t0 + m0 * t0_stride, nsteps, n, t0_stride, xg, yg, None, None)
-            _capi.check(self.lib.lc_advect_series(self.ctx, C.byref(a)), self.lib)
-            xs, ys = xg, yg
-            if smooth:     # scipy's gaussian_filter of each window's departure points (LCS/LCS.py:187-190), as _sigma_of
-                xs = self.torch.stack([self.gaussian_filter(xg[i], gauss_sigma) for i in range(n)])
-                ys = self.torch.stack([self.gaussian_filter(yg[i], gauss_sigma) for i in range(n)])
-            self._use_current_stream()
-            _capi.check(self.lib.lc_sigma_batch(self.ctx, self._ptr(xs), self._ptr(ys), _NP2LC[dtype], ny, nx, self._ptr(slat),
-                                                dlat, dlon, int(bool(fd_fp32_cast)), _LAYOUTS[tensor_layout], n,
-                                                self._ptr(sig[m0:m0 + n])), self.lib)
+        x, y, (sig,) = self._windowed("lcs_series", self._sigma_planes(tensor_layout), field, seed_lat, seed_lon, timestep, nsteps,
+                                      n_windows, t0, t0_stride, SETTLS_order, interp_order, cyclic_xboundary, gauss_sigma,
+                                      fd_fp32_cast, noncyclic_clamp)
         return {"sigma": sig, "x_dep": x, "y_dep": y}
 
     def lcs_bidirectional(self, field: PackedField, seed_lat, seed_lon, timestep, nsteps: int, n_windows: int = 1, t0=0,
@@ -1168,41 +1199,9 @@ class Engine:
         One ``lc_advect_series_dirs`` call (both directions of every window in one launch per level chunk) and one
         ``lc_sigma_batch`` call per group of windows; a group counts two planes per window against ``SERIES_MEM_CAP``, and the
         results do not depend on the grouping."""
-        if interp_order != 1 and field.order != interp_order:
-            raise ValueError(f"field was prepared for interp_order={field.order}")
-        timestep = float(timestep)
-        if not timestep or not np.isfinite(timestep):
-            raise ValueError(f"lcs_bidirectional: timestep {timestep} (non-zero: its sign is taken from the direction)")
-        n_windows, nsteps, t0, t0_stride = int(n_windows), int(nsteps), int(t0), int(t0_stride)
-        if n_windows < 1 or nsteps < 0 or t0 < 0 or t0_stride < 0:
-            raise ValueError(f"lcs_bidirectional: n_windows {n_windows}, nsteps {nsteps}, t0 {t0}, t0_stride {t0_stride}")
-        dtype = field.dtype
-        seed_lat = np.asarray(seed_lat, dtype=dtype)
-        seed_lon = np.asarray(seed_lon, dtype=dtype)
-        slat, slon = self.to_device(seed_lat, dtype), self.to_device(seed_lon, dtype)
-        ny, nx = int(slat.numel()), int(slon.numel())
-        # the library's plane order: window-major, [n_windows][2][ny][nx], plane 2w + d with -timestep for d = 1
-        x, y, sig = (self._empty((n_windows, 2, ny, nx), dtype) for _ in range(3))
-        xmode = x_boundary_mode(cyclic_xboundary, noncyclic_clamp, True)
-        smooth = isinstance(gauss_sigma, (float, int)) and not isinstance(gauss_sigma, bool) and gauss_sigma > 1e-15
-        dlat = float(seed_lat[1] - seed_lat[0])     # as _sigma_of: the spacing in the coordinate dtype (tools.py:255-256)
-        dlon = float(seed_lon[1] - seed_lon[0])
-        g = self.series_group(dtype, 2 * ny * nx, n_windows, cyclic_xboundary)
-        for m0 in range(0, n_windows, g):
-            n = min(g, n_windows - m0)
-            xg, yg = x[m0:m0 + n], y[m0:m0 + n]
-            self._use_current_stream()
-            a = self._advect_args(field, interp_order, slat, ny, slon, nx, 0, ny, None, None, -abs(timestep), SETTLS_order,
-                                  xmode, t0 + m0 * t0_stride, nsteps, n, t0_stride, xg, yg, None, None)
-            _capi.check(self.lib.lc_advect_series_dirs(self.ctx, C.byref(a), 2), self.lib)
-            xs, ys = xg.reshape(2 * n, ny, nx), yg.reshape(2 * n, ny, nx)
-            if smooth:     # scipy's gaussian_filter of each plane's departure points (LCS/LCS.py:187-190), as _sigma_of
-                xs = self.torch.stack([self.gaussian_filter(xs[i], gauss_sigma) for i in range(2 * n)])
-                ys = self.torch.stack([self.gaussian_filter(ys[i], gauss_sigma) for i in range(2 * n)])
-            self._use_current_stream()
-            _capi.check(self.lib.lc_sigma_batch(self.ctx, self._ptr(xs), self._ptr(ys), _NP2LC[dtype], ny, nx, self._ptr(slat),
-                                                dlat, dlon, int(bool(fd_fp32_cast)), _LAYOUTS[tensor_layout], 2 * n,
-                                                self._ptr(sig[m0:m0 + n])), self.lib)
+        x, y, (sig,) = self._windowed("lcs_bidirectional", self._sigma_planes(tensor_layout), field, seed_lat, seed_lon, timestep,
+                                      nsteps, n_windows, t0, t0_stride, SETTLS_order, interp_order, cyclic_xboundary, gauss_sigma,
+                                      fd_fp32_cast, noncyclic_clamp, n_dirs=2)
         return {k: t.transpose(0, 1).contiguous() for k, t in (("sigma", sig), ("x_dep", x), ("y_dep", y))}
 
     def sigma_batch(self, x_dep, y_dep, seed_lat, dlat, dlon, fd_fp32_cast=True, tensor_layout="reference"):
@@ -1267,39 +1266,10 @@ class Engine:
         call per memory group.  Returns ``{"s1", "s2", "e_lon", "e_lat", "x_dep", "y_dep"}`` as ``(n_windows, ny, nx)`` device
         tensors; ``x_dep`` / ``y_dep`` equal :meth:`lcs_series`' bit for bit.  ``gauss_sigma`` smooths the departure fields
         first, as there."""
-        if interp_order != 1 and field.order != interp_order:
-            raise ValueError(f"field was prepared for interp_order={field.order}")
-        n_windows, nsteps, t0, t0_stride = int(n_windows), int(nsteps), int(t0), int(t0_stride)
-        if n_windows < 1 or nsteps < 0 or t0 < 0 or t0_stride < 0:
-            raise ValueError(f"lcs_strain: n_windows {n_windows}, nsteps {nsteps}, t0 {t0}, t0_stride {t0_stride}")
-        dtype = field.dtype
-        seed_lat = np.asarray(seed_lat, dtype=dtype)
-        seed_lon = np.asarray(seed_lon, dtype=dtype)
-        slat, slon = self.to_device(seed_lat, dtype), self.to_device(seed_lon, dtype)
-        ny, nx = int(slat.numel()), int(slon.numel())
-        x, y, s1, s2, ex, ey = (self._empty((n_windows, ny, nx), dtype) for _ in range(6))
-        xmode = x_boundary_mode(cyclic_xboundary, noncyclic_clamp, True)
-        smooth = isinstance(gauss_sigma, (float, int)) and not isinstance(gauss_sigma, bool) and gauss_sigma > 1e-15
-        dlat = float(seed_lat[1] - seed_lat[0])     # as _sigma_of: the spacing in the coordinate dtype (tools.py:255-256)
-        dlon = float(seed_lon[1] - seed_lon[0])
-        # series_group's count with the three planes a window holds here on top of lcs_series' (s2, e_lon, e_lat)
-        per = (8 if cyclic_xboundary else 12) * ny * nx * np.dtype(dtype).itemsize
-        g = max(1, min(n_windows, int(self.SERIES_MEM_CAP) // per))
-        for m0 in range(0, n_windows, g):
-            n = min(g, n_windows - m0)
-            xg, yg = x[m0:m0 + n], y[m0:m0 + n]
-            self._use_current_stream()
-            a = self._advect_args(field, interp_order, slat, ny, slon, nx, 0, ny, None, None, timestep, SETTLS_order, xmode,
-                                  t0 + m0 * t0_stride, nsteps, n, t0_stride, xg, yg, None, None)
-            _capi.check(self.lib.lc_advect_series(self.ctx, C.byref(a)), self.lib)
-            xs, ys = xg, yg
-            if smooth:     # scipy's gaussian_filter of each window's departure points (LCS/LCS.py:187-190), as _sigma_of
-                xs = self.torch.stack([self.gaussian_filter(xg[i], gauss_sigma) for i in range(n)])
-                ys = self.torch.stack([self.gaussian_filter(yg[i], gauss_sigma) for i in range(n)])
-            self._use_current_stream()
-            _capi.check(self.lib.lc_strain(self.ctx, self._ptr(xs), self._ptr(ys), _NP2LC[dtype], ny, nx, self._ptr(slat), dlat, dlon,
-                                           int(bool(fd_fp32_cast)), n, *(self._ptr(t[m0:m0 + n]) for t in (s1, s2, ex, ey))), self.lib)
-        return {"s1": s1, "s2": s2, "e_lon": ex, "e_lat": ey, "x_dep": x, "y_dep": y}
+        x, y, outs = self._windowed("lcs_strain", lambda head, planes, outs: self.lib.lc_strain(*head, planes, *outs), field, seed_lat,
+                                    seed_lon, timestep, nsteps, n_windows, t0, t0_stride, SETTLS_order, interp_order, cyclic_xboundary,
+                                    gauss_sigma, fd_fp32_cast, noncyclic_clamp, extra_planes=len(self._STRAIN_PLANES) - 1)
+        return {**dict(zip(self._STRAIN_PLANES, outs)), "x_dep": x, "y_dep": y}
 
     def synchronize(self):
         self.torch.cuda.synchronize(self.device)

@@ -9,6 +9,7 @@ The expected value is always ``oracle.flowmap_gradient`` -> F -> ``numpy.linalg.
   * the rule cases: identity map, one NaN departure point;
   * batches against single calls, the kernel names;
   * float32 inside the band of the float32 oracle's own error around the float64 answer, small fields and a 4096 x 4096 run;
+  * the memory-capped grouping of ``lcs_strain`` gives the bits of one group;
   * the drop-in contract of ``LCS.strain``."""
 import numpy as np
 import pandas as pd
@@ -18,6 +19,7 @@ from lagrangiancoherence_amd import flows
 from tests import _strain as S
 from tests import labelled
 from tests._fullsize import band, dilate
+from tests.test_series_gpu import _diverging_wind
 
 pytestmark = pytest.mark.gpu
 
@@ -222,6 +224,29 @@ def test_float32_full_size_4096(eng, O):
         t64 = S.svd_reference(O.flowmap_gradient(c64(xw), c64(yw), c64(slat[ra:rb]), c64(slon[c0 - 2:c1 + 2]), fd_fp32_cast=False,
                                                  dlat=float(dl["dlat"]), dlon=float(dl["dlon"])))
         _band32(f"4096^2 {label}", got, o32, tuple(cut(a) for a in t64))
+
+
+# ------------------------------------------------------------------------------------------ memory groups
+@pytest.mark.parametrize("cyclic", [True, False])
+def test_memory_capped_groups_give_the_bits_of_one_group(eng, cyclic):
+    """tests/test_series_gpu.py's test of this name for ``lcs_strain``: 5 windows of its diverging wind (non-cyclic: the last
+    two leave the box) in groups of 1 and of 2 against one group, all six outputs bit for bit; a window holds three planes more
+    than a window of ``lcs_series`` (8 / 12 instead of 5 / 9)."""
+    u, v, lat, lon = _diverging_wind(np.float32)
+    f = eng.prepare_field(u, v, lat, lon, 3)
+    kw = dict(SETTLS_order=2, interp_order=3, cyclic_xboundary=cyclic)
+    whole = eng.lcs_strain(f, lat, lon, 3600.0, 20, 5, t0=0, t0_stride=2, **kw)
+    per = (8 if cyclic else 12) * lat.size * lon.size * 4
+    assert eng.series_group(np.float32, lat.size * lon.size, 5, cyclic, 3) == 5
+    try:
+        for g in (1, 2):
+            eng.SERIES_MEM_CAP = g * per
+            assert eng.series_group(np.float32, lat.size * lon.size, 5, cyclic, 3) == g
+            part = eng.lcs_strain(f, lat, lon, 3600.0, 20, 5, t0=0, t0_stride=2, **kw)
+            for k in PLANES + ("x_dep", "y_dep"):
+                assert np.array_equal(_np(whole[k]), _np(part[k]), equal_nan=True), (g, k)
+    finally:
+        del eng.SERIES_MEM_CAP
 
 
 # ------------------------------------------------------------------------------------------ the drop-in contract

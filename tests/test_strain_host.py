@@ -1,7 +1,7 @@
 """``LCS.strain`` and ``lc_strain`` on the CPU: the symbols and their argument checks before any device call, the signatures
 of the engine and drop-in methods, the drop-in's argument handling (window / stride validation, window count, time labels for
 both signs of ``timestep``, the ``subdomain`` crop, the ``return_dpts`` tuple) through a stand-in engine answering with the CPU
-oracle, and the closed form the kernel implements, stated in numpy (tests/_strain.py), against ``numpy.linalg.svd`` on the
+oracle, the one intake of the four call forms (what each hands to the engine, bit for bit), and the closed form the kernel implements, stated in numpy (tests/_strain.py), against ``numpy.linalg.svd`` on the
 golden departure fields.  The arithmetic on the GPU is tests/test_strain_gpu.py's."""
 import inspect
 
@@ -10,11 +10,13 @@ import pandas as pd
 import pytest
 import torch
 
-from lagrangiancoherence_amd import _capi, build, dropin, flows
+from lagrangiancoherence_amd import _capi, build, dropin, flows, preprocess
 from lagrangiancoherence_amd.engine import Engine
 from oracle import lcs_oracle as O
+from oracle import preprocess_oracle as P
 from tests import _strain as S
 from tests import labelled
+from tests.test_bidir_host import OracleBidirEngine
 from tests.test_capi_symbols import declared_symbols
 from tests.test_series_host import OracleSeriesEngine
 
@@ -71,10 +73,9 @@ def test_signatures():
     assert sig.parameters["n_windows"].default == 1 and sig.parameters["t0"].default == 0 and sig.parameters["t0_stride"].default == 1
     # the advection arguments of lcs_series, all of them (tensor_layout has no meaning here: the layout is the physical one)
     assert set(series.parameters) - set(sig.parameters) == {"tensor_layout"}
-    # the bodies of the three existing call forms do not go through the new intake helper (a follow-up)
-    for f in (LCS.__call__, LCS.series, LCS.bidirectional):
-        assert "_record_intake" not in inspect.getsource(f)
-    assert "_record_intake" in inspect.getsource(LCS.strain)
+    # all four call forms take their record from the one intake
+    for f in (LCS.__call__, LCS.series, LCS.bidirectional, LCS.strain):
+        assert "_record_intake" in inspect.getsource(f)
 
 
 # ------------------------------------------------------------------ drop-in adapter through a stand-in engine
@@ -199,6 +200,111 @@ def test_subdomain_crop_applies_to_the_fields_not_to_the_departure_points():
     g = LCS(timestep=-6 * 3600, timedim="time", SETTLS_order=1, subdomain=sub).strain(
         ds, window=3, verbose=False, traj_interp_order=1, isglobal=True, interp_to_common_grid=False, truncation=None)
     assert g[0].shape == (3, lat.size, lon.size)
+
+
+# ------------------------------------------------------------------ one intake for the four call forms
+class IntakeRecorder(OracleStrainEngine, OracleBidirEngine):
+    """The stand-in engines of the four call forms in one, recording what each is handed: the wind of ``lcs_wind``, the pack of
+    ``prepare_field``, the arguments of the windowed calls.  ``regrid`` and ``spectral_truncate`` answer with the oracle's."""
+
+    def __init__(self):
+        self.wind, self.packed, self.windows = [], [], []
+        self.series_calls, self.bidir_calls, self.strain_calls = [], [], []
+
+    def regrid(self, u, lat, lon, lats, lons):
+        return torch.as_tensor(np.ascontiguousarray(P.regrid_common_grid(np.asarray(u), lat, lon, lats, lons)[0]))
+
+    def spectral_truncate(self, f, T=20, gridtype="regular"):
+        return torch.as_tensor(np.ascontiguousarray(P.spectral_truncate(np.asarray(f), T, gridtype)))
+
+    def lcs_wind(self, u, v, lat, lon, slat, slon, timestep, **kw):
+        self.wind.append(dict(u=np.asarray(u).copy(), v=np.asarray(v).copy(), lat=lat, lon=lon, slat=slat, slon=slon,
+                              step=abs(timestep), order=kw["interp_order"], K=kw["SETTLS_order"], cyclic=kw["cyclic_xboundary"],
+                              gauss=kw["gauss_sigma"]))
+        n = len(self.packed)
+        res = super().lcs_wind(u, v, lat, lon, slat, slon, timestep, **kw)
+        del self.packed[n:]                         # (the stand-in's lcs_wind packs through prepare_field)
+        return res
+
+    def prepare_field(self, u, v, lat, lon, interp_order=1, dtype=None, fuse_levels=None, ext_image=None):
+        self.packed.append(dict(u=np.asarray(u).copy(), v=np.asarray(v).copy(), lat=lat, lon=lon, order=interp_order,
+                                fuse_levels=fuse_levels, ext_image=ext_image))
+        return super().prepare_field(u, v, lat, lon, interp_order, dtype, fuse_levels, ext_image)
+
+    def _windowed(name):
+        def call(self, f, slat, slon, timestep, nsteps, n_windows=1, t0=0, t0_stride=1, **kw):
+            # (t0_stride is left out: with one window it has no meaning, and series(window=nt) and window=None differ in it)
+            self.windows.append(dict(slat=slat, slon=slon, step=abs(timestep), nsteps=nsteps, n_windows=n_windows, t0=t0,
+                                     order=kw["interp_order"], K=kw["SETTLS_order"], cyclic=kw["cyclic_xboundary"],
+                                     gauss=kw["gauss_sigma"]))
+            return getattr(super(IntakeRecorder, self), name)(f, slat, slon, timestep, nsteps, n_windows, t0, t0_stride, **kw)
+        return call
+
+    lcs_series, lcs_bidirectional, lcs_strain = _windowed("lcs_series"), _windowed("lcs_bidirectional"), _windowed("lcs_strain")
+    del _windowed
+
+
+def _same_bits(a, b):
+    assert a.keys() == b.keys()
+    for k in a:
+        if isinstance(a[k], np.ndarray):
+            assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]), k
+        else:
+            assert a[k] == b[k] and type(a[k]) is type(b[k]), k
+
+
+@pytest.mark.parametrize("timestep", [6 * 3600, -6 * 3600])
+@pytest.mark.parametrize("isglobal", [False, True])
+def test_the_four_call_forms_hand_the_engine_the_same_record(monkeypatch, timestep, isglobal):
+    """One record through every branch of the intake -- descending latitude, unsorted longitude, a ``resample`` that halves the
+    spacing, a ``subdomain``, both signs of ``timestep``; with ``isglobal`` the 0.5 degree regrid, the T20 truncation and the
+    ``subdomain = None`` rule -- and through ``__call__``, ``series(window=nt)``, ``bidirectional(window=None)`` and
+    ``strain(window=None)``: what reaches the engine is the same bit for bit (``__call__``: the wind and the coordinates of
+    ``lcs_wind``; the others: the pack of ``prepare_field`` with the options ``_pack_options`` chose, and the step's magnitude and
+    the window geometry of the windowed call), and sigma and its time label are the same in the three forms that return one."""
+    from LagrangianCoherence.LCS.LCS import LCS
+    nt = 2 if isglobal else 3                   # (the 0.5 degree grid has 16 times the cells: the oracle's time)
+    ds, times, lat, lon = _dataset(nt=nt)
+    ilat, ilon = np.arange(lat.size)[::-1], np.roll(np.arange(lon.size), 7)
+    ds = labelled.Dataset({k: ds[k].isel(latitude=ilat, longitude=ilon) for k in ("u", "v")})
+    assert ds.u.coords["latitude"][0] > ds.u.coords["latitude"][1] and np.any(np.diff(ds.u.coords["longitude"]) < 0)
+    sub = {"latitude": slice(-40, 40), "longitude": slice(-100, 100)}
+    ctor = dict(timestep=timestep, timedim="time", SETTLS_order=1, subdomain=sub, gauss_sigma=1.0)
+    call = dict(resample="3h", isglobal=isglobal, verbose=False, traj_interp_order=1)
+    forms = {"call": lambda l: l(ds, **call), "series": lambda l: l.series(ds, window=nt, **call),
+             "bidirectional": lambda l: l.bidirectional(ds, **call), "strain": lambda l: l.strain(ds, **call)}
+    out, rec = {}, {}
+    for name, form in forms.items():
+        rec[name] = eng = IntakeRecorder()
+        monkeypatch.setattr(dropin, "_ENGINE", eng)
+        monkeypatch.setattr(dropin, "get_engine", lambda eng=eng: eng)
+        lcs = LCS(**ctor)
+        out[name] = form(lcs)
+        assert (lcs.subdomain is None) == isglobal                     # LCS.py:119-120
+    # what the engine was handed
+    wind, = rec["call"].wind
+    assert not rec["call"].packed and not rec["call"].windows
+    glat, glon = (preprocess.COMMON_LATS, preprocess.COMMON_LONS) if isglobal else (lat, lon)
+    assert np.array_equal(wind["lat"], glat) and np.array_equal(wind["lon"], glon)
+    assert wind["u"].shape == (2 * nt - 1, glat.size, glon.size) and wind["step"] == 3 * 3600.0 and wind["cyclic"] is isglobal
+    for name in ("series", "bidirectional", "strain"):
+        assert not rec[name].wind
+        (packed,), (windows,) = rec[name].packed, rec[name].windows
+        for got, keys in ((packed, ("u", "v", "lat", "lon", "order")), (windows, ("slat", "slon", "step", "K", "cyclic", "gauss"))):
+            _same_bits({k: got[k] for k in keys}, {k: wind[k] for k in keys})
+        _same_bits(packed, rec["series"].packed[0])
+        _same_bits(windows, rec["series"].windows[0])
+        assert (packed["fuse_levels"], packed["ext_image"]) == Engine._pack_options(np.dtype(np.float64), 1, False, None)
+        assert (windows["nsteps"], windows["n_windows"], windows["t0"]) == (2 * nt - 2, 1, 0)
+    # sigma and its label
+    one, ser, both = out["call"], out["series"], out["bidirectional"][timestep > 0]
+    for a in (ser, both):
+        assert a.dims == one.dims and a.shape == one.shape and np.array_equal(a.values, one.values)
+        for k in one.coords:
+            assert np.array_equal(np.asarray(a.coords[k]), np.asarray(one.coords[k])), k
+    assert one.coords["time"][0] == (times[-1] if timestep > 0 else times[0]) == out["strain"][0].coords["time"][0]
+    mlat, mlon = (lat > -40) & (lat < 40), (lon > -100) & (lon < 100)
+    assert one.shape == ((1, glat.size, glon.size) if isglobal else (1, mlat.sum(), mlon.sum())) == out["strain"][0].shape
 
 
 # ------------------------------------------------------------------ the closed form against numpy's SVD
