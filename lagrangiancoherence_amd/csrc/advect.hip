@@ -113,7 +113,15 @@ __device__ __forceinline__ int xcd_tile_id(const AdvectArgs<T> &A) {
 }
 template <typename T>
 static inline unsigned nmem(const AdvectArgs<T> &A) { return A.n_members > 1 ? (unsigned)A.n_members : 1u; }  // grid.y of an advect launch
-static inline int xcd_grid(int ntiles, int chunk) { return lcplan::xcd_grid(ntiles, chunk); }
+
+// The one launch form of the advect kernel families: `kernel` on grid x members workgroups of BLOCK threads, with A and
+// whatever the kernel takes after it.  Returns `name`: the kernel as a profiler prints it -- at every call a quoted literal,
+// which tests/kernel_routes.py's table and bench.py's profile matching read from this file.
+template <typename K, typename T, typename... Extra>
+static inline const char *launch_kernel(K kernel, int grid, hipStream_t st, const AdvectArgs<T> &A, const char *name, const Extra &...extra) {
+    hipLaunchKernelGGL(kernel, dim3(grid, nmem(A)), dim3(BLOCK), 0, st, A, extra...);
+    return name;
+}
 
 template <typename T>
 struct Pair {
@@ -2588,6 +2596,27 @@ static inline bool order1_two_seed_applies(const AdvectArgs<float> &A, int mode)
 template <typename T>
 static inline bool order1_two_seed_applies(const AdvectArgs<T> &, int) { return false; }
 
+// Patch mode and launch grid of the two-seed kernels (orders 1 and 3): a workgroup covers 8 x 64 seeds (PATCH_TALL), 16 x 32
+// (PATCH_WIDE) or 32 x 16 (PATCH_LINES).  The context's patch mode where one is set and `takes_set_mode`, else by call: whole-line
+// stores with trajectories that allow them, tall patches without.  Fills A.ntx, A.ntiles and A.xcd_chunk for that patch
+// shape, `grid` with the workgroups of the launch; returns the mode.
+static inline int two_seed_patch_grid(AdvectArgs<float> &A, bool takes_set_mode, int &grid) {
+    const int mode = (A.patch_mode >= 0 && takes_set_mode) ? A.patch_mode
+                                                            : (A.traj_x && A.traj_line_ok && A.nx >= TILE_W * 4 ? PATCH_LINES : PATCH_TALL);
+    int nty = (A.ny + TILE_H * SPL - 1) / (TILE_H * SPL);
+    if (mode == PATCH_WIDE) {
+        A.ntx = (A.nx + TILE_W * SPL - 1) / (TILE_W * SPL);
+        nty = (A.ny + TILE_H - 1) / TILE_H;
+    } else if (mode == PATCH_LINES) {
+        A.ntx = (A.nx + TILE_W * 4 - 1) / (TILE_W * 4);
+        nty = (A.ny + 8 * SPL - 1) / (8 * SPL);
+    }
+    A.xcd_chunk = lcplan::xcd_chunk_tiles(A.ntx, nty, A.xcd_rows, A.xcd_split);
+    A.ntiles = A.ntx * nty;
+    grid = lcplan::xcd_grid(A.ntiles, A.xcd_chunk) + A.pole_blocks;
+    return mode;
+}
+
 template <typename T, int ORDER>
 struct LdsLaunch {
     static const char *launch(const AdvectArgs<T> &, int, hipStream_t, int) { return nullptr; }
@@ -2606,106 +2635,67 @@ struct LdsLaunch<float, ORDER> {
         if (ORDER == 1 && A.pair_d >= 0) {
             // an ensemble, two MEMBERS per lane (advect_impl checked order1_two_seed_applies): the one-seed kernel's 8 x 32-seed workgroups
             A.tile_order = A.tile_order_two_seed;
-#define LC_LDS2P(KF, CY, MD, NAME)                                                                          \
-    {                                                                                                       \
-        hipLaunchKernelGGL((advect_lds2_kernel<KF, CY, MD>), dim3(grid, nmem(A)), dim3(BLOCK), 0, st, A);   \
-        return NAME;                                                                                        \
-    }
-            if (A.K == 4 && A.cyclic) LC_LDS2P(4, true, PATCH_PAIR, "advect_lds2_kernel<4, true, 3>")
-            if (A.K == 4) LC_LDS2P(4, false, PATCH_PAIR, "advect_lds2_kernel<4, false, 3>")
-            if (A.cyclic) LC_LDS2P(-1, true, PATCH_PAIR, "advect_lds2_kernel<-1, true, 3>")
-            LC_LDS2P(-1, false, PATCH_PAIR, "advect_lds2_kernel<-1, false, 3>")
-#undef LC_LDS2P
+            if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds2_kernel<4, true, PATCH_PAIR>, grid, st, A, "advect_lds2_kernel<4, true, 3>");
+            if (A.K == 4) return launch_kernel(advect_lds2_kernel<4, false, PATCH_PAIR>, grid, st, A, "advect_lds2_kernel<4, false, 3>");
+            if (A.cyclic) return launch_kernel(advect_lds2_kernel<-1, true, PATCH_PAIR>, grid, st, A, "advect_lds2_kernel<-1, true, 3>");
+            return launch_kernel(advect_lds2_kernel<-1, false, PATCH_PAIR>, grid, st, A, "advect_lds2_kernel<-1, false, 3>");
         }
         if (ORDER == 1 && order1_two_seed_applies(A, mode)) {
             // two seeds per lane; a workgroup covers 8 x 64 seeds (PATCH_TALL), 16 x 32 (PATCH_WIDE) or 32 x 16 (PATCH_LINES)
-            const int mode = (A.patch_mode >= 0 && A.patch_mode < PATCH_PAIR) ? A.patch_mode
-                                                                               : (A.traj_x && A.traj_line_ok && A.nx >= TILE_W * 4 ? PATCH_LINES : PATCH_TALL);
-            int nty = (A.ny + TILE_H * SPL - 1) / (TILE_H * SPL);
-            if (mode == PATCH_WIDE) {
-                A.ntx = (A.nx + TILE_W * SPL - 1) / (TILE_W * SPL);
-                nty = (A.ny + TILE_H - 1) / TILE_H;
-            } else if (mode == PATCH_LINES) {
-                A.ntx = (A.nx + TILE_W * 4 - 1) / (TILE_W * 4);
-                nty = (A.ny + 8 * SPL - 1) / (8 * SPL);
-            }
-            A.xcd_chunk = lcplan::xcd_chunk_tiles(A.ntx, nty, A.xcd_rows, A.xcd_split);
-            A.ntiles = A.ntx * nty;
+            int g2;
+            const int mode = two_seed_patch_grid(A, A.patch_mode < PATCH_PAIR, g2);  // (PATCH_PAIR is the ensemble's, above)
             A.tile_order = A.tile_order_two_seed;
-            const int g2 = xcd_grid(A.ntiles, A.xcd_chunk) + A.pole_blocks;
-#define LC_LDS2(KF, CY, MD, NAME)                                                                      \
-    {                                                                                                  \
-        hipLaunchKernelGGL((advect_lds2_kernel<KF, CY, MD>), dim3(g2, nmem(A)), dim3(BLOCK), 0, st, A);         \
-        return NAME;                                                                                   \
-    }
             if (mode == PATCH_LINES) {
-                if (A.K == 4 && A.cyclic) LC_LDS2(4, true, PATCH_LINES, "advect_lds2_kernel<4, true, 2>")
-                if (A.K == 4) LC_LDS2(4, false, PATCH_LINES, "advect_lds2_kernel<4, false, 2>")
-                if (A.cyclic) LC_LDS2(-1, true, PATCH_LINES, "advect_lds2_kernel<-1, true, 2>")
-                LC_LDS2(-1, false, PATCH_LINES, "advect_lds2_kernel<-1, false, 2>")
+                if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds2_kernel<4, true, PATCH_LINES>, g2, st, A, "advect_lds2_kernel<4, true, 2>");
+                if (A.K == 4) return launch_kernel(advect_lds2_kernel<4, false, PATCH_LINES>, g2, st, A, "advect_lds2_kernel<4, false, 2>");
+                if (A.cyclic) return launch_kernel(advect_lds2_kernel<-1, true, PATCH_LINES>, g2, st, A, "advect_lds2_kernel<-1, true, 2>");
+                return launch_kernel(advect_lds2_kernel<-1, false, PATCH_LINES>, g2, st, A, "advect_lds2_kernel<-1, false, 2>");
             }
             if (mode == PATCH_WIDE) {
-                if (A.K == 4 && A.cyclic) LC_LDS2(4, true, PATCH_WIDE, "advect_lds2_kernel<4, true, 1>")
-                if (A.K == 4) LC_LDS2(4, false, PATCH_WIDE, "advect_lds2_kernel<4, false, 1>")
-                if (A.cyclic) LC_LDS2(-1, true, PATCH_WIDE, "advect_lds2_kernel<-1, true, 1>")
-                LC_LDS2(-1, false, PATCH_WIDE, "advect_lds2_kernel<-1, false, 1>")
+                if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds2_kernel<4, true, PATCH_WIDE>, g2, st, A, "advect_lds2_kernel<4, true, 1>");
+                if (A.K == 4) return launch_kernel(advect_lds2_kernel<4, false, PATCH_WIDE>, g2, st, A, "advect_lds2_kernel<4, false, 1>");
+                if (A.cyclic) return launch_kernel(advect_lds2_kernel<-1, true, PATCH_WIDE>, g2, st, A, "advect_lds2_kernel<-1, true, 1>");
+                return launch_kernel(advect_lds2_kernel<-1, false, PATCH_WIDE>, g2, st, A, "advect_lds2_kernel<-1, false, 1>");
             }
             // (SETTLS_order = 0, the library default, compiled as such: no tile, no iteration blocks -- C3 1.73 -> 1.69 ms against the run-time-K instance)
-            if (A.K == 0 && A.cyclic) LC_LDS2(0, true, PATCH_TALL, "advect_lds2_kernel<0, true, 0>")
-            if (A.K == 0) LC_LDS2(0, false, PATCH_TALL, "advect_lds2_kernel<0, false, 0>")   // (cyclic_xboundary=False is the reference's default too)
+            if (A.K == 0 && A.cyclic) return launch_kernel(advect_lds2_kernel<0, true, PATCH_TALL>, g2, st, A, "advect_lds2_kernel<0, true, 0>");
+            if (A.K == 0) return launch_kernel(advect_lds2_kernel<0, false, PATCH_TALL>, g2, st, A, "advect_lds2_kernel<0, false, 0>");   // (cyclic_xboundary=False is the reference's default too)
             // (SETTLS_order 1, 2, 3 compiled as such too: the iteration loop unrolls and the kernel keeps the K = 4 instance's 59 registers
             // instead of the run-time-K instance's 71 -- C3 at K = 1: 3.28 -> 2.91 ms, K = 2: 4.26 -> 3.93)
-            if (A.K == 1 && A.cyclic) LC_LDS2(1, true, PATCH_TALL, "advect_lds2_kernel<1, true, 0>")
-            if (A.K == 2 && A.cyclic) LC_LDS2(2, true, PATCH_TALL, "advect_lds2_kernel<2, true, 0>")
-            if (A.K == 3 && A.cyclic) LC_LDS2(3, true, PATCH_TALL, "advect_lds2_kernel<3, true, 0>")
-            if (A.K == 4 && A.cyclic) LC_LDS2(4, true, PATCH_TALL, "advect_lds2_kernel<4, true, 0>")
-            if (A.K == 4) LC_LDS2(4, false, PATCH_TALL, "advect_lds2_kernel<4, false, 0>")
-            if (A.cyclic) LC_LDS2(-1, true, PATCH_TALL, "advect_lds2_kernel<-1, true, 0>")
-            LC_LDS2(-1, false, PATCH_TALL, "advect_lds2_kernel<-1, false, 0>")
-#undef LC_LDS2
+            if (A.K == 1 && A.cyclic) return launch_kernel(advect_lds2_kernel<1, true, PATCH_TALL>, g2, st, A, "advect_lds2_kernel<1, true, 0>");
+            if (A.K == 2 && A.cyclic) return launch_kernel(advect_lds2_kernel<2, true, PATCH_TALL>, g2, st, A, "advect_lds2_kernel<2, true, 0>");
+            if (A.K == 3 && A.cyclic) return launch_kernel(advect_lds2_kernel<3, true, PATCH_TALL>, g2, st, A, "advect_lds2_kernel<3, true, 0>");
+            if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds2_kernel<4, true, PATCH_TALL>, g2, st, A, "advect_lds2_kernel<4, true, 0>");
+            if (A.K == 4) return launch_kernel(advect_lds2_kernel<4, false, PATCH_TALL>, g2, st, A, "advect_lds2_kernel<4, false, 0>");
+            if (A.cyclic) return launch_kernel(advect_lds2_kernel<-1, true, PATCH_TALL>, g2, st, A, "advect_lds2_kernel<-1, true, 0>");
+            return launch_kernel(advect_lds2_kernel<-1, false, PATCH_TALL>, g2, st, A, "advect_lds2_kernel<-1, false, 0>");
         }
         // (order 3 also with SETTLS_order = 0, the reference's default: the Euler sample alone already gains from its LDS tile)
         if (ORDER == 3 && two_seed && (A.ext || A.K == 0) && A.nx_f + LC_PAD >= TileGeom<3>::COLS && A.ny_f + LC_PAD >= TileGeom<3>::ROWS) {
             // order 3, two seeds per lane: the same patches and patch modes as above
-            const int mode = A.patch_mode >= 0 ? A.patch_mode : (A.traj_x && A.traj_line_ok && A.nx >= TILE_W * 4 ? PATCH_LINES : PATCH_TALL);
-            int nty = (A.ny + TILE_H * SPL - 1) / (TILE_H * SPL);
-            if (mode == PATCH_WIDE) {
-                A.ntx = (A.nx + TILE_W * SPL - 1) / (TILE_W * SPL);
-                nty = (A.ny + TILE_H - 1) / TILE_H;
-            } else if (mode == PATCH_LINES) {
-                A.ntx = (A.nx + TILE_W * 4 - 1) / (TILE_W * 4);
-                nty = (A.ny + 8 * SPL - 1) / (8 * SPL);
-            }
-            A.xcd_chunk = lcplan::xcd_chunk_tiles(A.ntx, nty, A.xcd_rows, A.xcd_split);
-            A.ntiles = A.ntx * nty;
-            const int g2 = xcd_grid(A.ntiles, A.xcd_chunk) + A.pole_blocks;
-#define LC_LDS2O3(KF, CY, MD, NAME)                                                                       \
-    {                                                                                                     \
-        hipLaunchKernelGGL((advect_lds2_o3_kernel<KF, CY, MD>), dim3(g2, nmem(A)), dim3(BLOCK), 0, st, A);         \
-        return NAME;                                                                                      \
-    }
+            int g2;
+            const int mode = two_seed_patch_grid(A, true, g2);
             if (mode == PATCH_LINES) {
-                if (A.K == 4 && A.cyclic) LC_LDS2O3(4, true, PATCH_LINES, "advect_lds2_o3_kernel<4, true, 2>")
-                if (A.K == 4) LC_LDS2O3(4, false, PATCH_LINES, "advect_lds2_o3_kernel<4, false, 2>")
-                if (A.cyclic) LC_LDS2O3(-1, true, PATCH_LINES, "advect_lds2_o3_kernel<-1, true, 2>")
-                LC_LDS2O3(-1, false, PATCH_LINES, "advect_lds2_o3_kernel<-1, false, 2>")
+                if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds2_o3_kernel<4, true, PATCH_LINES>, g2, st, A, "advect_lds2_o3_kernel<4, true, 2>");
+                if (A.K == 4) return launch_kernel(advect_lds2_o3_kernel<4, false, PATCH_LINES>, g2, st, A, "advect_lds2_o3_kernel<4, false, 2>");
+                if (A.cyclic) return launch_kernel(advect_lds2_o3_kernel<-1, true, PATCH_LINES>, g2, st, A, "advect_lds2_o3_kernel<-1, true, 2>");
+                return launch_kernel(advect_lds2_o3_kernel<-1, false, PATCH_LINES>, g2, st, A, "advect_lds2_o3_kernel<-1, false, 2>");
             }
             if (mode == PATCH_WIDE) {
-                if (A.K == 4 && A.cyclic) LC_LDS2O3(4, true, PATCH_WIDE, "advect_lds2_o3_kernel<4, true, 1>")
-                if (A.K == 4) LC_LDS2O3(4, false, PATCH_WIDE, "advect_lds2_o3_kernel<4, false, 1>")
-                if (A.cyclic) LC_LDS2O3(-1, true, PATCH_WIDE, "advect_lds2_o3_kernel<-1, true, 1>")
-                LC_LDS2O3(-1, false, PATCH_WIDE, "advect_lds2_o3_kernel<-1, false, 1>")
+                if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds2_o3_kernel<4, true, PATCH_WIDE>, g2, st, A, "advect_lds2_o3_kernel<4, true, 1>");
+                if (A.K == 4) return launch_kernel(advect_lds2_o3_kernel<4, false, PATCH_WIDE>, g2, st, A, "advect_lds2_o3_kernel<4, false, 1>");
+                if (A.cyclic) return launch_kernel(advect_lds2_o3_kernel<-1, true, PATCH_WIDE>, g2, st, A, "advect_lds2_o3_kernel<-1, true, 1>");
+                return launch_kernel(advect_lds2_o3_kernel<-1, false, PATCH_WIDE>, g2, st, A, "advect_lds2_o3_kernel<-1, false, 1>");
             }
             // (interp_order = 3 with SETTLS_order = 0 are the reference's DEFAULT arguments: compiled as such, 85 registers instead of
             // 94 + scratch and no iteration blocks -- C3 3.26 -> 3.10 ms against the run-time-K instance)
-            if (A.K == 0 && A.cyclic) LC_LDS2O3(0, true, PATCH_TALL, "advect_lds2_o3_kernel<0, true, 0>")
-            if (A.K == 0) LC_LDS2O3(0, false, PATCH_TALL, "advect_lds2_o3_kernel<0, false, 0>")   // (... with cyclic_xboundary=False, its default)
+            if (A.K == 0 && A.cyclic) return launch_kernel(advect_lds2_o3_kernel<0, true, PATCH_TALL>, g2, st, A, "advect_lds2_o3_kernel<0, true, 0>");
+            if (A.K == 0) return launch_kernel(advect_lds2_o3_kernel<0, false, PATCH_TALL>, g2, st, A, "advect_lds2_o3_kernel<0, false, 0>");   // (... with cyclic_xboundary=False, its default)
             // (order-3 instances for K = 1, 2: measured, < 1 %)
-            if (A.K == 4 && A.cyclic) LC_LDS2O3(4, true, PATCH_TALL, "advect_lds2_o3_kernel<4, true, 0>")
-            if (A.K == 4) LC_LDS2O3(4, false, PATCH_TALL, "advect_lds2_o3_kernel<4, false, 0>")
-            if (A.cyclic) LC_LDS2O3(-1, true, PATCH_TALL, "advect_lds2_o3_kernel<-1, true, 0>")
-            LC_LDS2O3(-1, false, PATCH_TALL, "advect_lds2_o3_kernel<-1, false, 0>")
-#undef LC_LDS2O3
+            if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds2_o3_kernel<4, true, PATCH_TALL>, g2, st, A, "advect_lds2_o3_kernel<4, true, 0>");
+            if (A.K == 4) return launch_kernel(advect_lds2_o3_kernel<4, false, PATCH_TALL>, g2, st, A, "advect_lds2_o3_kernel<4, false, 0>");
+            if (A.cyclic) return launch_kernel(advect_lds2_o3_kernel<-1, true, PATCH_TALL>, g2, st, A, "advect_lds2_o3_kernel<-1, true, 0>");
+            return launch_kernel(advect_lds2_o3_kernel<-1, false, PATCH_TALL>, g2, st, A, "advect_lds2_o3_kernel<-1, false, 0>");
         }
         // the fixed-size tile must fit inside one padded time level
         if ((!A.ext && !(ORDER == 3 && A.K == 0)) || A.nx_f + LC_PAD < TileGeom<ORDER>::COLS || A.ny_f + LC_PAD < TileGeom<ORDER>::ROWS) return nullptr;
@@ -2722,37 +2712,25 @@ struct LdsLaunch<float, ORDER> {
             const int nty = (A.ny + 7) / 8;
             A.ntiles = A.ntx * nty;
             A.xcd_chunk = lcplan::xcd_chunk_tiles(A.ntx, nty, A.xcd_rows, A.xcd_split);
-            g1 = xcd_grid(A.ntiles, A.xcd_chunk) + A.pole_blocks;
+            g1 = lcplan::xcd_grid(A.ntiles, A.xcd_chunk) + A.pole_blocks;
         }
-#define LC_LDS1(KF, CY, LN, NAME)                                                                                       \
-    {                                                                                                                   \
-        hipLaunchKernelGGL((advect_lds_kernel<ORDER, KF, CY, LN>), dim3(g1, nmem(A)), dim3(BLOCK), 0, st, A);           \
-        return NAME;                                                                                                    \
-    }
         // K = 4 is the setting the reference's example and drivers use
         if (lines) {
-            if (A.K == 4 && A.cyclic) LC_LDS1(4, true, true, ORDER == 3 ? "advect_lds_kernel<3, 4, true, lines>" : "advect_lds_kernel<1, 4, true, lines>")
-            if (A.K == 4) LC_LDS1(4, false, true, ORDER == 3 ? "advect_lds_kernel<3, 4, false, lines>" : "advect_lds_kernel<1, 4, false, lines>")
-            if (A.cyclic) LC_LDS1(-1, true, true, ORDER == 3 ? "advect_lds_kernel<3, -1, true, lines>" : "advect_lds_kernel<1, -1, true, lines>")
-            LC_LDS1(-1, false, true, ORDER == 3 ? "advect_lds_kernel<3, -1, false, lines>" : "advect_lds_kernel<1, -1, false, lines>")
+            if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds_kernel<ORDER, 4, true, true>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, 4, true, lines>" : "advect_lds_kernel<1, 4, true, lines>");
+            if (A.K == 4) return launch_kernel(advect_lds_kernel<ORDER, 4, false, true>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, 4, false, lines>" : "advect_lds_kernel<1, 4, false, lines>");
+            if (A.cyclic) return launch_kernel(advect_lds_kernel<ORDER, -1, true, true>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, -1, true, lines>" : "advect_lds_kernel<1, -1, true, lines>");
+            return launch_kernel(advect_lds_kernel<ORDER, -1, false, true>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, -1, false, lines>" : "advect_lds_kernel<1, -1, false, lines>");
         }
         if (A.verify) {  // lc_ctx_set_verify: the instances that audit each wave's tile and slot level by level
-#define LC_LDS1V(KF, CY, NAME)                                                                                           \
-    {                                                                                                                    \
-        hipLaunchKernelGGL((advect_lds_kernel<ORDER, KF, CY, false, true>), dim3(g1, nmem(A)), dim3(BLOCK), 0, st, A);   \
-        return NAME;                                                                                                     \
-    }
-            if (A.K == 4 && A.cyclic) LC_LDS1V(4, true, ORDER == 3 ? "advect_lds_kernel<3, 4, true, verify>" : "advect_lds_kernel<1, 4, true, verify>")
-            if (A.K == 4) LC_LDS1V(4, false, ORDER == 3 ? "advect_lds_kernel<3, 4, false, verify>" : "advect_lds_kernel<1, 4, false, verify>")
-            if (A.cyclic) LC_LDS1V(-1, true, ORDER == 3 ? "advect_lds_kernel<3, -1, true, verify>" : "advect_lds_kernel<1, -1, true, verify>")
-            LC_LDS1V(-1, false, ORDER == 3 ? "advect_lds_kernel<3, -1, false, verify>" : "advect_lds_kernel<1, -1, false, verify>")
-#undef LC_LDS1V
+            if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds_kernel<ORDER, 4, true, false, true>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, 4, true, verify>" : "advect_lds_kernel<1, 4, true, verify>");
+            if (A.K == 4) return launch_kernel(advect_lds_kernel<ORDER, 4, false, false, true>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, 4, false, verify>" : "advect_lds_kernel<1, 4, false, verify>");
+            if (A.cyclic) return launch_kernel(advect_lds_kernel<ORDER, -1, true, false, true>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, -1, true, verify>" : "advect_lds_kernel<1, -1, true, verify>");
+            return launch_kernel(advect_lds_kernel<ORDER, -1, false, false, true>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, -1, false, verify>" : "advect_lds_kernel<1, -1, false, verify>");
         }
-        if (A.K == 4 && A.cyclic) LC_LDS1(4, true, false, ORDER == 3 ? "advect_lds_kernel<3, 4, true>" : "advect_lds_kernel<1, 4, true>")
-        if (A.K == 4) LC_LDS1(4, false, false, ORDER == 3 ? "advect_lds_kernel<3, 4, false>" : "advect_lds_kernel<1, 4, false>")
-        if (A.cyclic) LC_LDS1(-1, true, false, ORDER == 3 ? "advect_lds_kernel<3, -1, true>" : "advect_lds_kernel<1, -1, true>")
-        LC_LDS1(-1, false, false, ORDER == 3 ? "advect_lds_kernel<3, -1, false>" : "advect_lds_kernel<1, -1, false>")
-#undef LC_LDS1
+        if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds_kernel<ORDER, 4, true, false>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, 4, true>" : "advect_lds_kernel<1, 4, true>");
+        if (A.K == 4) return launch_kernel(advect_lds_kernel<ORDER, 4, false, false>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, 4, false>" : "advect_lds_kernel<1, 4, false>");
+        if (A.cyclic) return launch_kernel(advect_lds_kernel<ORDER, -1, true, false>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, -1, true>" : "advect_lds_kernel<1, -1, true>");
+        return launch_kernel(advect_lds_kernel<ORDER, -1, false, false>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, -1, false>" : "advect_lds_kernel<1, -1, false>");
     }
 };
 
@@ -3734,8 +3712,6 @@ struct InteriorPath<float, ORDER, FUSED, SRC_IMAGES> {
     }
 };
 
-// double, order 1 sits at 69 VGPRs (7 waves per SIMD); asking for 8 costs nothing measurable per wave and
-// lets BASELINE config 2 (1024^2 seeds = 16 workgroups per CU) run in two full rounds instead of 7 + 7 + 2.
 template <typename T, int ORDER, bool FUSED, int SRC = SRC_IMAGES>
 __device__ __forceinline__ void advect_kernel_body(const AdvectArgs<T> &A0) {
     const AdvectArgs<T> A = for_member(A0);
@@ -3797,78 +3773,50 @@ struct Lds64Launch<double> {
             const int nty = (A.ny + W64_SIDE - 1) / W64_SIDE;
             B.ntiles = B.ntx * nty;
             B.xcd_chunk = lcplan::xcd_chunk_tiles(B.ntx, nty, A.xcd_rows, A.xcd_split);
-            const int gw = xcd_grid(B.ntiles, B.xcd_chunk) + B.pole_blocks;
-#define LC_WG64(KF, CY, SR, NAME)                                                                                   \
-    {                                                                                                               \
-        hipLaunchKernelGGL((advect_wg64_kernel<KF, CY, SR>), dim3(gw, nmem(B)), dim3(BLOCK), 0, st, B);             \
-        return NAME;                                                                                                \
-    }
+            const int gw = lcplan::xcd_grid(B.ntiles, B.xcd_chunk) + B.pole_blocks;
             const int sr = A.ext_raw ? 2 : (A.u_raw ? 1 : 0);
-            if (A.K == 4 && A.cyclic && sr == 2) LC_WG64(4, true, 2, "advect_wg64_kernel<4, true, 2>")
-            if (A.K == 4 && A.cyclic && sr == 1) LC_WG64(4, true, 1, "advect_wg64_kernel<4, true, 1>")
-            if (A.K == 4 && A.cyclic) LC_WG64(4, true, 0, "advect_wg64_kernel<4, true, 0>")
-            if (A.cyclic && sr == 2) LC_WG64(-1, true, 2, "advect_wg64_kernel<-1, true, 2>")
-            if (A.cyclic && sr == 1) LC_WG64(-1, true, 1, "advect_wg64_kernel<-1, true, 1>")
-            if (A.cyclic) LC_WG64(-1, true, 0, "advect_wg64_kernel<-1, true, 0>")
-            if (sr == 2) LC_WG64(-1, false, 2, "advect_wg64_kernel<-1, false, 2>")
-            if (sr == 1) LC_WG64(-1, false, 1, "advect_wg64_kernel<-1, false, 1>")
-            LC_WG64(-1, false, 0, "advect_wg64_kernel<-1, false, 0>")
-#undef LC_WG64
+            if (A.K == 4 && A.cyclic && sr == 2) return launch_kernel(advect_wg64_kernel<4, true, 2>, gw, st, B, "advect_wg64_kernel<4, true, 2>");
+            if (A.K == 4 && A.cyclic && sr == 1) return launch_kernel(advect_wg64_kernel<4, true, 1>, gw, st, B, "advect_wg64_kernel<4, true, 1>");
+            if (A.K == 4 && A.cyclic) return launch_kernel(advect_wg64_kernel<4, true, 0>, gw, st, B, "advect_wg64_kernel<4, true, 0>");
+            if (A.cyclic && sr == 2) return launch_kernel(advect_wg64_kernel<-1, true, 2>, gw, st, B, "advect_wg64_kernel<-1, true, 2>");
+            if (A.cyclic && sr == 1) return launch_kernel(advect_wg64_kernel<-1, true, 1>, gw, st, B, "advect_wg64_kernel<-1, true, 1>");
+            if (A.cyclic) return launch_kernel(advect_wg64_kernel<-1, true, 0>, gw, st, B, "advect_wg64_kernel<-1, true, 0>");
+            if (sr == 2) return launch_kernel(advect_wg64_kernel<-1, false, 2>, gw, st, B, "advect_wg64_kernel<-1, false, 2>");
+            if (sr == 1) return launch_kernel(advect_wg64_kernel<-1, false, 1>, gw, st, B, "advect_wg64_kernel<-1, false, 1>");
+            return launch_kernel(advect_wg64_kernel<-1, false, 0>, gw, st, B, "advect_wg64_kernel<-1, false, 0>");
         }
         // (names as a profiler prints them; the last argument: 0 = lin + ext images, 1 = raw planes for the Euler sample + ext
         // image, 2 = raw planes for both, the fused-level value formed node by node: lc_advect_ex)
-#define LC_LDS64(KF, CY, SR, NAME)                                                                                  \
-    {                                                                                                               \
-        hipLaunchKernelGGL((advect_lds64_kernel<KF, CY, SR>), dim3(grid, nmem(A)), dim3(BLOCK), 0, st, A);          \
-        return NAME;                                                                                                \
-    }
         if (A.ext_raw) {
-            if (A.K == 4 && A.cyclic) LC_LDS64(4, true, 2, "advect_lds64_kernel<4, true, 2>")
-            if (A.K == 4) LC_LDS64(4, false, 2, "advect_lds64_kernel<4, false, 2>")
-            if (A.cyclic) LC_LDS64(-1, true, 2, "advect_lds64_kernel<-1, true, 2>")
-            LC_LDS64(-1, false, 2, "advect_lds64_kernel<-1, false, 2>")
+            if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds64_kernel<4, true, 2>, grid, st, A, "advect_lds64_kernel<4, true, 2>");
+            if (A.K == 4) return launch_kernel(advect_lds64_kernel<4, false, 2>, grid, st, A, "advect_lds64_kernel<4, false, 2>");
+            if (A.cyclic) return launch_kernel(advect_lds64_kernel<-1, true, 2>, grid, st, A, "advect_lds64_kernel<-1, true, 2>");
+            return launch_kernel(advect_lds64_kernel<-1, false, 2>, grid, st, A, "advect_lds64_kernel<-1, false, 2>");
         }
         if (A.u_raw) {
-            if (A.K == 4 && A.cyclic) LC_LDS64(4, true, 1, "advect_lds64_kernel<4, true, 1>")
-            if (A.K == 4) LC_LDS64(4, false, 1, "advect_lds64_kernel<4, false, 1>")
-            if (A.cyclic) LC_LDS64(-1, true, 1, "advect_lds64_kernel<-1, true, 1>")
-            LC_LDS64(-1, false, 1, "advect_lds64_kernel<-1, false, 1>")
+            if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds64_kernel<4, true, 1>, grid, st, A, "advect_lds64_kernel<4, true, 1>");
+            if (A.K == 4) return launch_kernel(advect_lds64_kernel<4, false, 1>, grid, st, A, "advect_lds64_kernel<4, false, 1>");
+            if (A.cyclic) return launch_kernel(advect_lds64_kernel<-1, true, 1>, grid, st, A, "advect_lds64_kernel<-1, true, 1>");
+            return launch_kernel(advect_lds64_kernel<-1, false, 1>, grid, st, A, "advect_lds64_kernel<-1, false, 1>");
         }
-        if (A.K == 4 && A.cyclic) LC_LDS64(4, true, 0, "advect_lds64_kernel<4, true, 0>")
-        if (A.K == 4) LC_LDS64(4, false, 0, "advect_lds64_kernel<4, false, 0>")
-        if (A.cyclic) LC_LDS64(-1, true, 0, "advect_lds64_kernel<-1, true, 0>")
-        LC_LDS64(-1, false, 0, "advect_lds64_kernel<-1, false, 0>")
-#undef LC_LDS64
+        if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds64_kernel<4, true, 0>, grid, st, A, "advect_lds64_kernel<4, true, 0>");
+        if (A.K == 4) return launch_kernel(advect_lds64_kernel<4, false, 0>, grid, st, A, "advect_lds64_kernel<4, false, 0>");
+        if (A.cyclic) return launch_kernel(advect_lds64_kernel<-1, true, 0>, grid, st, A, "advect_lds64_kernel<-1, true, 0>");
+        return launch_kernel(advect_lds64_kernel<-1, false, 0>, grid, st, A, "advect_lds64_kernel<-1, false, 0>");
     }
     // order 3 (SETTLS_order = 0 included: the Euler sample has its own tile)
     static const char *launch_o3(const AdvectArgs<double> &A, int grid, hipStream_t st, int mode) {
         if (mode == 0 || A.wind_f32 || !(A.ext || A.ext_cub) || A.nx_f + LC_PAD < T64O3 || A.ny_f + LC_PAD < T64O3) return nullptr;
         if (A.ext_cub) {  // no ext image: the iteration tile is formed from img[t], img[t+1] while it is staged
-            if (A.K == 4 && A.cyclic) {
-                hipLaunchKernelGGL((advect_lds64_o3_kernel<4, true, true>), dim3(grid, nmem(A)), dim3(BLOCK), 0, st, A);
-                return "advect_lds64_o3_kernel<4, true, cub>";
-            } else if (A.K == 4) {
-                hipLaunchKernelGGL((advect_lds64_o3_kernel<4, false, true>), dim3(grid, nmem(A)), dim3(BLOCK), 0, st, A);
-                return "advect_lds64_o3_kernel<4, false, cub>";
-            } else if (A.cyclic) {
-                hipLaunchKernelGGL((advect_lds64_o3_kernel<-1, true, true>), dim3(grid, nmem(A)), dim3(BLOCK), 0, st, A);
-                return "advect_lds64_o3_kernel<-1, true, cub>";
-            }
-            hipLaunchKernelGGL((advect_lds64_o3_kernel<-1, false, true>), dim3(grid, nmem(A)), dim3(BLOCK), 0, st, A);
-            return "advect_lds64_o3_kernel<-1, false, cub>";
+            if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds64_o3_kernel<4, true, true>, grid, st, A, "advect_lds64_o3_kernel<4, true, cub>");
+            if (A.K == 4) return launch_kernel(advect_lds64_o3_kernel<4, false, true>, grid, st, A, "advect_lds64_o3_kernel<4, false, cub>");
+            if (A.cyclic) return launch_kernel(advect_lds64_o3_kernel<-1, true, true>, grid, st, A, "advect_lds64_o3_kernel<-1, true, cub>");
+            return launch_kernel(advect_lds64_o3_kernel<-1, false, true>, grid, st, A, "advect_lds64_o3_kernel<-1, false, cub>");
         }
-        if (A.K == 4 && A.cyclic) {
-            hipLaunchKernelGGL((advect_lds64_o3_kernel<4, true>), dim3(grid, nmem(A)), dim3(BLOCK), 0, st, A);
-            return "advect_lds64_o3_kernel<4, true>";
-        } else if (A.K == 4) {
-            hipLaunchKernelGGL((advect_lds64_o3_kernel<4, false>), dim3(grid, nmem(A)), dim3(BLOCK), 0, st, A);
-            return "advect_lds64_o3_kernel<4, false>";
-        } else if (A.cyclic) {
-            hipLaunchKernelGGL((advect_lds64_o3_kernel<-1, true>), dim3(grid, nmem(A)), dim3(BLOCK), 0, st, A);
-            return "advect_lds64_o3_kernel<-1, true>";
-        }
-        hipLaunchKernelGGL((advect_lds64_o3_kernel<-1, false>), dim3(grid, nmem(A)), dim3(BLOCK), 0, st, A);
-        return "advect_lds64_o3_kernel<-1, false>";
+        if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds64_o3_kernel<4, true>, grid, st, A, "advect_lds64_o3_kernel<4, true>");
+        if (A.K == 4) return launch_kernel(advect_lds64_o3_kernel<4, false>, grid, st, A, "advect_lds64_o3_kernel<4, false>");
+        if (A.cyclic) return launch_kernel(advect_lds64_o3_kernel<-1, true>, grid, st, A, "advect_lds64_o3_kernel<-1, true>");
+        return launch_kernel(advect_lds64_o3_kernel<-1, false>, grid, st, A, "advect_lds64_o3_kernel<-1, false>");
     }
 };
 
@@ -3876,27 +3824,23 @@ template <typename T, int ORDER>
 struct DirectLaunch {
     static const char *launch(const AdvectArgs<T> &A, int grid, hipStream_t st) {
         if constexpr (ORDER == 1 && sizeof(T) == 8) {
-            if (A.u_raw) {  // exact order with the raw planes as the order-1 source (lc_advect_ex)
-                hipLaunchKernelGGL((advect_kernel<T, 1, false, SRC_RAW_EULER>), dim3(grid, nmem(A)), dim3(BLOCK), 0, st, A);
-                return "advect_kernel<double, 1, false, 1>";
-            }
+            // exact order with the raw planes as the order-1 source (lc_advect_ex)
+            if (A.u_raw) return launch_kernel(advect_kernel<T, 1, false, SRC_RAW_EULER>, grid, st, A, "advect_kernel<double, 1, false, 1>");
         }
-        hipLaunchKernelGGL((advect_kernel<T, ORDER>), dim3(grid, nmem(A)), dim3(BLOCK), 0, st, A);
         // (as a profiler prints them: all four template arguments)
-        return ORDER == 1 ? "advect_kernel<double, 1, false, 0>" : ORDER == 2 ? "advect_kernel<double, 2, false, 0>"
-             : ORDER == 3 ? "advect_kernel<double, 3, false, 0>" : ORDER == 4 ? "advect_kernel<double, 4, false, 0>"
-                                                                              : "advect_kernel<double, 5, false, 0>";
+        return launch_kernel(advect_kernel<T, ORDER>, grid, st, A,
+                             ORDER == 1 ? "advect_kernel<double, 1, false, 0>" : ORDER == 2 ? "advect_kernel<double, 2, false, 0>"
+                           : ORDER == 3 ? "advect_kernel<double, 3, false, 0>" : ORDER == 4 ? "advect_kernel<double, 4, false, 0>"
+                                                                                            : "advect_kernel<double, 5, false, 0>");
     }
 };
 template <int ORDER>
 struct DirectLaunch<float, ORDER> {
     static const char *launch(const AdvectArgs<float> &A, int grid, hipStream_t st) {
-        if (ORDER == 1)
-            hipLaunchKernelGGL((advect_kernel_f32<ORDER>), dim3(grid, nmem(A)), dim3(BLOCK), 0, st, A);
-        else
-            hipLaunchKernelGGL((advect_kernel_f32_wide<ORDER>), dim3(grid, nmem(A)), dim3(BLOCK), 0, st, A);
-        return ORDER == 1 ? "advect_kernel_f32<1>" : ORDER == 2 ? "advect_kernel_f32_wide<2>" : ORDER == 3 ? "advect_kernel_f32_wide<3>"
-             : ORDER == 4 ? "advect_kernel_f32_wide<4>" : "advect_kernel_f32_wide<5>";
+        if (ORDER == 1) return launch_kernel(advect_kernel_f32<ORDER>, grid, st, A, "advect_kernel_f32<1>");
+        return launch_kernel(advect_kernel_f32_wide<ORDER>, grid, st, A,
+                             ORDER == 2 ? "advect_kernel_f32_wide<2>" : ORDER == 3 ? "advect_kernel_f32_wide<3>"
+                           : ORDER == 4 ? "advect_kernel_f32_wide<4>" : "advect_kernel_f32_wide<5>");
     }
 };
 
@@ -4120,6 +4064,28 @@ __global__ void outer_store_batch_kernel(const AdvectArgs<T> A, const OuterArgs<
     }
 }
 
+// The sub-step kernels of an interpolation order (scipy's 1 .. 5: lc_advect_ex checked)
+template <typename T>
+static auto outer_substep_for(int order) {
+    switch (order) {
+        case 2: return outer_substep_kernel<T, 2>;
+        case 3: return outer_substep_kernel<T, 3>;
+        case 4: return outer_substep_kernel<T, 4>;
+        case 5: return outer_substep_kernel<T, 5>;
+        default: return outer_substep_kernel<T, 1>;
+    }
+}
+template <typename T>
+static auto outer_substep_batch_for(int order) {
+    switch (order) {
+        case 2: return outer_substep_batch_kernel<T, 2>;
+        case 3: return outer_substep_batch_kernel<T, 3>;
+        case 4: return outer_substep_batch_kernel<T, 4>;
+        case 5: return outer_substep_batch_kernel<T, 5>;
+        default: return outer_substep_batch_kernel<T, 1>;
+    }
+}
+
 template <typename T>
 int advect_outer_impl(lc_ctx *ctx, AdvectArgs<T> A, int s_begin = 0, const T *x0 = nullptr, const T *y0 = nullptr) {
     // s_begin, x0, y0: restart at step s_begin from these positions (the state the fused kernel saved before the chunk
@@ -4161,15 +4127,7 @@ int advect_outer_impl(lc_ctx *ctx, AdvectArgs<T> A, int s_begin = 0, const T *x0
             O.p_clo = prev + A.ny;
             O.p_rhi = O.p_clo + A.nx;
             O.p_chi = O.p_rhi + A.ny;
-#define LC_OUTER(ORD) hipLaunchKernelGGL((outer_substep_kernel<T, ORD>), dim3(blocks), dim3(256), 0, st, A, O, A.t0 + s, k > 0)
-            switch (A.order) {
-                case 2: LC_OUTER(2); break;
-                case 3: LC_OUTER(3); break;
-                case 4: LC_OUTER(4); break;
-                case 5: LC_OUTER(5); break;
-                default: LC_OUTER(1); break;
-            }
-#undef LC_OUTER
+            launch_kernel(outer_substep_for<T>(A.order), blocks, st, A, "outer_substep_kernel", O, A.t0 + s, k > 0);  // (one member: grid.y = 1)
             if (ctx->flag_reduce && ctx->flag_reduce(ctx->flag_reduce_user, O.clo, (size_t)A.nx) != 0) goto reduce_failed;
             hipLaunchKernelGGL((outer_hi_kernel<T>), dim3(blocks), dim3(256), 0, st, A, O);
             if (ctx->flag_reduce && ctx->flag_reduce(ctx->flag_reduce_user, O.chi, (size_t)A.nx) != 0) goto reduce_failed;
@@ -4250,15 +4208,7 @@ int advect_outer_series_impl(lc_ctx *ctx, AdvectArgs<T> A, const std::vector<int
             unsigned *cur = flags + (size_t)(sub & 1) * fbuf, *prev = flags + (size_t)((sub & 1) ^ 1) * fbuf;
             (void)hipMemsetAsync(cur, 0, fbuf * sizeof(unsigned), st);
             point(cur, prev);
-#define LC_OUTER_B(ORD) hipLaunchKernelGGL((outer_substep_batch_kernel<T, ORD>), grid, dim3(256), 0, st, A, O, S, s, k > 0)
-            switch (A.order) {
-                case 2: LC_OUTER_B(2); break;
-                case 3: LC_OUTER_B(3); break;
-                case 4: LC_OUTER_B(4); break;
-                case 5: LC_OUTER_B(5); break;
-                default: LC_OUTER_B(1); break;
-            }
-#undef LC_OUTER_B
+            launch_kernel(outer_substep_batch_for<T>(A.order), blocks, st, A, "outer_substep_batch_kernel", O, S, s, k > 0);  // (grid.y = nm)
             hipLaunchKernelGGL((outer_hi_batch_kernel<T>), grid, dim3(256), 0, st, A, O, S, s);
         }
     }
@@ -4271,74 +4221,94 @@ int advect_outer_series_impl(lc_ctx *ctx, AdvectArgs<T> A, const std::vector<int
     return LC_OK;
 }
 
+// The images and raw planes of a call's field, as its kernels are to read them
+struct FieldSource {
+    const void *lin, *cub;      // lc_field_pack's order-1 image; the image of the call's order (read when that is not 1)
+    const void *u_raw, *v_raw;  // NULL, or the raw planes as the order-1 source (only where a kernel family reads them)
+};
+
+// The field geometry of a call, for the advect, sample and tracer launches alike: where the images and planes are, their
+// shape, the index transform (Q2) and the block of seed rows the pole rule (Q3) looks at.  G is lc_advect_args,
+// lc_tracer_args or SampleCall, which name these things alike.
+template <typename T, typename G>
+static void set_field_geometry(AdvectArgs<T> &A, const FieldSource &src, const G &g) {
+    A.lin = (const T *)src.lin;
+    A.img = (g.interp_order != 1) ? (const T *)src.cub : (const T *)src.lin;
+    A.u_raw = (const T *)src.u_raw;
+    A.v_raw = (const T *)src.v_raw;
+    A.raw_plane = (size_t)g.ny_f * g.nx_f;
+    A.level_elems = lc_level_elems(g.ny_f, g.nx_f);
+    A.pitch = g.nx_f + LC_PAD;
+    A.ny_f = g.ny_f;
+    A.nx_f = g.nx_f;
+    A.lat_min = (T)g.lat_min;
+    A.lon_min = (T)g.lon_min;
+    A.lat_span = (T)g.lat_max - (T)g.lat_min;
+    A.lon_span = (T)g.lon_max - (T)g.lon_min;
+    set_fast_transform(A);
+    A.ny = g.ny;
+    A.nx = g.nx;
+    A.row0 = g.row0;
+    A.ny_global = g.ny_global;
+    A.order = g.interp_order;
+}
+
+// What advect_ex_checked decides about a call beyond its lc_advect_args (resolve_advect_call)
+struct AdvectCall {
+    FieldSource src;
+    const void *ext;              // packed_ext
+    const void *lin32, *lin32_v;  // LC_F64_WIND_F32_LIN32: the float32 order-1 image (order 1), or the float32 raw planes u and v (order 3)
+    int wind_f32;                 // float64 arithmetic on a float32-valued wind: numpy's promotion rules (Q10)
+    bool series;                  // lc_advect_series: the outer clamp is decided per member
+    int dirs;                     // lc_advect_series_dirs: 2 = every window in both directions of time
+};
+
 template <typename T>
-int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, const void *packed_ext, const void *u_raw,
-                const void *v_raw, int nt, int ny_f, int nx_f,
-                double lat_min, double lat_max, double lon_min, double lon_max, const void *seed_lat, int ny,
-                const void *seed_lon, int nx, int row0, int ny_global, double timestep, int K, int order, int cyclic,
-                int t0, int nsteps, void *x_out, void *y_out, void *traj_x, void *traj_y, const void *x_start,
-                const void *y_start, int wind_f32 = 0, int n_members = 1, int t0_stride = 0, int fuse_levels_raw = 0,
-                const void *lin32 = nullptr, const void *lin32_v = nullptr, bool series = false, int dirs = 1) {
+int advect_impl(lc_ctx *ctx, const lc_advect_args &a, const AdvectCall &call) {
+    const int ny = a.ny, nx = a.nx, order = a.interp_order, K = a.settls_order, t0_stride = a.t0_stride;
+    const int n_members = a.n_members * call.dirs;  // planes of x_out / y_out
     AdvectArgs<T> A{};
-    A.member_dirs = dirs == 2;  // lc_advect_series_dirs: n_members = 2 x windows, plane 2w + d (see the level chunks below)
-    A.wind_f32 = wind_f32;
+    A.member_dirs = call.dirs == 2;  // lc_advect_series_dirs: n_members = 2 x windows, plane 2w + d (see the level chunks below)
+    A.wind_f32 = call.wind_f32;
     A.n_members = n_members;
     A.member_t0_stride = t0_stride;
     A.member_plane = (size_t)ny * nx;
-    A.x_start = (const T *)x_start;
-    A.y_start = (const T *)y_start;
+    A.x_start = (const T *)a.x_start;
+    A.y_start = (const T *)a.y_start;
     A.traj_skip0 = 0;
     A.pair_d = -1;
-    A.traj_pair_ok = (nx % 2 == 0) && ((size_t)traj_x % (2 * sizeof(T)) == 0) && ((size_t)traj_y % (2 * sizeof(T)) == 0);
-    A.out_pair_ok = (nx % 2 == 0) && ((size_t)x_out % (2 * sizeof(T)) == 0) && ((size_t)y_out % (2 * sizeof(T)) == 0);
-    A.traj_line_ok = (nx % 4 == 0) && ((size_t)traj_x % 16 == 0) && ((size_t)traj_y % 16 == 0) && sizeof(T) == 4;
+    A.traj_pair_ok = (nx % 2 == 0) && ((size_t)a.traj_x % (2 * sizeof(T)) == 0) && ((size_t)a.traj_y % (2 * sizeof(T)) == 0);
+    A.out_pair_ok = (nx % 2 == 0) && ((size_t)a.x_out % (2 * sizeof(T)) == 0) && ((size_t)a.y_out % (2 * sizeof(T)) == 0);
+    A.traj_line_ok = (nx % 4 == 0) && ((size_t)a.traj_x % 16 == 0) && ((size_t)a.traj_y % 16 == 0) && sizeof(T) == 4;
     A.patch_mode = ctx->patch_mode;
     A.xcd_rows = ctx->xcd_chunk_rows;
     A.xcd_split = ctx->xcd_split;
-    A.lin = (const T *)packed_lin;
-    A.img = (order != 1) ? (const T *)packed_cub : (const T *)packed_lin;
-    A.ext = (order == 1 || order == 3) ? (const T *)packed_ext : nullptr;  // general orders: two-sample form
-    A.lin32 = (sizeof(T) == 8 && order == 1) ? (const float *)lin32 : nullptr;  // LC_F64_WIND_F32_LIN32: the float32 order-1 image (then lin == img == NULL)
-    A.u_raw32 = (sizeof(T) == 8 && order == 3) ? (const float *)lin32 : nullptr;  // ... at order 3: the float32 raw planes (u, then v given as u_raw / v_raw)
-    A.v_raw32 = (sizeof(T) == 8 && order == 3) ? (const float *)lin32_v : nullptr;
-    A.u_raw = (const T *)u_raw;  // (lc_advect_ex validated: only where a kernel reads them)
-    A.v_raw = (const T *)v_raw;
-    A.raw_plane = (size_t)ny_f * nx_f;
-    A.ext_raw = fuse_levels_raw && sizeof(T) == 8 && order == 1 && u_raw && !wind_f32 && !packed_ext;
-    A.ext_cub = fuse_levels_raw && sizeof(T) == 8 && order == 3 && packed_cub && !wind_f32 && !packed_ext;
-    A.level_elems = lc_level_elems(ny_f, nx_f);
-    A.pitch = nx_f + LC_PAD;
-    A.ny_f = ny_f;
-    A.nx_f = nx_f;
-    A.lat_min = (T)lat_min;
-    A.lon_min = (T)lon_min;
-    A.lat_span = (T)lat_max - (T)lat_min;
-    A.lon_span = (T)lon_max - (T)lon_min;
-    set_fast_transform(A);
-    A.y_min = (T)lat_min;
-    A.y_max = (T)lat_max;
-    A.x_min = (T)lon_min;
-    A.x_max = (T)lon_max;
-    A.seed_lat = (const T *)seed_lat;
-    A.seed_lon = (const T *)seed_lon;
-    A.ny = ny;
-    A.nx = nx;
-    A.row0 = row0;
-    A.ny_global = ny_global;
+    set_field_geometry(A, call.src, a);  // (raw planes: lc_advect_ex validated, only where a kernel reads them)
+    A.ext = (order == 1 || order == 3) ? (const T *)call.ext : nullptr;  // general orders: two-sample form
+    A.lin32 = (sizeof(T) == 8 && order == 1) ? (const float *)call.lin32 : nullptr;  // LC_F64_WIND_F32_LIN32: the float32 order-1 image (then lin == img == NULL)
+    A.u_raw32 = (sizeof(T) == 8 && order == 3) ? (const float *)call.lin32 : nullptr;  // ... at order 3: the float32 raw planes (u, then v given as u_raw / v_raw)
+    A.v_raw32 = (sizeof(T) == 8 && order == 3) ? (const float *)call.lin32_v : nullptr;
+    A.ext_raw = a.fuse_levels_raw && sizeof(T) == 8 && order == 1 && call.src.u_raw && !call.wind_f32 && !call.ext;
+    A.ext_cub = a.fuse_levels_raw && sizeof(T) == 8 && order == 3 && call.src.cub && !call.wind_f32 && !call.ext;
+    A.y_min = (T)a.lat_min;
+    A.y_max = (T)a.lat_max;
+    A.x_min = (T)a.lon_min;
+    A.x_max = (T)a.lon_max;
+    A.seed_lat = (const T *)a.seed_lat_dev;
+    A.seed_lon = (const T *)a.seed_lon_dev;
     const double conv_y = 180.0 / (6371000.0 * 3.141592653589793);  // trajectory.py:55
-    A.dt = (T)timestep;
-    A.half_dt = (T)(0.5 * timestep);
-    A.dtcy = (T)(timestep * conv_y);
-    A.hdtcy = (T)((0.5 * timestep) * conv_y);
+    A.dt = (T)a.timestep;
+    A.half_dt = (T)(0.5 * a.timestep);
+    A.dtcy = (T)(a.timestep * conv_y);
+    A.hdtcy = (T)((0.5 * a.timestep) * conv_y);
     A.K = K;
-    A.order = order;
-    const bool outer = cyclic == LC_X_CLAMP_REFERENCE_OUTER;
-    A.cyclic = cyclic == LC_X_CYCLIC;
+    const bool outer = a.cyclic_x == LC_X_CLAMP_REFERENCE_OUTER;
+    A.cyclic = a.cyclic_x == LC_X_CYCLIC;
     A.clamp_flag = nullptr;
     A.verify = sizeof(T) == 4 ? ctx->verify_dev : nullptr;
     unsigned *clamp_flag = nullptr;
     // lc_advect_series: one flag per member, decided per member (each keeps its fused result, or restarts at its own chunk)
-    const bool per_member = outer && series && n_members > 1;
+    const bool per_member = outer && call.series && n_members > 1;
     const int n_flags = per_member ? n_members : 1;
     if (outer) {
         // fused kernel first, with a flag that says whether the clamp ever moved a parcel; if not, per-point and
@@ -4348,12 +4318,12 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
         A.clamp_flag = clamp_flag;
         A.clamp_stride = per_member ? 1 : 0;
     }
-    A.t0 = t0;
-    A.nsteps = nsteps;
-    A.x_out = (T *)x_out;
-    A.y_out = (T *)y_out;
-    A.traj_x = (T *)traj_x;
-    A.traj_y = (T *)traj_y;
+    A.t0 = a.t0;
+    A.nsteps = a.nsteps;
+    A.x_out = (T *)a.x_out;
+    A.y_out = (T *)a.y_out;
+    A.traj_x = (T *)a.traj_x;
+    A.traj_y = (T *)a.traj_y;
     A.ntx = (nx + TILE_W - 1) / TILE_W;
     const int nty = (ny + TILE_H - 1) / TILE_H;
     A.ntiles = A.ntx * nty;
@@ -4367,7 +4337,7 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
         A.pole_hi = pr.hi;
         A.pole_blocks = pr.blocks;
     }
-    const int grid = xcd_grid(A.ntiles, A.xcd_chunk) + A.pole_blocks;
+    const int grid = lcplan::xcd_grid(A.ntiles, A.xcd_chunk) + A.pole_blocks;
     // Kernel choice (float + fused levels only; measured on MI355X, 4096^2 seeds, 96 steps, K=4, 8x8-seed waves):
     //   order 1: direct gather 10.9 ms (vector-L1 lookup bound), LDS tiles 10.2 ms (VALU-issue bound);
     //   order 3: direct gather 37.8 ms, LDS tiles 20.4 ms.
@@ -4378,52 +4348,34 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
     // lc_ctx_set_lds_tiles / LCS_LDS_TILES (read once at context creation) override (profiling).
     const bool use_lds = ctx->lds_tiles != 0;
     const bool fused64 = sizeof(T) == 8 && (A.ext != nullptr || A.ext_raw || A.ext_cub);  // single-sample iterations in float64
-    const char *name = nullptr;
-    auto launch = [&](const AdvectArgs<T> &A) {
+    auto launch = [&](const AdvectArgs<T> &A) -> const char * {  // the name of the kernel it launched
         if constexpr (sizeof(T) == 8) {
             if (A.lin32) {  // LC_F64_WIND_F32_LIN32: per-wave LDS tiles of levels t and t + 1, or direct gathers
                 const bool tiles = use_lds && A.K > 0 && A.nx_f + LC_PAD >= TW_COLS && A.ny_f + LC_PAD >= TW_ROWS;
-#define LC_W32(KF, CY, NAME)                                                                                       \
-    {                                                                                                              \
-        hipLaunchKernelGGL((advect_lds64w_kernel<KF, CY>), dim3(grid, nmem(A)), dim3(BLOCK), 0, ctx->stream, A);   \
-        name = NAME;                                                                                               \
-        return;                                                                                                    \
-    }
-                if (tiles && A.K == 4 && A.cyclic) LC_W32(4, true, "advect_lds64w_kernel<4, true>")
-                if (tiles && A.K == 4) LC_W32(4, false, "advect_lds64w_kernel<4, false>")
-                if (tiles && A.cyclic) LC_W32(-1, true, "advect_lds64w_kernel<-1, true>")
-                if (tiles) LC_W32(-1, false, "advect_lds64w_kernel<-1, false>")
-#undef LC_W32
-                hipLaunchKernelGGL(advect_w32_kernel, dim3(grid, nmem(A)), dim3(BLOCK), 0, ctx->stream, A);
-                name = "advect_w32_kernel";
-                return;
+                if (tiles && A.K == 4 && A.cyclic) return launch_kernel(advect_lds64w_kernel<4, true>, grid, ctx->stream, A, "advect_lds64w_kernel<4, true>");
+                if (tiles && A.K == 4) return launch_kernel(advect_lds64w_kernel<4, false>, grid, ctx->stream, A, "advect_lds64w_kernel<4, false>");
+                if (tiles && A.cyclic) return launch_kernel(advect_lds64w_kernel<-1, true>, grid, ctx->stream, A, "advect_lds64w_kernel<-1, true>");
+                if (tiles) return launch_kernel(advect_lds64w_kernel<-1, false>, grid, ctx->stream, A, "advect_lds64w_kernel<-1, false>");
+                return launch_kernel(advect_w32_kernel, grid, ctx->stream, A, "advect_w32_kernel");
             }
             if (A.u_raw32 && order == 3 && use_lds && A.nx_f + LC_PAD >= TW3 && A.ny_f + LC_PAD >= TW3) {
                 // LC_F64_WIND_F32_LIN32 at order 3: tiles of the float64 coefficients of levels t and t + 1 (else: the generic kernel below,
                 // whose pole rows read the float32 planes)
-#define LC_W32O3(KF, CY, NAME)                                                                                        \
-    {                                                                                                                 \
-        hipLaunchKernelGGL((advect_lds64w_o3_kernel<KF, CY>), dim3(grid, nmem(A)), dim3(BLOCK), 0, ctx->stream, A);   \
-        name = NAME;                                                                                                  \
-        return;                                                                                                       \
-    }
-                if (A.K == 4 && A.cyclic) LC_W32O3(4, true, "advect_lds64w_o3_kernel<4, true>")
-                if (A.K == 4) LC_W32O3(4, false, "advect_lds64w_o3_kernel<4, false>")
-                if (A.cyclic) LC_W32O3(-1, true, "advect_lds64w_o3_kernel<-1, true>")
-                LC_W32O3(-1, false, "advect_lds64w_o3_kernel<-1, false>")
-#undef LC_W32O3
+                if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds64w_o3_kernel<4, true>, grid, ctx->stream, A, "advect_lds64w_o3_kernel<4, true>");
+                if (A.K == 4) return launch_kernel(advect_lds64w_o3_kernel<4, false>, grid, ctx->stream, A, "advect_lds64w_o3_kernel<4, false>");
+                if (A.cyclic) return launch_kernel(advect_lds64w_o3_kernel<-1, true>, grid, ctx->stream, A, "advect_lds64w_o3_kernel<-1, true>");
+                return launch_kernel(advect_lds64w_o3_kernel<-1, false>, grid, ctx->stream, A, "advect_lds64w_o3_kernel<-1, false>");
             }
         }
+        const char *name = nullptr;
         if (order == 2 || order == 4 || order == 5) {  // generic direct kernel, any dtype
             name = order == 2 ? DirectLaunch<T, 2>::launch(A, grid, ctx->stream)
                  : order == 4 ? DirectLaunch<T, 4>::launch(A, grid, ctx->stream) : DirectLaunch<T, 5>::launch(A, grid, ctx->stream);
         } else if (order == 3) {
             if (fused64) {
                 name = Lds64Launch<T>::launch_o3(A, grid, ctx->stream, ctx->lds_tiles);
-                if (!name) {  // (with ext_cub too: advect_seed_fast64_o3 looks at it)
-                    hipLaunchKernelGGL((advect_kernel<T, 3, sizeof(T) == 8>), dim3(grid, nmem(A)), dim3(BLOCK), 0, ctx->stream, A);
-                    name = "advect_kernel<double, 3, true, 0>";
-                }
+                // (with ext_cub too: advect_seed_fast64_o3 looks at it)
+                if (!name) return launch_kernel(advect_kernel<T, 3, sizeof(T) == 8>, grid, ctx->stream, A, "advect_kernel<double, 3, true, 0>");
             } else if (!(use_lds && (name = LdsLaunch<T, 3>::launch(A, grid, ctx->stream, ctx->lds_tiles)))) {
                 name = DirectLaunch<T, 3>::launch(A, grid, ctx->stream);
             }
@@ -4432,23 +4384,18 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
                 name = Lds64Launch<T>::launch(A, grid, ctx->stream, ctx->lds_tiles);
                 if (!name) {
                     if constexpr (sizeof(T) == 8) {
-                        if (A.ext_raw) {
-                            hipLaunchKernelGGL((advect_kernel<T, 1, true, SRC_RAW_ALL>), dim3(grid, nmem(A)), dim3(BLOCK), 0, ctx->stream, A);
-                            name = "advect_kernel<double, 1, true, 2>";
-                        } else if (A.u_raw) {
-                            hipLaunchKernelGGL((advect_kernel<T, 1, true, SRC_RAW_EULER>), dim3(grid, nmem(A)), dim3(BLOCK), 0, ctx->stream, A);
-                            name = "advect_kernel<double, 1, true, 1>";
-                        } else {
-                            hipLaunchKernelGGL((advect_kernel<T, 1, true>), dim3(grid, nmem(A)), dim3(BLOCK), 0, ctx->stream, A);
-                            name = "advect_kernel<double, 1, true, 0>";
-                        }
+                        if (A.ext_raw) return launch_kernel(advect_kernel<T, 1, true, SRC_RAW_ALL>, grid, ctx->stream, A, "advect_kernel<double, 1, true, 2>");
+                        if (A.u_raw) return launch_kernel(advect_kernel<T, 1, true, SRC_RAW_EULER>, grid, ctx->stream, A, "advect_kernel<double, 1, true, 1>");
+                        return launch_kernel(advect_kernel<T, 1, true>, grid, ctx->stream, A, "advect_kernel<double, 1, true, 0>");
                     }
                 }
             } else if (!(use_lds && (name = LdsLaunch<T, 1>::launch(A, grid, ctx->stream, ctx->lds_tiles)))) {
                 name = DirectLaunch<T, 1>::launch(A, grid, ctx->stream);
             }
         }
+        return name;
     };
+    const char *name = nullptr;
     // Level chunks (lc_ctx_set_level_chunk): the series runs as consecutive launches of at most `chunk` time levels,
     // each continuing from the positions the previous one left in x_out / y_out (a seed's start is read by the thread
     // that writes its result, so in place is safe).  A launch's workgroups then stay within `chunk` levels of each
@@ -4488,14 +4435,14 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
     const int n_dir = A.member_dirs ? 2 : 1;
     const int n_launch = n_members / n_dir;  // members of one fused launch
     A.n_members = n_launch;  // (the kernel choice by size counts a launch's members: lc_advect_series's for the same windows)
-    const bool pairs_ok = n_launch > 1 && order == 1 && !outer && !traj_x && use_lds &&
+    const bool pairs_ok = n_launch > 1 && order == 1 && !outer && !a.traj_x && use_lds &&
                           (ctx->patch_mode < 0 || ctx->patch_mode == PATCH_PAIR) && K > 0 && order1_two_seed_applies(A, ctx->lds_tiles);
-    const lcplan::Groups G = lcplan::member_groups(n_launch, t0_stride, nsteps, pairs_ok);
+    const lcplan::Groups G = lcplan::member_groups(n_launch, t0_stride, a.nsteps, pairs_ok);
     const int total = G.total;
     A.member_plane = (size_t)n_dir * plane_elems;
     if (G.g) {
         A.pair_d = t0_stride;
-        A.pair_n = nsteps;
+        A.pair_n = a.nsteps;
         A.pair_plane = (size_t)n_dir * plane_elems;
         A.pair_g = G.g;
         A.pair_last = G.last;
@@ -4507,7 +4454,7 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
     int n_launches = 0;
     auto launch_dirs = [&](const AdvectArgs<T> &C) {
         if (n_dir == 1) {
-            launch(C);
+            name = launch(C);
             ++n_launches;
             return;
         }
@@ -4521,7 +4468,7 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
                 D.y_start = C.y_start + (size_t)d * plane_elems;
             }
             if (C.clamp_flag) D.clamp_flag = C.clamp_flag + d;
-            launch(D);
+            name = launch(D);
             ++n_launches;
         }
     };
@@ -4530,7 +4477,7 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
     // per_member: saved is [2][n_members][ny*nx] (each member's positions at the start of ITS current chunk: a member whose flag
     // fired keeps the plane of that chunk), restarts[m] = the step member m re-enters at in the sub-step phase, -1 = not fired
     std::vector<int> restarts(per_member ? n_members : 0, -1);
-    std::vector<unsigned> moved_m(per_member ? n_members : 0, 0u);
+    std::vector<unsigned> moved(n_flags, 0u);  // the clamp flags as read back after a chunk (outer mode)
     int n_fired = 0;
     const size_t saved_planes = per_member ? (size_t)n_members : 1;
     auto flag_error = [&]() {
@@ -4541,7 +4488,7 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
     for (int ci = 0, nci = lcplan::n_chunks(total, chunk); ci < nci; ++ci) {
         const int s0 = lcplan::chunk_first(ci, chunk);
         AdvectArgs<T> C = A;
-        C.t0 = t0 + s0;
+        C.t0 = a.t0 + s0;
         C.nsteps = lcplan::chunk_levels(ci, total, chunk);
         C.pair_l0 = s0;
         if (s0 > 0) {
@@ -4579,40 +4526,30 @@ int advect_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, con
             }
         }
         launch_dirs(C);
+        if (!outer) continue;
+        hipError_t e1 = hipGetLastError();
+        // one flag, row-sharded: "did a parcel leave the box ANYWHERE" -- every rank must take the same path below
+        // (a flag per member: whole grids only, no flag all-reduce -- lc_advect_series refuses row blocks)
+        const bool red_fail = !per_member && e1 == hipSuccess && ctx->flag_reduce && ctx->flag_reduce(ctx->flag_reduce_user, clamp_flag, 1) != 0;
+        // (every member's flag in one read-back)
+        if (e1 == hipSuccess && !red_fail) e1 = hipMemcpyAsync(moved.data(), clamp_flag, n_flags * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream);
+        if (e1 == hipSuccess && !red_fail) e1 = hipStreamSynchronize(ctx->stream);
+        if (red_fail || e1 != hipSuccess) {
+            (void)hipFreeAsync(clamp_flag, ctx->stream);
+            if (saved) (void)hipFreeAsync(saved, ctx->stream);
+            if (red_fail) return flag_error();
+            LC_HIP_CHECK(e1);
+        }
         if (per_member) {
-            // every member's flag in one read-back (whole grids only: no flag all-reduce, lc_advect_series refuses row blocks)
-            hipError_t e1 = hipGetLastError();
-            if (e1 == hipSuccess)
-                e1 = hipMemcpyAsync(moved_m.data(), clamp_flag, n_members * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream);
-            if (e1 == hipSuccess) e1 = hipStreamSynchronize(ctx->stream);
-            if (e1 != hipSuccess) {
-                (void)hipFreeAsync(clamp_flag, ctx->stream);
-                if (saved) (void)hipFreeAsync(saved, ctx->stream);
-                LC_HIP_CHECK(e1);
-            }
             for (int m = 0; m < n_members; ++m)
-                if (restarts[m] < 0 && moved_m[m]) {
+                if (restarts[m] < 0 && moved[m]) {
                     restarts[m] = lcplan::outer_restart(s0, saved != nullptr);
                     ++n_fired;
                 }
             if (n_fired == n_members) break;
-        } else if (outer) {
-            unsigned moved = 0;
-            hipError_t e1 = hipGetLastError();
-            // row-sharded: "did a parcel leave the box ANYWHERE" -- every rank must take the same path below
-            const bool red_fail = e1 == hipSuccess && ctx->flag_reduce && ctx->flag_reduce(ctx->flag_reduce_user, clamp_flag, 1) != 0;
-            if (e1 == hipSuccess && !red_fail) e1 = hipMemcpyAsync(&moved, clamp_flag, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream);
-            if (e1 == hipSuccess && !red_fail) e1 = hipStreamSynchronize(ctx->stream);
-            if (red_fail || e1 != hipSuccess) {
-                (void)hipFreeAsync(clamp_flag, ctx->stream);
-                if (saved) (void)hipFreeAsync(saved, ctx->stream);
-                if (red_fail) return flag_error();
-                LC_HIP_CHECK(e1);
-            }
-            if (moved) {
-                restart = lcplan::outer_restart(s0, saved != nullptr);   // (no room for the saved positions: from the seed grid, as before)
-                break;
-            }
+        } else if (moved[0]) {
+            restart = lcplan::outer_restart(s0, saved != nullptr);   // (no room for the saved positions: from the seed grid, as before)
+            break;
         }
     }
     ctx->last_advect_kernel = name;
@@ -4663,36 +4600,27 @@ __global__ void sample_kernel(const AdvectArgs<T> A, const T *__restrict__ px, c
     }
 }
 
+// A validated lc_sample_raw call (the field's shape and the seed block under set_field_geometry's names)
+struct SampleCall {
+    FieldSource src;
+    int ny_f, nx_f;
+    double lat_min, lat_max, lon_min, lon_max;
+    int ny, nx, row0, ny_global, interp_order;
+    int level;
+    const void *px, *py;  // [ny*nx] positions (degrees)
+    void *out_u, *out_v;
+};
+
 template <typename T>
-int sample_impl(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, const void *u_raw, const void *v_raw, int ny_f, int nx_f, double lat_min,
-                double lat_max, double lon_min, double lon_max, int level, const void *px, const void *py, int ny,
-                int nx, int row0, int ny_global, int order, void *out_u, void *out_v) {
+int sample_impl(lc_ctx *ctx, const SampleCall &c) {
     AdvectArgs<T> A = {};
-    A.lin = (const T *)packed_lin;
-    A.img = (order != 1) ? (const T *)packed_cub : (const T *)packed_lin;
-    A.u_raw = (const T *)u_raw;
-    A.v_raw = (const T *)v_raw;
-    A.raw_plane = (size_t)ny_f * nx_f;
-    A.level_elems = lc_level_elems(ny_f, nx_f);
-    A.pitch = nx_f + LC_PAD;
-    A.ny_f = ny_f;
-    A.nx_f = nx_f;
-    A.lat_min = (T)lat_min;
-    A.lon_min = (T)lon_min;
-    A.lat_span = (T)lat_max - (T)lat_min;
-    A.lon_span = (T)lon_max - (T)lon_min;
-    set_fast_transform(A);
-    A.ny = ny;
-    A.nx = nx;
-    A.row0 = row0;
-    A.ny_global = ny_global;
-    A.order = order;
-    const size_t n = (size_t)ny * nx;
+    set_field_geometry(A, c.src, c);
+    const size_t n = (size_t)c.ny * c.nx;
     const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
-#define LC_SAMPLE(ORD)                                                                                                 \
-    hipLaunchKernelGGL((sample_kernel<T, ORD>), dim3(blocks), dim3(256), 0, ctx->stream, A, (const T *)px, (const T *)py, \
-                       level, (T *)out_u, (T *)out_v)
-    switch (order) {
+#define LC_SAMPLE(ORD)                                                                                                     \
+    hipLaunchKernelGGL((sample_kernel<T, ORD>), dim3(blocks), dim3(256), 0, ctx->stream, A, (const T *)c.px, (const T *)c.py, \
+                       c.level, (T *)c.out_u, (T *)c.out_v)
+    switch (c.interp_order) {
         case 2: LC_SAMPLE(2); break;
         case 3: LC_SAMPLE(3); break;
         case 4: LC_SAMPLE(4); break;
@@ -4790,27 +4718,9 @@ __global__ void __launch_bounds__(256) tracer_kernel(const AdvectArgs<T> A, cons
 }
 
 template <typename T>
-int tracer_impl(lc_ctx *ctx, const lc_tracer_args &a, const void *c1_raw, const void *c2_raw) {
+int tracer_impl(lc_ctx *ctx, const lc_tracer_args &a, const FieldSource &src) {
     AdvectArgs<T> A = {};
-    A.lin = (const T *)a.tracer_lin;
-    A.img = (a.interp_order != 1) ? (const T *)a.tracer_cub : (const T *)a.tracer_lin;
-    A.u_raw = (const T *)c1_raw;
-    A.v_raw = (const T *)c2_raw;
-    A.raw_plane = (size_t)a.ny_f * a.nx_f;
-    A.level_elems = lc_level_elems(a.ny_f, a.nx_f);
-    A.pitch = a.nx_f + LC_PAD;
-    A.ny_f = a.ny_f;
-    A.nx_f = a.nx_f;
-    A.lat_min = (T)a.lat_min;
-    A.lon_min = (T)a.lon_min;
-    A.lat_span = (T)a.lat_max - (T)a.lat_min;
-    A.lon_span = (T)a.lon_max - (T)a.lon_min;
-    set_fast_transform(A);
-    A.ny = a.ny;
-    A.nx = a.nx;
-    A.row0 = a.row0;
-    A.ny_global = a.ny_global;
-    A.order = a.interp_order;
+    set_field_geometry(A, src, a);
     TracerOut<T> O;
     O.c1 = (T *)a.c1_out;
     O.c2 = (T *)a.c2_out;
@@ -4900,12 +4810,26 @@ extern "C" int lc_sample_raw(lc_ctx *ctx, const void *packed_lin, const void *pa
     LC_REQUIRE(row0 >= 0 && row0 + ny <= ny_global, "lc_sample: rows outside the global grid");
     LC_REQUIRE(lat_max > lat_min && lon_max > lon_min, "lc_sample: field coordinates must be ascending");
     LC_HIP_CHECK(hipSetDevice(ctx->device));
-    if (!raw_replaces_lin(u_raw, v_raw, dtype, interp_order)) u_raw = v_raw = nullptr;
-    if (dtype == LC_F32)
-        return sample_impl<float>(ctx, packed_lin, packed_cub, u_raw, v_raw, ny_f, nx_f, lat_min, lat_max, lon_min, lon_max, level,
-                                  pos_x_dev, pos_y_dev, ny, nx, row0, ny_global, interp_order, out_u, out_v);
-    return sample_impl<double>(ctx, packed_lin, packed_cub, u_raw, v_raw, ny_f, nx_f, lat_min, lat_max, lon_min, lon_max, level,
-                               pos_x_dev, pos_y_dev, ny, nx, row0, ny_global, interp_order, out_u, out_v);
+    const bool raw = raw_replaces_lin(u_raw, v_raw, dtype, interp_order);
+    SampleCall c = {};
+    c.src = {packed_lin, packed_cub, raw ? u_raw : nullptr, raw ? v_raw : nullptr};
+    c.ny_f = ny_f;
+    c.nx_f = nx_f;
+    c.lat_min = lat_min;
+    c.lat_max = lat_max;
+    c.lon_min = lon_min;
+    c.lon_max = lon_max;
+    c.ny = ny;
+    c.nx = nx;
+    c.row0 = row0;
+    c.ny_global = ny_global;
+    c.interp_order = interp_order;
+    c.level = level;
+    c.px = pos_x_dev;
+    c.py = pos_y_dev;
+    c.out_u = out_u;
+    c.out_v = out_v;
+    return dtype == LC_F32 ? sample_impl<float>(ctx, c) : sample_impl<double>(ctx, c);
 }
 
 extern "C" int lc_sample(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, int dtype, int nt, int ny_f,
@@ -4940,9 +4864,9 @@ extern "C" int lc_tracer_sample(lc_ctx *ctx, const lc_tracer_args *args) {
     LC_REQUIRE(!(a.mean1_out || a.mean2_out) || a.mean_count >= 1, "lc_tracer_sample: mean_count %d", a.mean_count);
     LC_HIP_CHECK(hipSetDevice(ctx->device));
     const bool raw = raw_replaces_lin(a.c1_raw, a.c2_raw, a.dtype, a.interp_order);
-    const void *c1_raw = raw ? a.c1_raw : nullptr, *c2_raw = raw ? a.c2_raw : nullptr;
-    if (a.dtype == LC_F32) return tracer_impl<float>(ctx, a, c1_raw, c2_raw);
-    return tracer_impl<double>(ctx, a, c1_raw, c2_raw);
+    const FieldSource src = {a.tracer_lin, a.tracer_cub, raw ? a.c1_raw : nullptr, raw ? a.c2_raw : nullptr};
+    if (a.dtype == LC_F32) return tracer_impl<float>(ctx, a, src);
+    return tracer_impl<double>(ctx, a, src);
 }
 
 extern "C" int lc_advect(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, const void *packed_ext,
@@ -5008,6 +4932,25 @@ extern "C" int lc_advect_batch(lc_ctx *ctx, const void *packed_lin, const void *
     return lc_advect_ex(ctx, &a);
 }
 
+// The pointers of a checked call as the kernels of its dtype read them, and the call's kind.  raw_ok: the raw planes serve
+// a kernel family of this dtype and order.
+static AdvectCall resolve_advect_call(const lc_advect_args &a, bool raw_ok, bool series, int dirs) {
+    AdvectCall c = {};
+    c.series = series;
+    c.dirs = dirs;
+    c.wind_f32 = a.dtype == LC_F64_WIND_F32 || a.dtype == LC_F64_WIND_F32_LIN32;
+    if (a.dtype == LC_F64_WIND_F32_LIN32) {   // (order 1: the float32 image; order 3: the float64 coefficients + the float32 planes)
+        c.src.cub = a.interp_order == 3 ? a.packed_cub : nullptr;
+        c.lin32 = a.interp_order == 1 ? a.packed_lin : a.u_raw;
+        c.lin32_v = a.interp_order == 3 ? a.v_raw : nullptr;
+        return c;
+    }
+    // (without raw_ok: float32 at order 1 reads the lin image's 16-byte node pairs)
+    c.src = {a.packed_lin, a.packed_cub, raw_ok ? a.u_raw : nullptr, raw_ok ? a.v_raw : nullptr};
+    c.ext = a.packed_ext;
+    return c;
+}
+
 // lc_advect_ex, and with series = true lc_advect_series: the reference's outer clamp for n_members > 1 (a flag per member,
 // advect_outer_series_impl), whole grids only.  dirs = 2 (lc_advect_series_dirs): every window in both directions of time,
 // 2 x n_members planes, plane 2w + d with -timestep for d = 1.
@@ -5018,99 +4961,80 @@ static int advect_ex_checked(lc_ctx *ctx, const lc_advect_args *args, bool serie
     LC_REQUIRE(dirs == 1 || dirs == 2, "lc_advect_series_dirs: n_dirs %d (1 or 2)", dirs);
     LC_REQUIRE(ctx, "lc_advect: null context");
     const lc_advect_args &a = *args;
-    const void *packed_lin = a.packed_lin, *packed_cub = a.packed_cub, *packed_ext = a.packed_ext, *u_raw = a.u_raw, *v_raw = a.v_raw;
-    const int dtype = a.dtype, nt = a.nt, ny_f = a.ny_f, nx_f = a.nx_f, ny = a.ny, nx = a.nx, row0 = a.row0, ny_global = a.ny_global;
-    const int settls_order = a.settls_order, interp_order = a.interp_order, cyclic_x = a.cyclic_x, t0 = a.t0, nsteps = a.nsteps;
-    const int n_members = a.n_members, t0_stride = a.t0_stride;
-    const void *x_start = a.x_start, *y_start = a.y_start, *seed_lat_dev = a.seed_lat_dev, *seed_lon_dev = a.seed_lon_dev;
-    void *x_out = a.x_out, *y_out = a.y_out, *traj_x = a.traj_x, *traj_y = a.traj_y;
-    const double lat_min = a.lat_min, lat_max = a.lat_max, lon_min = a.lon_min, lon_max = a.lon_max, timestep = a.timestep;
-    LC_REQUIRE(n_members >= 1 && n_members * dirs <= 65535 && t0_stride >= 0, "lc_advect_batch: bad n_members %d / t0_stride %d", n_members,
-               t0_stride);
+    LC_REQUIRE(a.n_members >= 1 && a.n_members * dirs <= 65535 && a.t0_stride >= 0, "lc_advect_batch: bad n_members %d / t0_stride %d", a.n_members,
+               a.t0_stride);
+    const bool outer = a.cyclic_x == LC_X_CLAMP_REFERENCE_OUTER, row_block = a.row0 != 0 || a.ny != a.ny_global;
     if (series) {
-        LC_REQUIRE(!traj_x && !traj_y, "lc_advect_series: traj_x / traj_y must be NULL");
-        if (row0 != 0 || ny != ny_global) {
-            lc_set_error("lc_advect_series: whole seed grids only (rows [%d,%d) of %d given)", row0, row0 + ny, ny_global);
+        LC_REQUIRE(!a.traj_x && !a.traj_y, "lc_advect_series: traj_x / traj_y must be NULL");
+        if (row_block) {
+            lc_set_error("lc_advect_series: whole seed grids only (rows [%d,%d) of %d given)", a.row0, a.row0 + a.ny, a.ny_global);
             return LC_EUNSUPPORTED;
         }
-    } else if (n_members > 1) {
-        LC_REQUIRE(!traj_x && !traj_y, "lc_advect_batch: trajectories are per member: call lc_advect for each");
-        if (cyclic_x == LC_X_CLAMP_REFERENCE_OUTER) {
+    } else if (a.n_members > 1) {
+        LC_REQUIRE(!a.traj_x && !a.traj_y, "lc_advect_batch: trajectories are per member: call lc_advect for each");
+        if (outer) {
             lc_set_error("lc_advect_batch: LC_X_CLAMP_REFERENCE_OUTER is decided per member: call lc_advect for each");
             return LC_EUNSUPPORTED;
         }
     }
-    LC_REQUIRE((x_start == nullptr) == (y_start == nullptr), "lc_advect_from: x_start and y_start must both be set or both NULL");
-    if (x_start && cyclic_x == LC_X_CLAMP_REFERENCE_OUTER) {
+    LC_REQUIRE((a.x_start == nullptr) == (a.y_start == nullptr), "lc_advect_from: x_start and y_start must both be set or both NULL");
+    if (a.x_start && outer) {
         lc_set_error("lc_advect_from: LC_X_CLAMP_REFERENCE_OUTER restarts from the seed grid when a parcel leaves the box "
                      "and cannot continue from given positions");
         return LC_EUNSUPPORTED;
     }
-    LC_REQUIRE(dtype == LC_F32 || dtype == LC_F64 || dtype == LC_F64_WIND_F32 || dtype == LC_F64_WIND_F32_LIN32, "lc_advect: bad dtype %d", dtype);
-    LC_REQUIRE((dtype != LC_F64_WIND_F32 && dtype != LC_F64_WIND_F32_LIN32) || !packed_ext, "lc_advect: LC_F64_WIND_F32 keeps the two-sample form (no ext)");
-    if (dtype == LC_F64_WIND_F32_LIN32) {
-        if ((interp_order != 1 && interp_order != 3) || cyclic_x == LC_X_CLAMP_REFERENCE_OUTER) {
+    const bool lin32 = a.dtype == LC_F64_WIND_F32_LIN32;
+    LC_REQUIRE(a.dtype == LC_F32 || a.dtype == LC_F64 || a.dtype == LC_F64_WIND_F32 || lin32, "lc_advect: bad dtype %d", a.dtype);
+    LC_REQUIRE((a.dtype != LC_F64_WIND_F32 && !lin32) || !a.packed_ext, "lc_advect: LC_F64_WIND_F32 keeps the two-sample form (no ext)");
+    if (lin32) {
+        if ((a.interp_order != 1 && a.interp_order != 3) || outer) {
             lc_set_error("lc_advect: LC_F64_WIND_F32_LIN32 serves interp_order 1 and 3 with cyclic / per-point boundaries; interp_order %d or "
-                         "LC_X_CLAMP_REFERENCE_OUTER take LC_F64_WIND_F32 (float64 images of the float32 wind)", interp_order);
+                         "LC_X_CLAMP_REFERENCE_OUTER take LC_F64_WIND_F32 (float64 images of the float32 wind)", a.interp_order);
             return LC_EUNSUPPORTED;
         }
-        if (interp_order == 1)
-            LC_REQUIRE(packed_lin && !packed_cub && !u_raw && !v_raw, "lc_advect: LC_F64_WIND_F32_LIN32 at order 1 takes packed_lin (the float32 order-1 image) and nothing else");
+        if (a.interp_order == 1)
+            LC_REQUIRE(a.packed_lin && !a.packed_cub && !a.u_raw && !a.v_raw, "lc_advect: LC_F64_WIND_F32_LIN32 at order 1 takes packed_lin (the float32 order-1 image) and nothing else");
         else
-            LC_REQUIRE(packed_cub && u_raw && v_raw && !packed_lin, "lc_advect: LC_F64_WIND_F32_LIN32 at order 3 takes packed_cub (float64 coefficients: "
+            LC_REQUIRE(a.packed_cub && a.u_raw && a.v_raw && !a.packed_lin, "lc_advect: LC_F64_WIND_F32_LIN32 at order 3 takes packed_cub (float64 coefficients: "
                        "lc_field_pack with LC_F64_WIND_F32) and the float32 planes as u_raw / v_raw");
     }
-    if (interp_order < 1 || interp_order > 5) {
+    if (a.interp_order < 1 || a.interp_order > 5) {
         lc_set_error("lc_advect: interp_order %d unsupported (scipy's spline orders 1..5; 0 fails in the reference too)",
-                     interp_order);
+                     a.interp_order);
         return LC_EUNSUPPORTED;
     }
-    LC_REQUIRE((u_raw == nullptr) == (v_raw == nullptr), "lc_advect_ex: u_raw and v_raw must both be set or both NULL");
-    const bool raw_ok = raw_replaces_lin(u_raw, v_raw, dtype, interp_order) || dtype == LC_F64_WIND_F32_LIN32;
-    LC_REQUIRE(packed_lin || raw_ok, "lc_advect: packed_lin is required (the order-1 image: pole rows use order 1) unless lc_advect_ex is "
+    LC_REQUIRE((a.u_raw == nullptr) == (a.v_raw == nullptr), "lc_advect_ex: u_raw and v_raw must both be set or both NULL");
+    const bool raw_ok = raw_replaces_lin(a.u_raw, a.v_raw, a.dtype, a.interp_order) || lin32;
+    LC_REQUIRE(a.packed_lin || raw_ok, "lc_advect: packed_lin is required (the order-1 image: pole rows use order 1) unless lc_advect_ex is "
                "given the raw planes u_raw / v_raw -- and in LC_F32 at interp_order 1 always");
-    if (!raw_ok) u_raw = v_raw = nullptr;  // (float32 at order 1 reads the lin image's 16-byte node pairs)
-    LC_REQUIRE(interp_order == 1 || packed_cub, "lc_advect: interp_order > 1 needs packed_cub (lc_field_pack of that order)");
-    LC_REQUIRE(interp_order == 1 || interp_order == 3 || !packed_ext, "lc_advect: orders 2, 4, 5 take no packed_ext");
-    LC_REQUIRE(nt >= 2 && ny_f >= 4 && nx_f >= 4, "lc_advect: field too small (nt=%d ny_f=%d nx_f=%d)", nt, ny_f, nx_f);
-    LC_REQUIRE(ny >= 1 && nx >= 1 && seed_lat_dev && seed_lon_dev, "lc_advect: bad seed grid");
-    LC_REQUIRE(row0 >= 0 && row0 + ny <= ny_global, "lc_advect: rows [%d,%d) outside global grid of %d rows", row0,
-               row0 + ny, ny_global);
-    LC_REQUIRE(settls_order >= 0, "lc_advect: SETTLS_order must be >= 0");
-    LC_REQUIRE(cyclic_x >= LC_X_CLAMP_POINT && cyclic_x <= LC_X_CLAMP_REFERENCE_OUTER, "lc_advect: bad cyclic_x %d", cyclic_x);
-    if (cyclic_x == LC_X_CLAMP_REFERENCE_OUTER && (row0 != 0 || ny != ny_global) && !ctx->flag_reduce) {
+    LC_REQUIRE(a.interp_order == 1 || a.packed_cub, "lc_advect: interp_order > 1 needs packed_cub (lc_field_pack of that order)");
+    LC_REQUIRE(a.interp_order == 1 || a.interp_order == 3 || !a.packed_ext, "lc_advect: orders 2, 4, 5 take no packed_ext");
+    LC_REQUIRE(a.nt >= 2 && a.ny_f >= 4 && a.nx_f >= 4, "lc_advect: field too small (nt=%d ny_f=%d nx_f=%d)", a.nt, a.ny_f, a.nx_f);
+    LC_REQUIRE(a.ny >= 1 && a.nx >= 1 && a.seed_lat_dev && a.seed_lon_dev, "lc_advect: bad seed grid");
+    LC_REQUIRE(a.row0 >= 0 && a.row0 + a.ny <= a.ny_global, "lc_advect: rows [%d,%d) outside global grid of %d rows", a.row0,
+               a.row0 + a.ny, a.ny_global);
+    LC_REQUIRE(a.settls_order >= 0, "lc_advect: SETTLS_order must be >= 0");
+    LC_REQUIRE(a.cyclic_x >= LC_X_CLAMP_POINT && a.cyclic_x <= LC_X_CLAMP_REFERENCE_OUTER, "lc_advect: bad cyclic_x %d", a.cyclic_x);
+    if (outer && row_block && !ctx->flag_reduce) {
         lc_set_error("lc_advect: LC_X_CLAMP_REFERENCE_OUTER couples every seed row through the offending columns: a row "
-                     "block (rows [%d,%d) of %d) needs lc_ctx_set_flag_allreduce", row0, row0 + ny, ny_global);
+                     "block (rows [%d,%d) of %d) needs lc_ctx_set_flag_allreduce", a.row0, a.row0 + a.ny, a.ny_global);
         return LC_EUNSUPPORTED;
     }
-    LC_REQUIRE(t0 >= 0 && nsteps >= 0 && t0 + (n_members - 1) * t0_stride + nsteps <= nt - 1,
-               "lc_advect: steps [%d,%d) need levels up to %d, have %d", t0, t0 + (n_members - 1) * t0_stride + nsteps,
-               t0 + (n_members - 1) * t0_stride + nsteps, nt);
-    LC_REQUIRE(x_out && y_out, "lc_advect: null output");
-    LC_REQUIRE((traj_x == nullptr) == (traj_y == nullptr), "lc_advect: traj_x and traj_y must both be set or both NULL");
-    LC_REQUIRE(lat_max > lat_min && lon_max > lon_min, "lc_advect: field coordinates must be ascending");
+    const int last_level = a.t0 + (a.n_members - 1) * a.t0_stride + a.nsteps;  // of the last member's last step
+    LC_REQUIRE(a.t0 >= 0 && a.nsteps >= 0 && last_level <= a.nt - 1, "lc_advect: steps [%d,%d) need levels up to %d, have %d", a.t0, last_level,
+               last_level, a.nt);
+    LC_REQUIRE(a.x_out && a.y_out, "lc_advect: null output");
+    LC_REQUIRE((a.traj_x == nullptr) == (a.traj_y == nullptr), "lc_advect: traj_x and traj_y must both be set or both NULL");
+    LC_REQUIRE(a.lat_max > a.lat_min && a.lon_max > a.lon_min, "lc_advect: field coordinates must be ascending");
     // the kernels address a tap inside one time level with 32-bit offsets (24-bit row multiply)
-    if (lc_level_elems(ny_f, nx_f) * ((dtype == LC_F32 || dtype == LC_F64_WIND_F32_LIN32) ? 4 : 1) >= (size_t)1 << 32 || nx_f + LC_PAD >= (1 << 24) ||
-        ny_f + LC_PAD >= (1 << 24)) {
-        lc_set_error("lc_advect: a %dx%d time level is too large for 32-bit tap offsets", ny_f, nx_f);
+    if (lc_level_elems(a.ny_f, a.nx_f) * ((a.dtype == LC_F32 || lin32) ? 4 : 1) >= (size_t)1 << 32 || a.nx_f + LC_PAD >= (1 << 24) ||
+        a.ny_f + LC_PAD >= (1 << 24)) {
+        lc_set_error("lc_advect: a %dx%d time level is too large for 32-bit tap offsets", a.ny_f, a.nx_f);
         return LC_EUNSUPPORTED;
     }
     LC_HIP_CHECK(hipSetDevice(ctx->device));
-    if (dtype == LC_F32)
-        return advect_impl<float>(ctx, packed_lin, packed_cub, packed_ext, u_raw, v_raw, nt, ny_f, nx_f, lat_min, lat_max, lon_min,
-                                  lon_max, seed_lat_dev, ny, seed_lon_dev, nx, row0, ny_global, timestep, settls_order,
-                                  interp_order, cyclic_x, t0, nsteps, x_out, y_out, traj_x, traj_y, x_start, y_start, 0,
-                                  n_members * dirs, t0_stride, 0, nullptr, nullptr, series, dirs);
-    if (dtype == LC_F64_WIND_F32_LIN32)   // (order 1: the float32 image; order 3: the float64 coefficients + the float32 planes)
-        return advect_impl<double>(ctx, nullptr, interp_order == 3 ? packed_cub : nullptr, nullptr, nullptr, nullptr, nt, ny_f, nx_f, lat_min, lat_max, lon_min,
-                                   lon_max, seed_lat_dev, ny, seed_lon_dev, nx, row0, ny_global, timestep, settls_order,
-                                   interp_order, cyclic_x, t0, nsteps, x_out, y_out, traj_x, traj_y, x_start, y_start,
-                                   1, n_members * dirs, t0_stride, 0, interp_order == 1 ? packed_lin : u_raw, interp_order == 3 ? v_raw : nullptr,
-                                   series, dirs);
-    return advect_impl<double>(ctx, packed_lin, packed_cub, packed_ext, u_raw, v_raw, nt, ny_f, nx_f, lat_min, lat_max, lon_min,
-                               lon_max, seed_lat_dev, ny, seed_lon_dev, nx, row0, ny_global, timestep, settls_order,
-                               interp_order, cyclic_x, t0, nsteps, x_out, y_out, traj_x, traj_y, x_start, y_start,
-                               dtype == LC_F64_WIND_F32, n_members * dirs, t0_stride, a.fuse_levels_raw, nullptr, nullptr, series, dirs);
+    const AdvectCall call = resolve_advect_call(a, raw_ok, series, dirs);
+    return a.dtype == LC_F32 ? advect_impl<float>(ctx, a, call) : advect_impl<double>(ctx, a, call);
 }
 
 extern "C" int lc_advect_ex(lc_ctx *ctx, const lc_advect_args *args) { return advect_ex_checked(ctx, args, false); }

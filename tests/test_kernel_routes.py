@@ -44,12 +44,12 @@ def check_complete(names, routes, unreachable):
 
 def test_extractor_sees_the_dispatch_forms():
     snippet = '''
-        if (A.K == 4) LC_LDS2(4, false, PATCH_LINES, "advect_lds2_kernel<4, false, 2>")
-        LC_LDS1(-1, false, true, ORDER == 3 ? "advect_lds_kernel<3, -1, false, lines>" : "advect_lds_kernel<1, -1, false, lines>")
+        if (A.K == 4) return launch_kernel(advect_lds2_kernel<4, false, PATCH_LINES>, g2, st, A, "advect_lds2_kernel<4, false, 2>");
+        return launch_kernel(advect_lds_kernel<ORDER, -1, false, true>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, -1, false, lines>" : "advect_lds_kernel<1, -1, false, lines>");
             return "advect_lds64_o3_kernel<4, true, cub>";
         ctx->last_advect_kernel = "outer_substep_kernel";
         ctx->last_sigma_kernel = fd_fp32_cast ? "sigma_kernel<double, float>" : "sigma_kernel<double, double>";
-        LC_LDS2(7, true, PATCH_TALL, "advect_lds2_kernel<7, true, 0>")   // "advect_in_a_comment<1>"
+        return launch_kernel(advect_lds2_kernel<7, true, PATCH_TALL>, g2, st, A, "advect_lds2_kernel<7, true, 0>");   // "advect_in_a_comment<1>"
         lc_set_error("lc_advect: bad dtype %d", dtype);
     '''
     assert kernel_names(snippet) == {
