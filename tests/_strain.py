@@ -71,10 +71,11 @@ def sign_convention_holds(ex, ey):
     return bool(np.all((ex > 0) | ((ex == 0) & (ey > 0))))
 
 
-def perturbed_seed_grid(ny=37, nx=64, seed=7, dtype=np.float64):
-    """A seed grid (odd tile remainder in both directions) and a smooth random perturbation of it as departure points."""
+def perturbed_seed_grid(ny=37, nx=64, seed=7, dtype=np.float64, lat_edge=70.0):
+    """A seed grid (odd tile remainder in both directions; rows from -lat_edge to lat_edge) and a smooth random perturbation of
+    it as departure points."""
     rng = np.random.default_rng(seed)
-    lat = np.linspace(-70.0, 70.0, ny)
+    lat = np.linspace(-lat_edge, lat_edge, ny)
     lon = -180.0 + 360.0 / nx * np.arange(nx)
     yy, xx = np.meshgrid(np.deg2rad(lat), np.deg2rad(lon), indexing="ij")
     x, y = xx * 0, yy * 0

@@ -8,6 +8,7 @@ The expected value is always ``oracle.flowmap_gradient`` -> F -> ``numpy.linalg.
     on every cell and against numpy's ``v1`` where the spectral gap allows;
   * the rule cases: identity map, one NaN departure point;
   * batches against single calls, the kernel names;
+  * the identities that hold because sigma and strain run one gradient core (csrc/flowmap_gradient.h), at every tile and strip edge;
   * float32 inside the band of the float32 oracle's own error around the float64 answer, small fields and a 4096 x 4096 run;
   * the memory-capped grouping of ``lcs_strain`` gives the bits of one group;
   * the drop-in contract of ``LCS.strain``."""
@@ -155,6 +156,87 @@ def test_batch_equals_single_calls_and_optional_planes(eng, dtype, cast):
         eng.strain(xs, ys, lat, dlat, dlon, want=("s1", "s3"))
     with pytest.raises(ValueError):
         eng.strain(xs[:, :4], ys[:, :4], lat[:4], dlat, dlon)      # fewer than 5 rows
+
+
+# ------------------------------------------------------------------------------------------ one gradient core
+# rows: the stencil minimum; a row that is both "first two" and "last two"; one row past the 16-row tile; one past the 20-row
+# strip of the marching kernel; two ragged tiles.  widths: narrower than the halo wrap; around the 64-column tile; one even width
+# past the 124 columns a marching wave writes and one beyond it.
+CORE_ROWS = (5, 6, 17, 21, 37)
+CORE_WIDTHS = (5, 63, 64, 65, 126, 130)
+
+
+def _sigma_route_name(call, dtype, cast=True, march=None):
+    """The name tests/kernel_routes.py gives the sigma route of this call, dtype and ``set_sigma_march`` setting."""
+    from tests import kernel_routes as KR
+    setters = {} if march is None else {"set_sigma_march": march}
+    names = [n for n, r in KR.ROUTES.items() if n.startswith("sigma") and r["call"] == call and r["dtype"] == np.dtype(dtype).name
+             and r["setters"] == setters and (r["dtype"] == "float32" or r["fd_fp32_cast"] == cast)]
+    assert len(names) == 1, names
+    return names[0]
+
+
+def test_sigma_and_strain_share_one_gradient_core(eng):
+    """What follows from sigma.hip and strain.hip taking the six derivatives and the Gram eigenvalue from one header, bit for bit
+    (``equal_nan``), on smooth random perturbations of seed grids that reach within half a cell of both poles, and on one with a
+    NaN departure point in the corner of a tile:
+
+      * float64, both values of ``fd_fp32_cast``: ``strain``'s s1 is ``sigma(tensor_layout="physical")`` and plane 0 of
+        ``sigma_batch``; plane 1 of a two-plane batch is the single call on that plane, for ``sigma_batch`` and for ``strain``;
+      * float32, every width: batched ``strain`` is the single calls, ``want=("s1",)`` gives the full call's s1;
+      * float32, even widths from 64: the marching kernel is the LDS-tile kernel in both layouts, and ``sigma_batch`` is ``sigma``
+        plane by plane under both;
+      * every call reports the kernel ``KERNELS`` and the route table name."""
+    eq = lambda a, b: np.array_equal(_np(a), _np(b), equal_nan=True)
+    f32 = np.float32
+    try:
+        for ny, nx, nan in [(ny, nx, False) for ny in CORE_ROWS for nx in CORE_WIDTHS] + [(21, 130, True)]:
+            x, y, lat, lon = S.perturbed_seed_grid(ny, nx, seed=1000 * ny + nx, lat_edge=89.0)
+            x2, y2, _, _ = S.perturbed_seed_grid(ny, nx, seed=1000 * ny + nx + 1, lat_edge=89.0)
+            dlat, dlon = float(lat[1] - lat[0]), float(lon[1] - lon[0])
+            assert 90.0 - lat[-1] < 0.5 * dlat and lat[0] + 90.0 < 0.5 * dlat
+            if nan:
+                x[16, 64] = np.nan          # first row and first column of a tile: its stencil arms reach into three others
+            xs, ys = np.stack([x, x2]), np.stack([y, y2])
+            at = f"{ny} x {nx}" + (" with a NaN" if nan else "")
+            # ---- float64
+            for cast in (True, False):
+                kw = dict(fd_fp32_cast=cast)
+                st = eng.strain(x, y, lat, dlat, dlon, **kw)
+                assert eng.last_strain_kernel() == KERNELS[(np.float64, cast)]
+                assert bool(np.isnan(_np(st["s1"])).any()) == nan, at
+                sg = eng.sigma(x, y, lat, dlat, dlon, tensor_layout="physical", **kw)
+                assert eng.last_sigma_kernel() == _sigma_route_name("sigma", np.float64, cast)
+                sb = eng.sigma_batch(xs, ys, lat, dlat, dlon, tensor_layout="physical", **kw)
+                assert eng.last_sigma_kernel() == _sigma_route_name("batch", np.float64, cast)
+                assert eq(st["s1"], sg) and eq(st["s1"], sb[0]), (at, cast)
+                assert eq(sb[1], eng.sigma(x2, y2, lat, dlat, dlon, tensor_layout="physical", **kw)), (at, cast)
+                stb, st2 = eng.strain(xs, ys, lat, dlat, dlon, **kw), eng.strain(x2, y2, lat, dlat, dlon, **kw)
+                assert all(eq(stb[k][0], st[k]) and eq(stb[k][1], st2[k]) for k in PLANES), (at, cast)
+            # ---- float32
+            lat32, planes32 = lat.astype(f32), [(x.astype(f32), y.astype(f32)), (x2.astype(f32), y2.astype(f32))]
+            xs32, ys32 = xs.astype(f32), ys.astype(f32)
+            stb = eng.strain(xs32, ys32, lat32, dlat, dlon)
+            assert eng.last_strain_kernel() == KERNELS[(f32, True)]
+            for m, (xm, ym) in enumerate(planes32):
+                one = eng.strain(xm, ym, lat32, dlat, dlon)
+                only = eng.strain(xm, ym, lat32, dlat, dlon, want=("s1",))
+                assert eng.last_strain_kernel() == KERNELS[(f32, True)]
+                assert all(eq(stb[k][m], one[k]) for k in PLANES) and set(only) == {"s1"} and eq(only["s1"], one["s1"]), (at, m)
+            if nx % 2 or nx < 64:
+                continue
+            for layout in ("reference", "physical"):
+                sg = {}
+                for march in (1, 0):
+                    eng.set_sigma_march(march)
+                    sg[march] = [eng.sigma(xm, ym, lat32, dlat, dlon, tensor_layout=layout) for xm, ym in planes32]
+                    assert eng.last_sigma_kernel() == _sigma_route_name("sigma", f32, march=march)
+                    sb = eng.sigma_batch(xs32, ys32, lat32, dlat, dlon, tensor_layout=layout)
+                    assert eng.last_sigma_kernel() == _sigma_route_name("batch", f32, march=march)
+                    assert eq(sb[0], sg[march][0]) and eq(sb[1], sg[march][1]), (at, layout, march)
+                assert eq(sg[1][0], sg[0][0]) and eq(sg[1][1], sg[0][1]), (at, layout)
+    finally:
+        eng.set_sigma_march(-1)
 
 
 # ------------------------------------------------------------------------------------------ float32
