@@ -213,7 +213,11 @@ int lc_ctx_last_advect_launches(const lc_ctx *ctx);
 const char *lc_ctx_last_sigma_kernel(const lc_ctx *ctx);
 /* The kernel the last lc_field_pack launched for its first stage (interleave / spline prefilter; "" before any): e.g.
  * "pack_fused_kernel", "prefilter_fir_kernel", "prefilter_fused_stream_kernel<double>" (float64 order 3, both axes of 64
- * nodes or more: both prefilter sweeps in one pass), "prefilter_cols_stream_kernel + prefilter_rows_stream_kernel".  The pads
+ * nodes or more: both prefilter sweeps in one pass), "prefilter_cols_stream_kernel + prefilter_rows_stream_kernel".  Every
+ * path names the kernels it launched: the split sweeps as "<latitude kernel> + <longitude kernel>" (prefilter_cols_kernel /
+ * prefilter_cols_stream_kernel, then prefilter_rows_kernel / prefilter_rows_lds_kernel -- lines of 64 nodes or more outside
+ * the streaming form -- / prefilter_rows_stream_kernel), LCS_FIR_PREFILTER=2 with ext_dev as "prefilter_fir_kernel (img + ext)"
+ * (the fused-level image as a second filtered image), orders 2, 4, 5 as "pack_interior_kernel + prefilter_general_kernel".  The pads
  * / fused-level pass that follows is not named.  Same lifetime as lc_ctx_last_advect_kernel's string. */
 const char *lc_ctx_last_pack_kernel(const lc_ctx *ctx);
 /* The kernel the context's last lc_tracer_sample launched ("" before any): "tracer_kernel<float | double, interp_order>".

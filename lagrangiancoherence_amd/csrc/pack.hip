@@ -1085,7 +1085,7 @@ int pack_impl(lc_ctx *ctx, const TIN *u, const TIN *v, int nt, int ny, int nx, i
             const dim3 grid((nx + FT - 1) / FT, (ny + FT - 1) / FT, nt * (both ? 2 : 1));
             hipLaunchKernelGGL(prefilter_fir_kernel, grid, dim3(256), 0, ctx->stream, u, v, packed, both ? ext : nullptr, nt, ny, nx,
                                cubic_fir_taps());
-            ctx->last_pack_kernel = "prefilter_fir_kernel";
+            ctx->last_pack_kernel = both ? "prefilter_fir_kernel (img + ext)" : "prefilter_fir_kernel";
             if (ext && nt >= 2 && !both) {  // ext = 2 img[t] - img[t+1] from the finished coefficients (pads rewritten, same values)
                 const int nchunk = (nt + PACK_LV - 1) / PACK_LV;
                 hipLaunchKernelGGL(pads_ext_kernel<T>, dim3((nx + LC_PAD + 255) / 256, ny + LC_PAD < 65535 ? ny + LC_PAD : 65535, nchunk < 65535 ? nchunk : 65535), dim3(threads), 0, ctx->stream, packed, ext, nt, ny, nx);
@@ -1123,6 +1123,7 @@ int pack_impl(lc_ctx *ctx, const TIN *u, const TIN *v, int nt, int ny, int nx, i
             ctx->last_pack_kernel = (cols_stream && stream && nx >= RS_RING) ? "prefilter_cols_stream_kernel + prefilter_rows_stream_kernel"
                                     : cols_stream                            ? "prefilter_cols_stream_kernel + prefilter_rows_kernel"
                                     : (stream && nx >= RS_RING)              ? "prefilter_cols_kernel + prefilter_rows_stream_kernel"
+                                    : nx >= PR_CHUNK                         ? "prefilter_cols_kernel + prefilter_rows_lds_kernel"
                                                                              : "prefilter_cols_kernel + prefilter_rows_kernel";
         if (fused) {
         } else if (stream && nx >= RS_RING) {

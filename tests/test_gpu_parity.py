@@ -813,7 +813,7 @@ def test_lds_tile_and_direct_gather_kernels_agree(eng, order, monkeypatch):
 
 
 @pytest.mark.parametrize("dtype,tol", [(np.float64, 5e-13), (np.float32, 4e-5)])
-def test_prefilter_wide_rows_lds_kernel(eng, O, dtype, tol):
+def test_prefilter_wide_rows_lds_kernel(eng, O, monkeypatch, dtype, tol):
     # nx >= 64 takes the LDS-chunked longitude sweep (3 chunks here, ragged last chunk, ragged row block)
     u, v, lat, lon = _rand_field(61, nt=2, ny=37, nx=150, dtype=dtype, scale=1.0)
     f = eng.prepare_field(u, v, lat, lon, 3)
@@ -822,6 +822,24 @@ def test_prefilter_wide_rows_lds_kernel(eng, O, dtype, tol):
     for t in range(nt):
         np.testing.assert_allclose(img[t, 1:ny + 1, 1:nx + 1, 0], O.spline_prefilter_mirror(u[t]), atol=tol)
         np.testing.assert_allclose(img[t, 1:ny + 1, 1:nx + 1, 1], O.spline_prefilter_mirror(v[t]), atol=tol)
+    # (in the default configuration that shape goes to prefilter_fir_kernel in float32 and to prefilter_rows_stream_kernel in
+    # float64.)  What does reach prefilter_rows_lds_kernel, by name: float32 on a grid too small for the FIR (12 rows), float64
+    # with the streaming forms off; tests/pack_routes.py lists every such route
+    from lagrangiancoherence_amd.engine import Engine
+    if dtype == np.float32:
+        e, ny = eng, 12
+    else:
+        monkeypatch.setenv("LCS_FIR_PREFILTER", "0")
+        e = Engine(0)
+        monkeypatch.undo()
+    f = e.prepare_field(u[:, :ny], v[:, :ny], lat[:ny], lon, 3)
+    assert e.last_pack_kernel() == "prefilter_cols_kernel + prefilter_rows_lds_kernel", e.last_pack_kernel()
+    img = _np(f.cub).reshape(nt, ny + 3, nx + 3, 2).astype(np.float64)
+    for t in range(nt):
+        np.testing.assert_allclose(img[t, 1:ny + 1, 1:nx + 1, 0], O.spline_prefilter_mirror(u[t, :ny]), atol=tol)
+        np.testing.assert_allclose(img[t, 1:ny + 1, 1:nx + 1, 1], O.spline_prefilter_mirror(v[t, :ny]), atol=tol)
+    if e is not eng:
+        e.close()
 
 
 def test_one_pass_prefilter_matches_the_recursive_sweeps(eng, O, monkeypatch):
@@ -836,7 +854,7 @@ def test_one_pass_prefilter_matches_the_recursive_sweeps(eng, O, monkeypatch):
     a = eng.prepare_field(u, v, lat, lon, 3)
     assert eng.last_pack_kernel() == "prefilter_fir_kernel", eng.last_pack_kernel()
     b = eng0.prepare_field(u, v, lat, lon, 3)
-    assert eng0.last_pack_kernel() == "prefilter_cols_kernel + prefilter_rows_kernel", eng0.last_pack_kernel()
+    assert eng0.last_pack_kernel() == "prefilter_cols_kernel + prefilter_rows_lds_kernel", eng0.last_pack_kernel()   # 150 nodes per row: the LDS row sweep
     scale = float(np.abs(u).max())
     for name in ("cub", "ext"):
         x, y = _np(getattr(a, name)).astype(np.float64), _np(getattr(b, name)).astype(np.float64)
@@ -876,7 +894,7 @@ def test_float64_streaming_prefilter_matches_the_two_march_sweeps_and_scipy(eng,
     if os.environ.get("LCS_FUSED_PREFILTER", "1") != "0":
         assert eng.last_pack_kernel() == ("prefilter_fused_stream_kernel<double>" if ny >= 64 and nx >= 64 else f"{cols} + {rows}"), eng.last_pack_kernel()
     b = eng0.prepare_field(u, v, lat, lon, 3)
-    assert eng0.last_pack_kernel() == "prefilter_cols_kernel + prefilter_rows_kernel", eng0.last_pack_kernel()
+    assert eng0.last_pack_kernel() == "prefilter_cols_kernel + " + ("prefilter_rows_lds_kernel" if nx >= 64 else "prefilter_rows_kernel"), eng0.last_pack_kernel()
     scale = float(np.abs(u).max())
     for name in ("cub", "ext"):
         x, y = _np(getattr(a, name)), _np(getattr(b, name))
