@@ -5,8 +5,9 @@
 //
 // dgeev on a symmetric 2x2 is closed form (no balancing, trivial Hessenberg reduction, dlahqr on one
 // 2x2 block): the Ahues-Tisseur deflation test, else one dlanv2 standardisation (two branches), then
-// dtrevc on the resulting triangle and dgeev's unit 2-norm scaling.  Restated line by line below and
-// pinned against numpy.linalg.eig itself (tests/test_ridges.py: eigenvalues bit-exact, vectors 3e-16).
+// dtrevc on the resulting triangle and dgeev's unit 2-norm scaling, all of it on the matrix dgeev has scaled into
+// [2^-459, 2^459] where its norm lies outside.  Restated line by line below and pinned against numpy.linalg.eig itself
+// (tests/test_ridges.py, tests/test_ridge_chain.py: eigenvalues bit-exact, vectors 3e-16).
 #include "lcs_common.h"
 
 namespace {
@@ -34,7 +35,8 @@ __device__ __forceinline__ void normalise(double &x, double &y) {
     y /= n;
 }
 
-__device__ Eig2 dgeev_sym2(double a, double b, double d) {
+// dgeev from dlahqr on: the matrix as dgeev hands it on, already scaled where it scales (dgeev_sym2)
+__device__ Eig2 dgeev_sym2_unscaled(double a, double b, double d) {
 #pragma clang fp contract(off)
     const double ulp = 2.220446049250313e-16;   // dlamch('P')
     const double safmin = 2.2250738585072014e-308;
@@ -120,6 +122,24 @@ __device__ Eig2 dgeev_sym2(double a, double b, double d) {
     r.v10 = c10;
     r.v01 = c01;
     r.v11 = c11;
+    return r;
+}
+
+// dgeev scales a matrix whose largest |element| lies outside [smlnum, bignum] = [2^-459, 2^459] (sqrt(safmin)/ulp and its
+// reciprocal) to that bound before anything else, and the eigenvalues back at the end: one dlascl multiplication each way at
+// these magnitudes (the factor back, anrm / bound, is exact: the bound is a power of two).  The vectors are not scaled back.  Hessians below
+// 6.7e-139 take this path: every test of dlahqr and dlanv2 then sees the scaled values.
+__device__ Eig2 dgeev_sym2(double a, double b, double d) {
+#pragma clang fp contract(off)
+    const double smlnum = 0x1p-459, bignum = 0x1p459;
+    const double anrm = fmax(fmax(fabs(a), fabs(b)), fabs(d));  // dlange('M')
+    const bool small = anrm > 0.0 && anrm < smlnum;
+    if (!small && !(anrm > bignum)) return dgeev_sym2_unscaled(a, b, d);
+    const double cscale = small ? smlnum : bignum;
+    const double up = cscale / anrm, down = anrm / cscale;
+    Eig2 r = dgeev_sym2_unscaled(a * up, b * up, d * up);
+    r.w0 *= down;
+    r.w1 *= down;
     return r;
 }
 

@@ -75,8 +75,28 @@ def dlanv2_sym(a, b, d):
       * otherwise one dlanv2 standardisation; T comes out diagonal so V = [[cs,-sn],[sn,cs]].
     dlanv2's other branch ("complex or real (almost) equal eigenvalues": z < 4*eps, i.e. |b| and |a-d|
     below ~1e-15 in ABSOLUTE terms) equalises the diagonal with one rotation and, b and c having equal
-    signs, reduces to triangular form with a second one; dtrevc then solves [[A,B],[0,D]]."""
+    signs, reduces to triangular form with a second one; dtrevc then solves [[A,B],[0,D]].
+    All of this acts on the matrix as dgeev has scaled it (below): at |H| < 6.7e-139 the tests above see other values."""
     a, b, d = (np.asarray(v, dtype=np.float64) for v in (a, b, d))
+    # dgeev itself, before any of the above: a matrix whose largest |element| lies outside [2^-459, 2^459]
+    # (sqrt(safmin)/ulp and its reciprocal) is scaled to that bound with one dlascl multiplication, and the
+    # eigenvalues are scaled back with a second one (its factor anrm / bound is exact: a power of two); the vectors are not.
+    anrm = np.maximum(np.maximum(np.abs(a), np.abs(b)), np.abs(d))
+    cscale = np.where(anrm < _DGEEV_SMLNUM, _DGEEV_SMLNUM, _DGEEV_BIGNUM)
+    scalea = ((anrm > 0) & (anrm < _DGEEV_SMLNUM)) | (anrm > _DGEEV_BIGNUM)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore", under="ignore"):
+        up = np.where(scalea, cscale / anrm, 1.0)
+        down = np.where(scalea, anrm / cscale, 1.0)
+        w0, w1, V = _dgeev_sym2_unscaled(np.where(scalea, a * up, a), np.where(scalea, b * up, b), np.where(scalea, d * up, d))
+        return np.where(scalea, w0 * down, w0), np.where(scalea, w1 * down, w1), V
+
+
+_DGEEV_SMLNUM = 2.0 ** -459                            # dgeev: sqrt(dlamch('S')) / dlamch('P')
+_DGEEV_BIGNUM = 2.0 ** 459
+
+
+def _dgeev_sym2_unscaled(a, b, d):
+    """dlanv2_sym without dgeev's scaling of the matrix: what follows it (dlahqr, dlanv2, dtrevc, the normalisation)."""
     ulp = np.finfo(np.float64).eps                     # dlamch('P')
     safmin = np.finfo(np.float64).tiny
     smlnum = safmin * (2.0 / ulp)                      # dlahqr: safmin*(nh/ulp), nh = 2

@@ -8,25 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import ridges_oracle as RO
-
-
-def _matrices(n=120000, seed=0):
-    rng = np.random.default_rng(seed)
-    a = rng.standard_normal(n) * 10.0 ** rng.integers(-20, 3, n)
-    b = rng.standard_normal(n) * 10.0 ** rng.integers(-22, 3, n)
-    d = rng.standard_normal(n) * 10.0 ** rng.integers(-20, 3, n)
-    a[:100] = d[:100]
-    b[100:200] = 0
-    a[200:300] = 0
-    d[300:400] = -a[300:400]
-    d[600:700] = 0
-    a[700:800] = 0
-    d[700:800] = 0
-    a[2000:3000] = d[2000:3000] * (1 + 1e-16 * rng.integers(-5, 5, 1000))
-    a[5000:60000] *= 1e-10      # realistic Hessian magnitudes (FTLE per metre^2)
-    b[5000:60000] *= 1e-10
-    d[5000:60000] *= 1e-10
-    return a, b, d
+from tests.ridge_chain import ridge_inputs as _matrices
 
 
 def test_closed_form_equals_numpy_linalg_eig():
