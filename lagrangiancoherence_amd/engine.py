@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 from dataclasses import dataclass
 
 import numpy as np
@@ -53,12 +54,47 @@ def common_dtype(*arrays) -> np.dtype:
     return np.dtype(np.float32) if dts == {np.dtype(np.float32)} else np.dtype(np.float64)
 
 
+def _smoothing_width(gauss_sigma) -> float:
+    """``gauss_sigma`` as a width: anything that is not a real number (None, a bool) is no smoothing, 0."""
+    return float(gauss_sigma) if isinstance(gauss_sigma, (float, int)) and not isinstance(gauss_sigma, bool) else 0.0
+
+
+def _check_grid(a, b, lat_f, lon_f, what: str):
+    """``(nt, ny_f, nx_f)`` of the planes ``a``, ``b`` of a ``what`` ('field', 'tracer'; ``b`` may be None), coordinates checked."""
+    if len(a.shape) != 3 or (b is not None and tuple(b.shape) != tuple(a.shape)):
+        raise ValueError("u and v must both be (time, latitude, longitude)" if what == "field" else
+                         "tracers must be (time, latitude, longitude), both of one shape")
+    nt, ny_f, nx_f = (int(s) for s in a.shape)
+    if lat_f.shape != (ny_f,) or lon_f.shape != (nx_f,):
+        raise ValueError(f"coordinate lengths do not match the {what}")
+    if not (np.all(np.diff(lat_f) > 0) and np.all(np.diff(lon_f) > 0)):
+        raise ValueError("latitude and longitude must be ascending (sort first)")
+    return nt, ny_f, nx_f
+
+
+def _check_order(thing, interp_order):
+    """A field or tracer serves the order it was prepared for, and order 1."""
+    if interp_order != 1 and thing.order != interp_order:
+        raise ValueError(f"{'tracer' if isinstance(thing, PackedTracer) else 'field'} was prepared for interp_order={thing.order}")
+
+
+def _on_grid(cls, lat_f, lon_f, dtype, nt, ny_f, nx_f, **buffers):
+    """``cls`` -- :class:`PackedField` or :class:`PackedTracer`: the one place either is built -- of these buffers on this
+    grid: the coordinate extremes in the arithmetic dtype (what .min() / .max() give numpy), and the version stamps of
+    whatever planes a field is given to borrow, so no field exists that :meth:`Engine._check_planes` does not cover."""
+    dtype = np.dtype(dtype)
+    la, lo = np.asarray(lat_f).astype(dtype), np.asarray(lon_f).astype(dtype)
+    for stamp, a, b in (("planes_version", "u", "v"), ("planes32_version", "u32", "v32")):
+        if buffers.get(a) is not None:
+            buffers[stamp] = (buffers[a]._version, buffers[b]._version)
+    return cls(nt=int(nt), ny_f=int(ny_f), nx_f=int(nx_f), lat_min=float(la[0]), lat_max=float(la[-1]), lon_min=float(lo[0]),
+               lon_max=float(lo[-1]), dtype=dtype, **buffers)
+
+
 @dataclass
 class PackedField:
-    """Gather-ready image(s) of a wind time series, resident on the device."""
-    lin: "torch.Tensor | None"     # order-1 image; None when the raw planes ``u``, ``v`` below serve as the order-1 source
-    cub: "torch.Tensor | None"     # B-spline coefficient image of order ``order`` (2..5), None for order 1
-    ext: "torch.Tensor | None"     # 2*img[t]-img[t+1] of the image matching interp_order (fused SETTLS sample)
+    """Gather-ready image(s) of a wind time series, resident on the device.  Built by :meth:`on_grid`."""
+    on_grid = classmethod(_on_grid)
     nt: int
     ny_f: int
     nx_f: int
@@ -67,6 +103,9 @@ class PackedField:
     lon_min: float
     lon_max: float
     dtype: np.dtype
+    lin: "torch.Tensor | None" = None     # order-1 image; None when the raw planes ``u``, ``v`` below serve as the order-1 source
+    cub: "torch.Tensor | None" = None     # B-spline coefficient image of order ``order`` (2..5), None for order 1
+    ext: "torch.Tensor | None" = None     # 2*img[t]-img[t+1] of the image matching interp_order (fused SETTLS sample)
     wind_f32: bool = False          # float32 wind on float64 coordinates: numpy's promotion rules in lc_advect
     order: int = 1                  # interpolation order the field was prepared for (order 1 is always available)
     fuse_raw: bool = False          # float64 at order 1: fused levels with NO packed image (2 F[t] - F[t+1] formed from u, v in the kernels)
@@ -83,7 +122,8 @@ class PackedField:
 @dataclass
 class PackedTracer:
     """One or two scalar tracers on a wind grid, ready for ``lc_tracer_sample``: the (C1, C2) pair in the (u, v) slots of
-    ``lc_field_pack``'s layout (one tracer is the pair (C, C))."""
+    ``lc_field_pack``'s layout (one tracer is the pair (C, C)).  Built by :meth:`on_grid`."""
+    on_grid = classmethod(_on_grid)
     lin: "torch.Tensor | None"     # order-1 image: float32 at order 1 only (float64 samples the planes)
     cub: "torch.Tensor | None"     # B-spline coefficient image of order ``order`` (2..5), None for order 1
     c1: "torch.Tensor"             # the planes (nt, ny_f, nx_f): the order-1 source of the pole rows, and of every row in float64
@@ -98,6 +138,65 @@ class PackedTracer:
     lon_max: float
     dtype: np.dtype
     order: int = 1
+
+
+# What Engine.prepare_field does for one field (field_plan).  upload: the dtype in which the planes go to the device; images:
+# which of lin, lin32, cub, ext exist -> their length in time levels; packs: the lc_field_pack calls in order, each (LC dtype
+# code, order, image or None, ext passed); planes: the PackedField attributes that keep the uploaded planes -- (u, v), (u32, v32)
+# or (); wind_f32, fuse_raw, order: the field's; refusal: the ValueError of a combination that cannot be served, or None.
+FieldPlan = namedtuple("FieldPlan", "upload images packs planes wind_f32 fuse_raw order refusal")
+
+
+def field_plan(dtype, wind_f32, interp_order, nt, fuse_levels, lin_image, ext_image, ext_image_f64, ext_image_f64_o3) -> FieldPlan:
+    """:meth:`Engine.prepare_field`'s decisions as a pure function of its options (its docstring says what they mean);
+    ``wind_f32``: float32 wind on float64 coordinates; the last two are ``Engine.EXT_IMAGE_F64`` and ``EXT_IMAGE_F64_O3``."""
+    f32 = np.dtype(np.float32)
+    dtype, order = np.dtype(dtype), int(interp_order)
+    if wind_f32 and lin_image is None and order in (1, 3):
+        # The wind stays float32.  Order 1: its order-1 image as lc_field_pack builds it for float32 fields, widened node by
+        # node inside the kernels (LC_F64_WIND_F32_LIN32: the bits of the float64 images, half the bytes, no conversion pass;
+        # LCS/trajectory.py:86-87,110-112, SURVEY Q10).  Order 3: scipy's spline coefficients of a float32 field are float64,
+        # so the coefficient image is packed in float64 STRAIGHT from the float32 planes (LC_F64_WIND_F32), which also serve
+        # the pole rows.  The float64 planes are made when a call needs them (Engine._planes64).
+        image, code = ("lin32", _capi.LC_F32) if order == 1 else ("cub", _capi.LC_F64_WIND_F32)
+        return FieldPlan(f32, {image: nt}, ((code, order, image, False),), ("u32", "v32"), True, False, order, None)
+    # general orders and a float32 wind's float64 copy: generic direct kernel, two-sample form
+    fuse = (fuse_levels is None or bool(fuse_levels)) and nt >= 2 and not wind_f32 and order in (1, 3)
+    if lin_image is None:
+        lin_image = dtype == f32 and order == 1
+    # float64 with fused levels and no image to read them from: the kernels form 2 F[t] - F[t+1] themselves
+    fuse_raw = fuse and dtype != f32 and (order == 3 or not lin_image) and \
+        not ((ext_image_f64 if order == 1 else ext_image_f64_o3) if ext_image is None else ext_image)
+    ext = fuse and not fuse_raw
+    refusal = "float32 at interp_order=1 samples the order-1 image: lin_image cannot be False" \
+        if dtype == f32 and order == 1 and not lin_image else None
+    images = {k: n for k, n, on in (("lin", nt, lin_image), ("cub", nt, order != 1), ("ext", nt - 1, ext)) if on}
+    packs = [(_NP2LC[dtype], 1, "lin" if lin_image else None, order == 1 and ext)] if lin_image or (order == 1 and ext) else []
+    packs += [(_NP2LC[dtype], order, "cub", ext)] if order != 1 else []
+    return FieldPlan(dtype, images, tuple(packs), () if lin_image else ("u", "v"), bool(wind_f32), fuse_raw, order, refusal)
+
+
+# Where one advect call reads the wind from (call_source).  dtype: the call's LC dtype code; buffers: lc_advect_args pointer
+# field -> the PackedField attribute it points at; planes64: the call reads the float64 planes of a field that may keep only
+# float32 ones (Engine._planes64 first); lin: it reads the float32 order-1 image (Engine._ensure_lin builds a missing one).
+CallSource = namedtuple("CallSource", "dtype buffers fuse_levels_raw planes64 lin")
+
+
+def call_source(field: PackedField, interp_order, xmode) -> CallSource:
+    """The source of a call on ``field`` at ``interp_order`` under the x boundary ``xmode``.  A float32 wind kept float32
+    on float64 coordinates is read as it is (no float64 copy of the wind comes into being), except under the reference's
+    outer-product clamp, which only the general form serves."""
+    order = int(interp_order)
+    if field.u32 is not None and xmode != _capi.LC_X_CLAMP_REFERENCE_OUTER:
+        if field.lin32 is None and order == 3 == field.order:     # float64 coefficients, the float32 planes for the pole rows
+            return CallSource(_capi.LC_F64_WIND_F32_LIN32, {"packed_cub": "cub", "u_raw": "u32", "v_raw": "v32"}, 0, False, False)
+        if field.lin32 is not None and order == 1:
+            return CallSource(_capi.LC_F64_WIND_F32_LIN32, {"packed_lin": "lin32"}, 0, False, False)
+    same = field.order == order
+    buffers = {"packed_lin": "lin", "u_raw": "u", "v_raw": "v", **({"packed_cub": "cub"} if order != 1 else {}),
+               **({"packed_ext": "ext"} if same else {})}
+    return CallSource(_capi.LC_F64_WIND_F32 if field.wind_f32 else _NP2LC[field.dtype], buffers, int(bool(field.fuse_raw and same)),
+                      field.u32 is not None, field.dtype == np.dtype(np.float32) and order == 1)
 
 
 class Engine:
@@ -368,78 +467,29 @@ class Engine:
         if interp_order not in (1, 2, 3, 4, 5):
             raise ValueError(f"interp_order {interp_order} unsupported (scipy's spline orders 1..5; "
                              "0 fails in the reference too, LCS/tools.py:24-30)")
-        lat_f = np.asarray(lat_f)
-        lon_f = np.asarray(lon_f)
+        lat_f, lon_f = np.asarray(lat_f), np.asarray(lon_f)
         dtype = np.dtype(dtype or common_dtype(u, v, lat_f, lon_f))
-        f32 = np.dtype(np.float32)
-        wind_f32 = dtype == np.dtype(np.float64) and common_dtype(u, v) == f32 and common_dtype(lat_f, lon_f) != f32
-        if tuple(u.shape) != tuple(v.shape) or len(u.shape) != 3:
-            raise ValueError("u and v must both be (time, latitude, longitude)")
-        nt, ny_f, nx_f = (int(s) for s in u.shape)
-        if lat_f.shape != (ny_f,) or lon_f.shape != (nx_f,):
-            raise ValueError("coordinate lengths do not match the field")
-        if not (np.all(np.diff(lat_f) > 0) and np.all(np.diff(lon_f) > 0)):
-            raise ValueError("latitude and longitude must be ascending (sort first)")
-        n = self.lib.lc_packed_elems(nt, ny_f, nx_f)
+        wind_f32 = dtype == np.float64 and common_dtype(u, v) == np.float32 and common_dtype(lat_f, lon_f) != np.float32
+        nt, ny_f, nx_f = _check_grid(u, v, lat_f, lon_f, "field")
+        plan = field_plan(dtype, wind_f32, interp_order, nt, fuse_levels, lin_image, ext_image, self.EXT_IMAGE_F64, self.EXT_IMAGE_F64_O3)
+        if plan.refusal:
+            raise ValueError(plan.refusal)
         self._use_current_stream()
-        if wind_f32 and interp_order == 1 and lin_image is None:
-            # float32 wind on float64 coordinates at order 1: the wind stays float32 -- its order-1 image as lc_field_pack builds
-            # it for float32 fields, widened node by node inside the kernels (LC_F64_WIND_F32_LIN32: the bits of the float64
-            # images, half the bytes, no conversion pass; LCS/trajectory.py:86-87,110-112 with SURVEY Q10).  The float64 planes
-            # are made when a call needs them (_planes64: another order, the reference's outer-product clamp, sample()).
-            u32, v32 = self.to_device(u, f32), self.to_device(v, f32)
-            lin32 = self._empty((n,), f32)
-            _capi.check(self.lib.lc_field_pack(self.ctx, self._ptr(u32), self._ptr(v32), _capi.LC_F32, nt, ny_f, nx_f, 1,
-                                               self._ptr(lin32), None), self.lib)
-            la, lo = lat_f.astype(dtype), lon_f.astype(dtype)
-            return PackedField(None, None, None, nt, ny_f, nx_f, float(la[0]), float(la[-1]), float(lo[0]), float(lo[-1]), dtype,
-                               True, 1, False, None, None, None, lin32, u32, v32, (u32._version, v32._version))
-        if wind_f32 and interp_order == 3 and lin_image is None:
-            # ... and at order 3 (the reference's default): scipy's spline coefficients of a float32 field are float64
-            # (spline_filter(output=float64) inside map_coordinates), so the coefficient image is packed in float64 STRAIGHT from
-            # the float32 planes (lc_field_pack(LC_F64_WIND_F32): no float64 copy of the wind), and the planes themselves are the
-            # order-1 source of the pole rows.
-            u32, v32 = self.to_device(u, f32), self.to_device(v, f32)
-            cub = self._empty((n,), dtype)
-            _capi.check(self.lib.lc_field_pack(self.ctx, self._ptr(u32), self._ptr(v32), _capi.LC_F64_WIND_F32, nt, ny_f, nx_f, 3,
-                                               self._ptr(cub), None), self.lib)
-            la, lo = lat_f.astype(dtype), lon_f.astype(dtype)
-            return PackedField(None, cub, None, nt, ny_f, nx_f, float(la[0]), float(la[-1]), float(lo[0]), float(lo[-1]), dtype,
-                               True, 3, False, None, None, None, None, u32, v32, (u32._version, v32._version))
-        ud = self.to_device(u, dtype)
-        vd = self.to_device(v, dtype)
-        if fuse_levels is None:
-            fuse_levels = True
-        if wind_f32 or interp_order in (2, 4, 5):   # general orders: generic direct kernel, two-sample form
-            fuse_levels = False
-        ext = None
-        if lin_image is None:
-            lin_image = dtype == f32 and interp_order == 1
-        fuse_raw = False
-        if fuse_levels and nt >= 2 and dtype != f32 and interp_order == 1 and not lin_image:
-            fuse_raw = not (self.EXT_IMAGE_F64 if ext_image is None else ext_image)
-        if fuse_levels and nt >= 2 and dtype != f32 and interp_order == 3:
-            fuse_raw = not (self.EXT_IMAGE_F64_O3 if ext_image is None else ext_image)
-        if fuse_levels and nt >= 2 and not fuse_raw:
-            ext = self._empty((self.lib.lc_packed_elems(nt - 1, ny_f, nx_f),), dtype)
-        if dtype == f32 and interp_order == 1 and not lin_image:
-            raise ValueError("float32 at interp_order=1 samples the order-1 image: lin_image cannot be False")
-        lin = self._empty((n,), dtype) if lin_image else None
-        if lin is not None or (interp_order == 1 and ext is not None):
-            _capi.check(self.lib.lc_field_pack(self.ctx, self._ptr(ud), self._ptr(vd), _NP2LC[dtype], nt, ny_f, nx_f, 1,
-                                               self._ptr(lin), self._ptr(ext if interp_order == 1 else None)), self.lib)
-        cub = None
-        if interp_order != 1:
-            cub = self._empty((n,), dtype)
-            _capi.check(self.lib.lc_field_pack(self.ctx, self._ptr(ud), self._ptr(vd), _NP2LC[dtype], nt, ny_f, nx_f,
-                                               int(interp_order), self._ptr(cub), self._ptr(ext)), self.lib)
-        # coordinate extremes in the arithmetic dtype (what .min()/.max() give numpy)
-        la = lat_f.astype(dtype)
-        lo = lon_f.astype(dtype)
-        keep = lin is None
-        return PackedField(lin, cub, ext, nt, ny_f, nx_f, float(la[0]), float(la[-1]), float(lo[0]), float(lo[-1]), dtype,
-                           wind_f32, int(interp_order), fuse_raw, ud if keep else None, vd if keep else None,
-                           (ud._version, vd._version) if keep else None)
+        field, ud, vd = self._planned_field(plan, u, v, lat_f, lon_f, dtype, nt, ny_f, nx_f)
+        for code, order, image, with_ext in plan.packs:
+            _capi.check(self.lib.lc_field_pack(self.ctx, self._ptr(ud), self._ptr(vd), code, nt, ny_f, nx_f, order,
+                                               self._ptr(getattr(field, image) if image else None),
+                                               self._ptr(field.ext if with_ext else None)), self.lib)
+        return field
+
+    def _planned_field(self, plan: FieldPlan, u, v, lat_f, lon_f, dtype, nt, ny_f, nx_f):
+        """``(field, u, v)``: the planes on the device and the field of ``plan`` with its images allocated, not yet packed."""
+        ud, vd = self.to_device(u, plan.upload), self.to_device(v, plan.upload)
+        images = {k: self._empty((self.lib.lc_packed_elems(levels, ny_f, nx_f),), np.float32 if k == "lin32" else dtype)
+                  for k, levels in plan.images.items()}
+        field = PackedField.on_grid(lat_f, lon_f, dtype, nt, ny_f, nx_f, wind_f32=plan.wind_f32, order=plan.order,
+                                    fuse_raw=plan.fuse_raw, **images, **dict(zip(plan.planes, (ud, vd))))
+        return field, ud, vd
 
     # ------------------------------------------------------------------ global pre-processing (LCS.py:105-118)
     def regrid(self, u, lat, lon, lats, lons):
@@ -497,8 +547,7 @@ class Engine:
 
         ``halo=(n_lo, n_hi)``: return ``(n_lo + ny + n_hi, nx)`` buffers with the results in the middle
         rows, so a row-sharded caller can receive its neighbours' rows in place (sharded.py)."""
-        if interp_order != 1 and field.order != interp_order:
-            raise ValueError(f"field was prepared for interp_order={field.order}")
+        _check_order(field, interp_order)
         dtype = field.dtype
         slat = self.to_device(seed_lat, dtype)
         slon = self.to_device(seed_lon, dtype)
@@ -528,23 +577,19 @@ class Engine:
             for buf in (x_buf, y_buf):
                 buf[:n_lo].fill_(float("nan"))
                 buf[n_lo + ny:].fill_(float("nan"))
-        tx = ty = None
-        if return_traj:
-            tx = self._empty((nsteps + 1, ny, nx), dtype)
-            ty = self._empty((nsteps + 1, ny, nx), dtype)
-        sx = sy = None
+        traj = (self._empty((nsteps + 1, ny, nx), dtype), self._empty((nsteps + 1, ny, nx), dtype)) if return_traj else None
         if start is not None:
-            sx, sy = (self.to_device(a, dtype) for a in start)
+            start = sx, sy = tuple(self.to_device(a, dtype) for a in start)
             if tuple(sx.shape) != (ny, nx) or tuple(sy.shape) != (ny, nx):
                 raise ValueError(f"start positions must be two ({ny}, {nx}) arrays")
         self._use_current_stream()
-        a = self._advect_args(field, interp_order, slat, ny, slon, nx, row0, ny_global, sx, sy, timestep, SETTLS_order,
-                              x_boundary_mode(cyclic_xboundary, noncyclic_clamp, whole),
-                              t0, nsteps, 1, 0, x, y, tx, ty)
+        a = self._advect_args(field, interp_order, slat, ny, slon, nx, timestep, SETTLS_order,
+                              x_boundary_mode(cyclic_xboundary, noncyclic_clamp, whole), row0=row0, ny_global=ny_global,
+                              start=start, t0=t0, nsteps=nsteps, out=(x, y), traj=traj)
         _capi.check(self.lib.lc_advect_ex(self.ctx, C.byref(a)), self.lib)
         if halo:
             x, y = x_buf, y_buf
-        return (x, y, tx, ty) if return_traj else (x, y)
+        return (x, y, *traj) if return_traj else (x, y)
 
     @staticmethod
     def pole_window(global_rows, ny: int, ny_global: int, order: int):
@@ -571,8 +616,7 @@ class Engine:
         One launch per level chunk covers every member (:meth:`set_level_chunk`); each member's result equals
         ``advect(t0=t0 + m * t0_stride, nsteps=nsteps)`` bit for bit.  ``start`` / ``out``: ``(n_members, ny, nx)``
         tensors to continue from / write into (may be the same)."""
-        if interp_order != 1 and field.order != interp_order:
-            raise ValueError(f"field was prepared for interp_order={field.order}")
+        _check_order(field, interp_order)
         if not cyclic_xboundary:
             raise ValueError("advect_batch: the reference's non-cyclic clamp is decided per member; call advect for each")
         dtype = field.dtype
@@ -587,48 +631,31 @@ class Engine:
         x, y = (chk(t, "out") for t in out) if out is not None else (self._empty((n, ny, nx), dtype), self._empty((n, ny, nx), dtype))
         sx, sy = (chk(t, "start") for t in start) if start is not None else (None, None)
         self._use_current_stream()
-        a = self._advect_args(field, interp_order, slat, ny, slon, nx, 0, ny, sx, sy, timestep, SETTLS_order,
-                              _capi.LC_X_CYCLIC, t0, nsteps, n, t0_stride, x, y, None, None)
+        a = self._advect_args(field, interp_order, slat, ny, slon, nx, timestep, SETTLS_order, _capi.LC_X_CYCLIC,
+                              start=(sx, sy), t0=t0, nsteps=nsteps, n_members=n, t0_stride=t0_stride, out=(x, y))
         _capi.check(self.lib.lc_advect_ex(self.ctx, C.byref(a)), self.lib)
         return x, y
 
-    def _advect_args(self, field, interp_order, slat, ny, slon, nx, row0, ny_global, sx, sy, timestep, K, xmode, t0, nsteps,
-                     n_members, t0_stride, x, y, tx, ty) -> "_capi.AdvectArgs":
-        """``lc_advect_args`` of one call: the field's images, and its raw planes as the order-1 source where it has no
-        lin image."""
-        p = lambda t: t.data_ptr() if t is not None else None
+    def _advect_args(self, field, interp_order, slat, ny, slon, nx, timestep, K, xmode, *, row0=0, ny_global=None, start=None,
+                     t0=0, nsteps, n_members=1, t0_stride=0, out, traj=None) -> "_capi.AdvectArgs":
+        """``lc_advect_args`` of one call on ``field``: the borrowed planes checked, what the call's source (:func:`call_source`)
+        needs made, then the structure, filled here and nowhere else.  ``start``, ``out``, ``traj``: ``(x, y)`` pairs of tensors."""
         self._check_planes(field)
-        if field.u32 is not None and field.lin32 is None and interp_order == 3 == field.order and xmode != _capi.LC_X_CLAMP_REFERENCE_OUTER:
-            # float32 wind on float64 coordinates at order 3: float64 coefficients, the float32 planes for the pole rows
-            return _capi.AdvectArgs(
-                struct_size=C.sizeof(_capi.AdvectArgs), packed_cub=p(field.cub), u_raw=p(field.u32), v_raw=p(field.v32),
-                dtype=_capi.LC_F64_WIND_F32_LIN32, nt=field.nt, ny_f=field.ny_f, nx_f=field.nx_f, lat_min=field.lat_min,
-                lat_max=field.lat_max, lon_min=field.lon_min, lon_max=field.lon_max, seed_lat_dev=p(slat), ny=int(ny),
-                seed_lon_dev=p(slon), nx=int(nx), row0=int(row0), ny_global=int(ny_global), x_start=p(sx), y_start=p(sy),
-                timestep=float(timestep), settls_order=int(K), interp_order=3, cyclic_x=int(xmode), t0=int(t0), nsteps=int(nsteps),
-                n_members=int(n_members), t0_stride=int(t0_stride), x_out=p(x), y_out=p(y), traj_x=p(tx), traj_y=p(ty), fuse_levels_raw=0)
-        if field.lin32 is not None and interp_order == 1 and xmode != _capi.LC_X_CLAMP_REFERENCE_OUTER:
-            # float32 wind on float64 coordinates, the wind kept float32 (prepare_field)
-            return _capi.AdvectArgs(
-                struct_size=C.sizeof(_capi.AdvectArgs), packed_lin=p(field.lin32), dtype=_capi.LC_F64_WIND_F32_LIN32, nt=field.nt,
-                ny_f=field.ny_f, nx_f=field.nx_f, lat_min=field.lat_min, lat_max=field.lat_max, lon_min=field.lon_min,
-                lon_max=field.lon_max, seed_lat_dev=p(slat), ny=int(ny), seed_lon_dev=p(slon), nx=int(nx), row0=int(row0),
-                ny_global=int(ny_global), x_start=p(sx), y_start=p(sy), timestep=float(timestep), settls_order=int(K),
-                interp_order=1, cyclic_x=int(xmode), t0=int(t0), nsteps=int(nsteps), n_members=int(n_members),
-                t0_stride=int(t0_stride), x_out=p(x), y_out=p(y), traj_x=p(tx), traj_y=p(ty), fuse_levels_raw=0)
-        dt = _capi.LC_F64_WIND_F32 if field.wind_f32 else _NP2LC[field.dtype]
-        self._planes64(field)
-        self._ensure_lin(field, interp_order)
+        src = call_source(field, interp_order, xmode)
+        if src.planes64:
+            self._planes64(field)
+        if src.lin:
+            self._ensure_lin(field, interp_order)
+        p = lambda t: t.data_ptr() if t is not None else None
+        (sx, sy), (tx, ty) = start or (None, None), traj or (None, None)
         return _capi.AdvectArgs(
-            struct_size=C.sizeof(_capi.AdvectArgs), packed_lin=p(field.lin),
-            packed_cub=p(field.cub if interp_order != 1 else None),
-            packed_ext=p(field.ext if field.order == interp_order else None), u_raw=p(field.u), v_raw=p(field.v),
-            dtype=dt, nt=field.nt, ny_f=field.ny_f, nx_f=field.nx_f, lat_min=field.lat_min, lat_max=field.lat_max,
+            struct_size=C.sizeof(_capi.AdvectArgs), **{arg: p(getattr(field, name)) for arg, name in src.buffers.items()},
+            dtype=src.dtype, nt=field.nt, ny_f=field.ny_f, nx_f=field.nx_f, lat_min=field.lat_min, lat_max=field.lat_max,
             lon_min=field.lon_min, lon_max=field.lon_max, seed_lat_dev=p(slat), ny=int(ny), seed_lon_dev=p(slon), nx=int(nx),
-            row0=int(row0), ny_global=int(ny_global), x_start=p(sx), y_start=p(sy), timestep=float(timestep),
-            settls_order=int(K), interp_order=int(interp_order), cyclic_x=int(xmode), t0=int(t0), nsteps=int(nsteps),
-            n_members=int(n_members), t0_stride=int(t0_stride), x_out=p(x), y_out=p(y), traj_x=p(tx), traj_y=p(ty),
-            fuse_levels_raw=int(bool(field.fuse_raw and interp_order == field.order)))
+            row0=int(row0), ny_global=int(ny if ny_global is None else ny_global), x_start=p(sx), y_start=p(sy),
+            timestep=float(timestep), settls_order=int(K), interp_order=int(interp_order), cyclic_x=int(xmode), t0=int(t0),
+            nsteps=int(nsteps), n_members=int(n_members), t0_stride=int(t0_stride), x_out=p(out[0]), y_out=p(out[1]),
+            traj_x=p(tx), traj_y=p(ty), fuse_levels_raw=src.fuse_levels_raw)
 
     def _planes64(self, field: PackedField):
         """A wind_f32 field prepared at order 1 keeps its wind float32; the float64 planes (the order-1 source of every other
@@ -640,25 +667,18 @@ class Engine:
     @staticmethod
     def _check_planes(field: PackedField):
         """The borrowed wind planes (``u`` / ``v``, and the float32 ``u32`` / ``v32`` of a float32 wind on float64 coordinates)
-        must not have been written in place since ``prepare_field``: the kernels read them live (pole rows, Euler samples)
-        next to images packed from their old values.  Called on EVERY path that builds a call's arguments."""
-        stale = (field.u is not None and field.planes_version is not None
-                 and (field.u._version, field.v._version) != field.planes_version) or \
-                (field.u32 is not None and field.planes32_version is not None
-                 and (field.u32._version, field.v32._version) != field.planes32_version)
-        if stale:
-            raise RuntimeError("the wind tensors given to prepare_field were modified in place afterwards: the field's packed "
-                               "images no longer match them (prepare the field again, or pass copies)")
+        must not have been written in place since ``prepare_field`` (a time loop refilling its buffers): the kernels read them
+        live (pole rows, Euler samples) next to images packed from their old values; refused by the tensors' version counters.  The first thing :meth:`_advect_args` and :meth:`sample` do."""
+        for a, b, stamp in ((field.u, field.v, field.planes_version), (field.u32, field.v32, field.planes32_version)):
+            if a is not None and stamp is not None and (a._version, b._version) != stamp:
+                raise RuntimeError("the wind tensors given to prepare_field were modified in place afterwards: the field's packed "
+                                   "images no longer match them (prepare the field again, or pass copies)")
 
     def _ensure_lin(self, field: PackedField, interp_order: int):
-        """The order-1 source of a call on ``field``, checked and -- where it is an image that does not exist yet -- built.
-
-        A float32 field prepared for another order and now used at order 1 ("order 1 is always available"): its kernels
-        read the order-1 image's 16-byte node pairs, so the image is packed here, once, and kept on the field (``advect``
-        and ``sample`` alike).  Everywhere else the raw planes ``field.u`` / ``field.v`` are the order-1 source; they are
-        BORROWED from the caller when ``prepare_field`` was handed device tensors, so an in-place write to them since
-        then (a time loop refilling its buffers) would silently change what the pole rows and the float64 Euler sample
-        read while the packed images still hold the old wind: refused here by the tensors' version counters."""
+        """The order-1 source of a call on ``field``, checked (:meth:`_check_planes`) and -- where it is an image that does not
+        exist yet -- built.  A float32 field prepared for another order and now used at order 1 ("order 1 is always
+        available"): its kernels read the order-1 image's 16-byte node pairs, so the image is packed here, once, and kept on
+        the field (``advect`` and ``sample`` alike).  Everywhere else the raw planes ``field.u`` / ``field.v`` are the source."""
         self._check_planes(field)
         if field.lin is None and field.dtype == np.dtype(np.float32) and interp_order == 1:
             field.lin = self._empty((self.lib.lc_packed_elems(field.nt, field.ny_f, field.nx_f),), field.dtype)
@@ -668,17 +688,15 @@ class Engine:
 
     def sample(self, field: PackedField, pos_x, pos_y, level=0, interp_order=1, row0=0, ny_global=None):
         """tools.xr_map_coordinates for (u, v) of one time level at positions (ny, nx) in degrees."""
-        if interp_order != 1 and field.order != interp_order:
-            raise ValueError(f"field was prepared for interp_order={field.order}")
+        _check_order(field, interp_order)
+        self._check_planes(field)
         self._planes64(field)
         self._ensure_lin(field, interp_order)
         dtype = field.dtype
-        px = self.to_device(pos_x, dtype)
-        py = self.to_device(pos_y, dtype)
+        px, py = self.to_device(pos_x, dtype), self.to_device(pos_y, dtype)
         ny, nx = (int(s) for s in px.shape)
         ny_global = ny if ny_global is None else int(ny_global)
-        ou = self._empty((ny, nx), dtype)
-        ov = self._empty((ny, nx), dtype)
+        ou, ov = self._empty((ny, nx), dtype), self._empty((ny, nx), dtype)
         self._use_current_stream()
         _capi.check(self.lib.lc_sample_raw(
             self.ctx, self._ptr(field.lin), self._ptr(field.cub if interp_order != 1 else None), self._ptr(field.u),
@@ -704,29 +722,17 @@ class Engine:
             raise ValueError(f"interp_order {interp_order} unsupported (scipy's spline orders 1..5)")
         lat_f, lon_f = np.asarray(lat_f), np.asarray(lon_f)
         dtype = np.dtype(dtype or common_dtype(c1, c2, lat_f, lon_f))
-        if len(c1.shape) != 3 or (c2 is not None and tuple(c2.shape) != tuple(c1.shape)):
-            raise ValueError("tracers must be (time, latitude, longitude), both of one shape")
-        nt, ny_f, nx_f = (int(s) for s in c1.shape)
-        if lat_f.shape != (ny_f,) or lon_f.shape != (nx_f,):
-            raise ValueError("coordinate lengths do not match the tracer")
-        if not (np.all(np.diff(lat_f) > 0) and np.all(np.diff(lon_f) > 0)):
-            raise ValueError("latitude and longitude must be ascending (sort first)")
+        nt, ny_f, nx_f = _check_grid(c1, c2, lat_f, lon_f, "tracer")
         d1 = self.to_device(c1, dtype)
         d2 = self.to_device(c2, dtype) if c2 is not None else d1
-        n = self.lib.lc_packed_elems(nt, ny_f, nx_f)
-        lin = cub = None
+        img = None
         self._use_current_stream()
-        if interp_order == 1 and dtype == np.dtype(np.float32):
-            lin = self._empty((n,), dtype)
-            _capi.check(self.lib.lc_field_pack(self.ctx, self._ptr(d1), self._ptr(d2), _capi.LC_F32, nt, ny_f, nx_f, 1,
-                                               self._ptr(lin), None), self.lib)
-        elif interp_order != 1:
-            cub = self._empty((n,), dtype)
+        if interp_order != 1 or dtype == np.dtype(np.float32):
+            img = self._empty((self.lib.lc_packed_elems(nt, ny_f, nx_f),), dtype)
             _capi.check(self.lib.lc_field_pack(self.ctx, self._ptr(d1), self._ptr(d2), _NP2LC[dtype], nt, ny_f, nx_f,
-                                               int(interp_order), self._ptr(cub), None), self.lib)
-        la, lo = lat_f.astype(dtype), lon_f.astype(dtype)
-        return PackedTracer(lin, cub, d1, d2, c2 is not None, nt, ny_f, nx_f, float(la[0]), float(la[-1]), float(lo[0]),
-                            float(lo[-1]), dtype, int(interp_order))
+                                               int(interp_order), self._ptr(img), None), self.lib)
+        return PackedTracer.on_grid(lat_f, lon_f, dtype, nt, ny_f, nx_f, c1=d1, c2=d2, two=c2 is not None, order=int(interp_order),
+                                    lin=img if interp_order == 1 else None, cub=img if interp_order != 1 else None)
 
     def sample_tracer(self, tracer: PackedTracer, traj_x, traj_y, level0=0, interp_order=1, row0=0, ny_global=None,
                       values=True, sums=None, mean_count=None):
@@ -734,8 +740,7 @@ class Engine:
         tracer's dtype): entry j at field level ``level0 + j``.  Returns ``(c1, c2)`` per-entry values (``values``; c2
         None for one tracer) and ``(mean1, mean2)`` (when ``mean_count`` is given: sum / mean_count).  ``sums``: float64
         ``(ntracers, ny, nx)`` running sums the entries are added to (carried between calls)."""
-        if interp_order != 1 and tracer.order != interp_order:
-            raise ValueError(f"tracer was prepared for interp_order={tracer.order}")
+        _check_order(tracer, interp_order)
         dtype = tracer.dtype
         want = getattr(self.torch, dtype.name)
         if traj_x.dtype != want or traj_y.dtype != want or tuple(traj_x.shape) != tuple(traj_y.shape) or traj_x.dim() != 3 \
@@ -784,8 +789,7 @@ class Engine:
         if (tracer.nt, tracer.ny_f, tracer.nx_f) != (field.nt, field.ny_f, field.nx_f) or \
                 (tracer.lat_min, tracer.lat_max, tracer.lon_min, tracer.lon_max) != (field.lat_min, field.lat_max, field.lon_min, field.lon_max):
             raise ValueError("the tracer must lie on the wind's grid and time levels")
-        if interp_order != 1 and tracer.order != interp_order:
-            raise ValueError(f"tracer was prepared for interp_order={tracer.order}")
+        _check_order(tracer, interp_order)
         torch = self.torch
         dtype = field.dtype
         nsteps = field.nt - 1 - t0 if nsteps is None else int(nsteps)
@@ -817,10 +821,10 @@ class Engine:
         s = 0
         while s < nsteps:
             k = min(chunk, nsteps - s)
-            start = (x, y) if s else (None, None)
             self._use_current_stream()
-            a = self._advect_args(field, interp_order, slat, ny, slon, nx, row0, ny_global, start[0], start[1], timestep,
-                                  SETTLS_order, xmode, t0 + s, k, 1, 0, x, y, ring_x[:k + 1], ring_y[:k + 1])
+            a = self._advect_args(field, interp_order, slat, ny, slon, nx, timestep, SETTLS_order, xmode, row0=row0,
+                                  ny_global=ny_global, start=(x, y) if s else None, t0=t0 + s, nsteps=k, out=(x, y),
+                                  traj=(ring_x[:k + 1], ring_y[:k + 1]))
             _capi.check(self.lib.lc_advect_ex(self.ctx, C.byref(a)), self.lib)
             first = 0 if s == 0 else 1
             last = s + k == nsteps
@@ -1009,19 +1013,14 @@ class Engine:
             res = self.advect(field, seed_lat, seed_lon, timestep, SETTLS_order, interp_order, cyclic_xboundary,
                               return_traj=return_traj, noncyclic_clamp=noncyclic_clamp)
             return (field, *res)
-        if tuple(u.shape) != tuple(v.shape) or len(u.shape) != 3 or lat_f.shape != (u.shape[1],) or lon_f.shape != (u.shape[2],):
-            raise ValueError("u and v must both be (time, latitude, longitude) with matching coordinates")
-        if not (np.all(np.diff(lat_f) > 0) and np.all(np.diff(lon_f) > 0)):
-            raise ValueError("latitude and longitude must be ascending (sort first)")
-        ny_f, nx_f = int(u.shape[1]), int(u.shape[2])
-        ud, vd = self.to_device(u, dtype), self.to_device(v, dtype)
+        nt, ny_f, nx_f = _check_grid(u, v, lat_f, lon_f, "field")
+        # prepare_field's plan, its one pack call made chunk by chunk (order 1: the ext image IS that pack, whatever ext_image)
+        plan = field_plan(dtype, False, interp_order, nt, True, None, ext_image if interp_order == 3 else True,
+                          self.EXT_IMAGE_F64, self.EXT_IMAGE_F64_O3)
+        (code, order, image, with_ext), = plan.packs
+        field, ud, vd = self._planned_field(plan, u, v, lat_f, lon_f, dtype, nt, ny_f, nx_f)
+        img, ext, no_ext = getattr(field, image) if image else None, field.ext if with_ext else None, plan.fuse_raw
         le = self.lib.lc_packed_elems(1, ny_f, nx_f)
-        cub = self._empty((le * nt,), dtype) if interp_order == 3 else None
-        no_ext = dtype != f32 and interp_order == 3 and not (self.EXT_IMAGE_F64_O3 if ext_image is None else ext_image)   # the kernels form it from cub (prepare_field)
-        ext = None if no_ext else self._empty((le * (nt - 1),), dtype)
-        la, lo = lat_f.astype(dtype), lon_f.astype(dtype)
-        field = PackedField(None, cub, ext, nt, ny_f, nx_f, float(la[0]), float(la[-1]), float(lo[0]), float(lo[-1]), dtype,
-                            False, int(interp_order), no_ext, ud, vd, (ud._version, vd._version))
         slat, slon = self.to_device(seed_lat, dtype), self.to_device(seed_lon, dtype)
         x, y = self._empty((ny, nx), dtype), self._empty((ny, nx), dtype)
         cur = torch.cuda.current_stream(self.device)
@@ -1043,9 +1042,9 @@ class Engine:
                     # would see half-filtered values): each level is packed once, by the chunk that first needs it.
                     l0 = t0 + 1 if (no_ext and t0 > 0) else t0
                     _capi.check(self.lib.lc_field_pack(
-                        self.ctx, C.c_void_p(ud[l0:].data_ptr()), C.c_void_p(vd[l0:].data_ptr()), _NP2LC[dtype], t0 + n + 1 - l0, ny_f, nx_f,
-                        int(interp_order), C.c_void_p(cub[le * l0:].data_ptr()) if cub is not None else None,
-                        C.c_void_p(ext[le * t0:].data_ptr()) if ext is not None else None), self.lib)
+                        self.ctx, self._ptr(ud[l0:]), self._ptr(vd[l0:]), code, t0 + n + 1 - l0, ny_f, nx_f, order,
+                        self._ptr(img[le * l0:] if img is not None else None),
+                        self._ptr(ext[le * t0:] if ext is not None else None)), self.lib)
                     e = torch.cuda.Event()
                     e.record(side)
                     events.append(e)
@@ -1079,7 +1078,7 @@ class Engine:
     def _sigma_of(self, x, y, seed_lat, seed_lon, gauss_sigma, fd_fp32_cast, tensor_layout):
         xs, ys = x, y
         # scipy's gaussian_filter returns an unsmoothed copy for sigma = 0 (LCS/LCS.py:187-190): skip the filter
-        if isinstance(gauss_sigma, (float, int)) and not isinstance(gauss_sigma, bool) and gauss_sigma > 1e-15:
+        if _smoothing_width(gauss_sigma) > 1e-15:
             xs = self.gaussian_filter(x, gauss_sigma)
             ys = self.gaussian_filter(y, gauss_sigma)
         # spacing evaluated in the coordinate dtype, as lat[1]-lat[0] is in numpy (tools.py:255-256)
@@ -1127,8 +1126,7 @@ class Engine:
         fd_fp32_cast) for ``planes`` whole grids, ``outs`` the group's part of each of the ``1 + extra_planes`` results.
         Returns ``(x_dep, y_dep, results)``, every tensor ``(n_windows, ny, nx)``, or ``(n_windows, 2, ny, nx)`` for
         ``n_dirs = 2``."""
-        if interp_order != 1 and field.order != interp_order:
-            raise ValueError(f"field was prepared for interp_order={field.order}")
+        _check_order(field, interp_order)
         if n_dirs == 2:
             timestep = float(timestep)
             if not timestep or not np.isfinite(timestep):
@@ -1146,7 +1144,7 @@ class Engine:
         shape = (n_windows, ny, nx) if n_dirs == 1 else (n_windows, n_dirs, ny, nx)
         x, y, *outs = (self._empty(shape, dtype) for _ in range(3 + extra_planes))
         xmode = x_boundary_mode(cyclic_xboundary, noncyclic_clamp, True)
-        smooth = isinstance(gauss_sigma, (float, int)) and not isinstance(gauss_sigma, bool) and gauss_sigma > 1e-15
+        smooth = _smoothing_width(gauss_sigma) > 1e-15      # as _sigma_of
         dlat = float(seed_lat[1] - seed_lat[0])     # as _sigma_of: the spacing in the coordinate dtype (tools.py:255-256)
         dlon = float(seed_lon[1] - seed_lon[0])
         g = self.series_group(dtype, n_dirs * ny * nx, n_windows, cyclic_xboundary, extra_planes)
@@ -1154,8 +1152,8 @@ class Engine:
             n = min(g, n_windows - m0)
             xg, yg = x[m0:m0 + n], y[m0:m0 + n]
             self._use_current_stream()
-            a = self._advect_args(field, interp_order, slat, ny, slon, nx, 0, ny, None, None, timestep, SETTLS_order, xmode,
-                                  t0 + m0 * t0_stride, nsteps, n, t0_stride, xg, yg, None, None)
+            a = self._advect_args(field, interp_order, slat, ny, slon, nx, timestep, SETTLS_order, xmode,
+                                  t0=t0 + m0 * t0_stride, nsteps=nsteps, n_members=n, t0_stride=t0_stride, out=(xg, yg))
             _capi.check(self.lib.lc_advect_series(self.ctx, C.byref(a)) if n_dirs == 1 else
                         self.lib.lc_advect_series_dirs(self.ctx, C.byref(a), n_dirs), self.lib)
             planes = n_dirs * n
@@ -1314,7 +1312,7 @@ def lcs_host(u, v, lat_f, lon_f, timestep, SETTLS_order=0, interp_order=3, cycli
         _capi.check(lib.lc_ctx_set_f64_fidelity(ctx, Engine._FIDELITY[float64_fidelity or "auto"]), lib)
         on = (os.environ.get("LCS_HOST_PIPELINE", "1")[:1] != "0") if pipeline is None else bool(pipeline)
         _capi.check(lib.lc_ctx_set_host_pipeline(ctx, int(on)), lib)
-        gs = float(gauss_sigma) if isinstance(gauss_sigma, (float, int)) and not isinstance(gauss_sigma, bool) else 0.0
+        gs = _smoothing_width(gauss_sigma)
         _capi.check(lib.lc_lcs_host(
             ctx, p(u), p(v), _NP2LC[dtype], nt, ny_f, nx_f, p(lat_f), p(lon_f), p(seed_lat), ny, p(seed_lon), nx,
             float(timestep), int(SETTLS_order), int(interp_order), x_boundary_mode(cyclic_xboundary, noncyclic_clamp),
@@ -1372,7 +1370,7 @@ def lcs_global_host(u, v, lat_f, lon_f, timestep, SETTLS_order=0, interp_order=3
         lat, lon, odt = lat_f, lon_f, dtype
     out = {k: np.empty((lat.size, lon.size), odt) for k in ("sigma", "x_dep", "y_dep")}
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    gs = float(gauss_sigma) if isinstance(gauss_sigma, (float, int)) and not isinstance(gauss_sigma, bool) else 0.0
+    gs = _smoothing_width(gauss_sigma)
     ctx = C.c_void_p()
     _capi.check(lib.lc_ctx_create(int(device), C.byref(ctx)), lib)
     try:

@@ -1139,8 +1139,9 @@ def test_float32_wind_kept_float32_equals_the_float64_images_bit_for_bit(eng, O,
     sa, sb = eng.sample(f_new, px, py, level=2), eng.sample(f_old, px, py, level=2)
     assert all(np.array_equal(_np(p_), _np(q_)) for p_, q_ in zip(sa, sb))
     # the C ABI refuses what the dtype does not cover
-    a = eng._advect_args(f_new, 1, eng.to_device(lat, np.float64), lat.size, eng.to_device(lon, np.float64), lon.size, 0, lat.size, None, None,
-                         -1800.0, 2, 1, 0, 8, 1, 0, *(eng._empty((lat.size, lon.size), np.float64) for _ in range(2)), None, None)
+    a = eng._advect_args(f_new, 1, eng.to_device(lat, np.float64), lat.size, eng.to_device(lon, np.float64), lon.size, -1800.0, 2, 1,
+                         row0=0, ny_global=lat.size, t0=0, nsteps=8, n_members=1, t0_stride=0,
+                         out=tuple(eng._empty((lat.size, lon.size), np.float64) for _ in range(2)))
     a.interp_order = 3
     from lagrangiancoherence_amd import _capi
     import ctypes

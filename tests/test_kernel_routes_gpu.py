@@ -127,8 +127,8 @@ def _run(eng, r, field, K, dt):
         sl, so = eng.to_device(slat, field.dtype), eng.to_device(slon, field.dtype)
         ny, nx = sl.numel(), so.numel()
         x, y = eng._empty((M, ny, nx), field.dtype), eng._empty((M, ny, nx), field.dtype)
-        a = eng._advect_args(field, order, sl, ny, so, nx, 0, ny, None, None, dt, K, _capi.LC_X_CLAMP_POINT, KR.T0, KR.NSTEPS,
-                             M, 1, x, y, None, None)
+        a = eng._advect_args(field, order, sl, ny, so, nx, dt, K, _capi.LC_X_CLAMP_POINT, row0=0, ny_global=ny, t0=KR.T0,
+                             nsteps=KR.NSTEPS, n_members=M, t0_stride=1, out=(x, y))
         _capi.check(eng.lib.lc_advect_ex(eng.ctx, C.byref(a)), eng.lib)
         out = [(KR.T0 + m, x[m], y[m], None, None) for m in range(M)]
     elif call == "series":

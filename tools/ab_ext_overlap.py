@@ -33,9 +33,7 @@ def overlapped(chunk):
     ext = eng._empty((le * (nt - 1),), dtype)
     eng._use_current_stream()
     _capi.check(eng.lib.lc_field_pack(eng.ctx, eng._ptr(u), eng._ptr(v), _NP2LC[dtype], nt, ny_f, nx_f, 3, eng._ptr(cub), None), eng.lib)
-    lat64, lon64 = np.asarray(lat, dtype), np.asarray(lon, dtype)
-    field = PackedField(None, cub, ext, nt, ny_f, nx_f, float(lat64[0]), float(lat64[-1]), float(lon64[0]), float(lon64[-1]), dtype,
-                        False, 3, False, u, v, (u._version, v._version))
+    field = PackedField.on_grid(lat, lon, dtype, nt, ny_f, nx_f, cub=cub, ext=ext, order=3, u=u, v=v)
     x, y = eng._empty((ny_f, nx_f), dtype), eng._empty((ny_f, nx_f), dtype)
     side.wait_stream(cur)
     starts, events = list(range(0, nt - 1, chunk)), []

@@ -24,7 +24,6 @@ ud, vd = eng.to_device(u, f32), eng.to_device(v, f32)
 slat_d, slon_d = eng.to_device(slat, f32), eng.to_device(slon, f32)
 ny_f, nx_f = 720, 1440
 le = eng.lib.lc_packed_elems(1, ny_f, nx_f)
-la, lo = lat.astype(f32), lon.astype(f32)
 side = torch.cuda.Stream()
 side_hi = torch.cuda.Stream(priority=-1)
 
@@ -38,8 +37,7 @@ def piped(chunk, advect_stream=None):
     cur = torch.cuda.current_stream()
     lin = eng._empty((le * nt,), f32)
     ext = eng._empty((le * (nt - 1),), f32)
-    field = PackedField(lin, None, ext, nt, ny_f, nx_f, float(la[0]), float(la[-1]), float(lo[0]), float(lo[-1]), np.dtype(f32),
-                        False, 1, False, None, None, None)
+    field = PackedField.on_grid(lat, lon, f32, nt, ny_f, nx_f, lin=lin, ext=ext)
     x, y = eng._empty((n, n), f32), eng._empty((n, n), f32)
     side.wait_stream(cur)
     starts = list(range(0, nt - 1, chunk))
