@@ -54,8 +54,10 @@ def test_nearest_tie_goes_to_the_larger_index_like_pandas(eng):
     got = eng.regrid(u, src, src, dst, dst).cpu().numpy()
     ref = PO.regrid_common_grid(u, src, src, dst, dst)[0]
     assert np.array_equal(got, ref) and got[0, 0, 0] == 0.0 and got[0, 2, 2] == 15.0
-    # ties inside the range never reach the nearest path; a tie outside cannot occur -- check pandas' rule on a
-    # 2-node axis through the oracle's own indexer instead
+    # a tie outside the range cannot occur.  Ties inside it do reach the nearest path, through NaN: a NaN source node makes
+    # the interpolation NaN at the midpoints beside it (every second column of a 1 degree source on the 0.5 degree grid), and
+    # those are filled by this rule -- run on the GPU in test_preprocess_cases_gpu.py (nan_beside_midpoint).  Here, pandas'
+    # rule through the oracle's own indexer
     import pandas as pd
     assert list(pd.Index(src).get_indexer([0.5, 1.5], method="nearest")) == [1, 2]
 
