@@ -4896,31 +4896,12 @@ extern "C" int lc_advect_batch(lc_ctx *ctx, const void *packed_lin, const void *
                                int ny_global, const void *x_start, const void *y_start, double timestep, int settls_order,
                                int interp_order, int cyclic_x, int t0, int nsteps, int n_members, int t0_stride, void *x_out,
                                void *y_out, void *traj_x, void *traj_y) {
-    lc_advect_args a = {};
-    a.struct_size = sizeof(a);
-    a.packed_lin = packed_lin;
-    a.packed_cub = packed_cub;
-    a.packed_ext = packed_ext;
-    a.dtype = dtype;
-    a.nt = nt;
-    a.ny_f = ny_f;
-    a.nx_f = nx_f;
-    a.lat_min = lat_min;
-    a.lat_max = lat_max;
-    a.lon_min = lon_min;
-    a.lon_max = lon_max;
-    a.seed_lat_dev = seed_lat_dev;
-    a.ny = ny;
-    a.seed_lon_dev = seed_lon_dev;
-    a.nx = nx;
+    lc_advect_args a = lc_whole_grid_args({nullptr, nullptr, dtype, nt, ny_f, nx_f, lat_min, lat_max, lon_min, lon_max}, {packed_lin, packed_cub, packed_ext},
+                                          {seed_lat_dev, seed_lon_dev, ny, nx, 0.0, 0.0}, {timestep, settls_order, interp_order, cyclic_x});
     a.row0 = row0;
     a.ny_global = ny_global;
     a.x_start = x_start;
     a.y_start = y_start;
-    a.timestep = timestep;
-    a.settls_order = settls_order;
-    a.interp_order = interp_order;
-    a.cyclic_x = cyclic_x;
     a.t0 = t0;
     a.nsteps = nsteps;
     a.n_members = n_members;

@@ -158,56 +158,6 @@ extern "C" int lc_ctx_get_f64_fidelity(const lc_ctx *ctx, int *mode_out) {
     return LC_OK;
 }
 
-// lc_advect with the raw planes as the order-1 source where a kernel reads them (lc_advect_ex): the host routes then
-// neither allocate nor pack the order-1 image
-static bool host_route_needs_lin(int dtype, int interp_order) { return dtype == LC_F32 && interp_order == 1; }
-static int advect_with_raw(lc_ctx *ctx, const void *lin, const void *cub, const void *ext, const void *u, const void *v, int dtype,
-                           int nt, int ny_f, int nx_f, double lat_min, double lat_max, double lon_min, double lon_max,
-                           const void *slat, int ny, const void *slon, int nx, double timestep, int K, int order, int cyclic_x,
-                           int t0, int nsteps, void *x, void *y, void *tx, void *ty) {
-    lc_advect_args a = {};
-    a.struct_size = sizeof(a);
-    a.packed_lin = lin;
-    a.packed_cub = cub;
-    a.packed_ext = ext;
-    a.u_raw = u;
-    a.v_raw = v;
-    a.dtype = dtype;
-    a.nt = nt;
-    a.ny_f = ny_f;
-    a.nx_f = nx_f;
-    a.lat_min = lat_min;
-    a.lat_max = lat_max;
-    a.lon_min = lon_min;
-    a.lon_max = lon_max;
-    a.seed_lat_dev = slat;
-    a.ny = ny;
-    a.seed_lon_dev = slon;
-    a.nx = nx;
-    a.row0 = 0;
-    a.ny_global = ny;
-    a.timestep = timestep;
-    a.settls_order = K;
-    a.interp_order = order;
-    a.cyclic_x = cyclic_x;
-    a.t0 = t0;
-    a.nsteps = nsteps;
-    a.n_members = 1;
-    a.t0_stride = 0;
-    a.x_out = x;
-    a.y_out = y;
-    a.traj_x = tx;
-    a.traj_y = ty;
-    return lc_advect_ex(ctx, &a);
-}
-
-// float64 on the one-call host routes: the reference's operation order (no fused-level image) or the fast form
-static bool f64_exact_order(const lc_ctx *ctx, int dtype, int ny, int nx) {
-    if (dtype != LC_F64) return false;
-    return ctx->f64_fidelity == LC_F64_EXACT_ORDER ||
-           (ctx->f64_fidelity == LC_F64_AUTO && (long long)ny * nx <= LC_EXACT_ORDER_MAX_SEEDS);
-}
-
 extern "C" int lc_ctx_get_level_chunk(const lc_ctx *ctx, int *levels_out) {
     LC_REQUIRE(ctx && levels_out, "lc_ctx_get_level_chunk: null pointer");
     *levels_out = ctx->level_chunk;
@@ -499,7 +449,9 @@ struct HostWorkspace {
 struct DevBuf {
     void *p = nullptr;
     size_t bytes = 0;
-    HostWorkspace *ws = nullptr;  // NULL: plain hipMalloc / hipFree (lc_lcs_global_host, a context with the cache off)
+    HostWorkspace *ws;  // NULL: plain hipMalloc / hipFree (lc_lcs_global_host, a context with the cache off)
+    explicit DevBuf(HostWorkspace *ws_ = nullptr) : ws(ws_) {}
+    DevBuf(const DevBuf &) = delete;
     ~DevBuf() {
         if (!p) return;
         if (!(ws && ws->give(p, bytes))) (void)hipFree(p);
@@ -554,13 +506,13 @@ static lc_host_xfer *host_xfer_of(lc_ctx *ctx) {
 // host (Engine.to_device, the drop-in's results) moves large arrays with -- hipMemcpy from pages the runtime has not pinned
 // before runs at a quarter of the bus rate (hostxfer.h).  to_device: work enqueued on the context's stream after the call sees
 // the data.  to_host: sees everything enqueued on the context's stream before the call; returns when the bytes are in `host`.
-extern "C" int lc_copy_to_device(lc_ctx *ctx, void *dev, const void *host, size_t bytes) {
-    LC_REQUIRE(ctx && (bytes == 0 || (dev && host)), "lc_copy_to_device: null pointer");
+static int staged_copy(lc_ctx *ctx, const char *who, void *dst, const void *src, size_t bytes, bool to_device) {
+    LC_REQUIRE(ctx && (bytes == 0 || (dst && src)), "%s: null pointer", who);
     if (!bytes) return LC_OK;
     LC_HIP_CHECK(hipSetDevice(ctx->device));
     lc_host_xfer *hx = host_xfer_of(ctx);
     if (!hx) {
-        LC_HIP_CHECK(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+        LC_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, ctx->stream));
         LC_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // (a pageable source may be reused by the caller at once)
         return LC_OK;
     }
@@ -571,47 +523,27 @@ extern "C" int lc_copy_to_device(lc_ctx *ctx, void *dev, const void *host, size_
         hipEvent_t e;
         ~Ev() { (void)hipEventDestroy(e); }
     } guard{ev};
-    LC_HIP_CHECK(hipEventRecord(ev, ctx->stream));            // the destination may still be in use by earlier work of the stream
+    LC_HIP_CHECK(hipEventRecord(ev, ctx->stream));            // the device side may still be in use by earlier work of the stream
     LC_HIP_CHECK(hipStreamWaitEvent(hx->copy, ev, 0));
-    hipError_t e = hx->upload(dev, host, bytes);
+    hipError_t e = to_device ? hx->upload(dst, src, bytes) : hx->download(dst, src, bytes);
     if (e != hipSuccess) {
         hx->drain();
-        lc_set_error("lc_copy_to_device: staged upload failed: %s", hipGetErrorString(e));
+        lc_set_error("%s: staged %s failed: %s", who, to_device ? "upload" : "download", hipGetErrorString(e));
         (void)hipGetLastError();
         return LC_EHIP;
     }
+    if (!to_device) return LC_OK;                             // (download() returned with the bytes in `dst`)
     LC_HIP_CHECK(hipEventRecord(ev, hx->copy));
     LC_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ev, 0));
     return LC_OK;
 }
 
+extern "C" int lc_copy_to_device(lc_ctx *ctx, void *dev, const void *host, size_t bytes) {
+    return staged_copy(ctx, "lc_copy_to_device", dev, host, bytes, true);
+}
+
 extern "C" int lc_copy_to_host(lc_ctx *ctx, void *host, const void *dev, size_t bytes) {
-    LC_REQUIRE(ctx && (bytes == 0 || (dev && host)), "lc_copy_to_host: null pointer");
-    if (!bytes) return LC_OK;
-    LC_HIP_CHECK(hipSetDevice(ctx->device));
-    lc_host_xfer *hx = host_xfer_of(ctx);
-    if (!hx) {
-        LC_HIP_CHECK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        LC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        return LC_OK;
-    }
-    std::lock_guard<std::mutex> ring(hx->use);
-    hipEvent_t ev = nullptr;
-    LC_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    struct Ev {
-        hipEvent_t e;
-        ~Ev() { (void)hipEventDestroy(e); }
-    } guard{ev};
-    LC_HIP_CHECK(hipEventRecord(ev, ctx->stream));
-    LC_HIP_CHECK(hipStreamWaitEvent(hx->copy, ev, 0));
-    hipError_t e = hx->download(host, dev, bytes);
-    if (e != hipSuccess) {
-        hx->drain();
-        lc_set_error("lc_copy_to_host: staged download failed: %s", hipGetErrorString(e));
-        (void)hipGetLastError();
-        return LC_EHIP;
-    }
-    return LC_OK;
+    return staged_copy(ctx, "lc_copy_to_host", host, dev, bytes, false);
 }
 
 extern "C" int lc_ctx_set_host_cache(lc_ctx *ctx, int on) {
@@ -622,26 +554,175 @@ extern "C" int lc_ctx_set_host_cache(lc_ctx *ctx, int on) {
     return LC_OK;
 }
 
-namespace {
-template <typename T>
-void coord_extremes(const void *lat, int n, double *lo, double *hi) {
-    const T *p = (const T *)lat;
-    *lo = (double)p[0];
-    *hi = (double)p[n - 1];
-}
-}  // namespace
-
 #define LC_TRY(expr)              \
     do {                          \
         int _s = (expr);          \
         if (_s != LC_OK) return _s; \
     } while (0)
 
+// ---------------------------------------------------------------------------
+// The device-side core of the one-call host routes (lc_lcs_host, lc_lcs_global_host): how a wind and a seed grid are described
+// (lcs_common.h: lc_dev_wind, lc_dev_seeds), which packed images the call owns and how they are filled, the one fill of
+// lc_advect_args (lc_whole_grid_args), and the smoothing + sigma stage.  The routes differ in how bytes travel and in what
+// precedes the path (regridding, truncation), not in any of this.
+// ---------------------------------------------------------------------------
+namespace {
+// First and last node of a host coordinate array in its own dtype, and the spacing as numpy evaluates c[1] - c[0] in that dtype
+// (tools.py:255-256)
+struct CoordAxis {
+    double first, last, step;
+};
+template <typename T>
+CoordAxis coord_axis_of(const T *c, int n) {
+    return {(double)c[0], (double)c[n - 1], (double)(T)(c[n > 1 ? 1 : 0] - c[0])};
+}
+CoordAxis coord_axis(const void *c, int n, int dtype) {
+    return dtype == LC_F32 ? coord_axis_of((const float *)c, n) : coord_axis_of((const double *)c, n);
+}
+
+// The packed images of a route's wind: which of them exist for the call's options, their buffers, and the lc_field_pack calls
+// that fill a range of levels -- the C routes' counterpart of engine.field_plan, the one place the rule is written.
+struct HostImages {
+    int order;
+    bool has_lin, has_cub, has_ext;
+    DevBuf lin, cub, ext;
+    HostImages(const lc_ctx *ctx, HostWorkspace *ws, int dtype, int interp_order, int settls_order, int ny, int nx)
+        : order(interp_order), lin(ws), cub(ws), ext(ws) {
+        // float64: the reference's operation order (no fused-level image) or the fast form (lc_ctx_set_f64_fidelity)
+        const bool exact_order = dtype == LC_F64 && (ctx->f64_fidelity == LC_F64_EXACT_ORDER ||
+                                                     (ctx->f64_fidelity == LC_F64_AUTO && (long long)ny * nx <= LC_EXACT_ORDER_MAX_SEEDS));
+        // the order-1 image only where a kernel reads it: everywhere else the raw planes are the order-1 source (lc_advect_ex)
+        has_lin = dtype == LC_F32 && interp_order == 1;
+        has_cub = interp_order != 1;
+        // one combined sample per SETTLS iteration (ext image of the matching order) in float32, and in float64 beyond the
+        // size / setting where the reference's own operation order is kept
+        has_ext = settls_order > 0 && (interp_order == 1 || interp_order == 3) && !exact_order;
+    }
+    int alloc(const lc_dev_wind &w) {
+        const size_t es = w.dtype == LC_F32 ? 4 : 8;
+        if (has_lin) LC_TRY(lin.alloc(lc_packed_elems(w.nt, w.ny_f, w.nx_f) * es));
+        if (has_cub) LC_TRY(cub.alloc(lc_packed_elems(w.nt, w.ny_f, w.nx_f) * es));
+        if (has_ext) LC_TRY(ext.alloc(lc_packed_elems(w.nt - 1, w.ny_f, w.nx_f) * es));
+        return LC_OK;
+    }
+    // the images of wind levels [l0, l0 + nlev), ext of [l0, l0 + nlev - 1)
+    int pack(lc_ctx *ctx, const lc_dev_wind &w, int l0, int nlev) const {
+        const size_t es = w.dtype == LC_F32 ? 4 : 8;
+        const size_t plane = (size_t)l0 * w.ny_f * w.nx_f * es, image = (size_t)l0 * lc_packed_elems(1, w.ny_f, w.nx_f) * es;
+        auto at = [](void *base, size_t off) -> void * { return base ? (char *)base + off : nullptr; };
+        const void *ul = (const char *)w.u + plane, *vl = (const char *)w.v + plane;
+        if (has_lin || (order == 1 && has_ext))
+            LC_TRY(lc_field_pack(ctx, ul, vl, w.dtype, nlev, w.ny_f, w.nx_f, 1, at(lin.p, image), order == 1 ? at(ext.p, image) : nullptr));
+        if (has_cub) LC_TRY(lc_field_pack(ctx, ul, vl, w.dtype, nlev, w.ny_f, w.nx_f, order, at(cub.p, image), at(ext.p, image)));
+        return LC_OK;
+    }
+    lc_dev_images dev() const { return {lin.p, cub.p, ext.p}; }
+};
+
+// Gaussian smoothing of the departure fields (LCS.py:187-190; sigma = 0: scipy returns an unsmoothed copy), then sigma into `sig`
+struct SigmaStage {
+    DevBuf sig, gx, gy, gtmp;
+    explicit SigmaStage(HostWorkspace *ws) : sig(ws), gx(ws), gy(ws), gtmp(ws) {}
+    int run(lc_ctx *ctx, const void *x, const void *y, int dtype, const lc_dev_seeds &s, double gauss_sigma, int fd_fp32_cast,
+            int tensor_layout) {
+        const size_t sbytes = (size_t)s.ny * s.nx * (dtype == LC_F32 ? 4 : 8);
+        if (!sig.p) LC_TRY(sig.alloc(sbytes));
+        if (gauss_sigma > 1e-15) {
+            LC_TRY(gx.alloc(sbytes));
+            LC_TRY(gy.alloc(sbytes));
+            LC_TRY(gtmp.alloc(sbytes));
+            LC_TRY(lc_gaussian_filter(ctx, x, dtype, s.ny, s.nx, gauss_sigma, gtmp.p, gx.p));
+            LC_TRY(lc_gaussian_filter(ctx, y, dtype, s.ny, s.nx, gauss_sigma, gtmp.p, gy.p));
+            x = gx.p;
+            y = gy.p;
+        }
+        return lc_sigma(ctx, x, y, dtype, 0, s.ny, s.nx, s.ny, s.lat, s.dlat, s.dlon, fd_fp32_cast, tensor_layout, 0, s.ny, sig.p);
+    }
+};
+
+// The transfers of one lc_lcs_host call: the staging ring (hostxfer.h), or plain hipMemcpyAsync on the context's stream when
+// the ring cannot be had / is switched off (hx == NULL).  Declared AFTER the call's device buffers, so that it is gone before
+// they are freed.  Its members end in this order (the reverse of their declaration, after the destructor's body):
+//   the events; `touch` joined; `drain` -- whatever happened, no DMA of this call is left running into / out of buffers that are
+//   about to be freed; `ring` -- the ring is the device's, shared by every context: this call's until it returns, released last.
+struct HostTransfers {
+    lc_host_xfer *hx;
+    hipStream_t st;
+    std::unique_lock<std::mutex> ring;
+    struct Drain {
+        lc_host_xfer *hx;
+        hipStream_t st;
+        ~Drain() {
+            if (hx) hx->drain();
+            (void)hipStreamSynchronize(st);
+        }
+    } drain;
+    lc_prefault touch;
+    hipEvent_t ev_ready = nullptr, ev_up = nullptr, ev_done = nullptr;
+    HostTransfers(lc_host_xfer *hx_, hipStream_t st_) : hx(hx_), st(st_), drain{hx_, st_} {
+        if (hx) ring = std::unique_lock<std::mutex>(hx->use);
+    }
+    ~HostTransfers() {
+        for (hipEvent_t e : {ev_ready, ev_up, ev_done})
+            if (e) (void)hipEventDestroy(e);
+    }
+    // the copy stream starts after whatever the caller's stream was doing with this memory (nothing, normally); the pages of
+    // the caller's output arrays are touched in the background meanwhile
+    int begin(const std::vector<lc_host_xfer::Range> &results) {
+        if (!hx) return LC_OK;
+        LC_HIP_CHECK(hipEventCreateWithFlags(&ev_ready, hipEventDisableTiming));
+        LC_HIP_CHECK(hipEventCreateWithFlags(&ev_up, hipEventDisableTiming));
+        LC_HIP_CHECK(hipEventCreateWithFlags(&ev_done, hipEventDisableTiming));
+        LC_HIP_CHECK(hipEventRecord(ev_ready, st));
+        LC_HIP_CHECK(hipStreamWaitEvent(hx->copy, ev_ready, 0));
+        std::vector<std::pair<void *, size_t>> outs;
+        for (const auto &r : results) outs.emplace_back(r.host, r.bytes);
+        touch.start(outs);
+        return LC_OK;
+    }
+    int up(void *dev, const void *host, size_t bytes) {
+        if (!bytes) return LC_OK;
+        if (hx) {
+            LC_HIP_CHECK(hx->upload(dev, host, bytes));
+        } else {
+            LC_HIP_CHECK(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, st));
+        }
+        return LC_OK;
+    }
+    // work enqueued on the context's stream from here on sees everything uploaded so far
+    int uploaded() {
+        if (!hx) return LC_OK;
+        LC_HIP_CHECK(hipEventRecord(ev_up, hx->copy));
+        LC_HIP_CHECK(hipStreamWaitEvent(st, ev_up, 0));
+        return LC_OK;
+    }
+    // the copy stream waits for the kernels; so does the host (the first download DMA waits for this event anyway: the host has
+    // nothing else to do)
+    int kernels_done() {
+        if (!hx) return LC_OK;
+        LC_HIP_CHECK(hipEventRecord(ev_done, st));
+        LC_HIP_CHECK(hipStreamWaitEvent(hx->copy, ev_done, 0));
+        touch.join();
+        LC_HIP_CHECK(hipEventSynchronize(ev_done));
+        return LC_OK;
+    }
+    int down(const std::vector<lc_host_xfer::Range> &results) {
+        if (hx) {
+            LC_HIP_CHECK(hx->download(results));   // one pipelined sequence of pieces over all of them
+        } else {
+            for (const auto &r : results) LC_HIP_CHECK(hipMemcpyAsync(r.host, r.dev, r.bytes, hipMemcpyDeviceToHost, st));
+        }
+        return LC_OK;
+    }
+};
+}  // namespace
+
 extern "C" int lc_lcs_host(lc_ctx *ctx, const void *u_host, const void *v_host, int dtype, int nt, int ny_f, int nx_f,
                            const void *lat_f_host, const void *lon_f_host, const void *seed_lat_host, int ny,
                            const void *seed_lon_host, int nx, double timestep, int settls_order, int interp_order,
                            int cyclic_x, int t0, int nsteps, double gauss_sigma, int fd_fp32_cast, int tensor_layout,
                            void *sigma_out, void *x_out, void *y_out, void *traj_x, void *traj_y) {
+    // ---- validate: before any allocation (a negative nsteps must not turn into a huge hipMalloc) ---------------------------------
     LC_REQUIRE(ctx, "lc_lcs_host: null context");
     LC_REQUIRE(dtype == LC_F32 || dtype == LC_F64, "lc_lcs_host: bad dtype %d", dtype);
     LC_REQUIRE(u_host && v_host && lat_f_host && lon_f_host && seed_lat_host && seed_lon_host,
@@ -649,7 +730,6 @@ extern "C" int lc_lcs_host(lc_ctx *ctx, const void *u_host, const void *v_host, 
     LC_REQUIRE(nt >= 2 && ny_f >= 4 && nx_f >= 4 && ny >= 1 && nx >= 1, "lc_lcs_host: bad sizes");
     LC_REQUIRE((traj_x == nullptr) == (traj_y == nullptr), "lc_lcs_host: traj_x/traj_y must be set together");
     LC_REQUIRE(!sigma_out || (ny >= 5 && nx >= 5), "lc_lcs_host: sigma needs at least a 5x5 seed grid");
-    // validated before any allocation (a negative nsteps must not turn into a huge hipMalloc)
     LC_REQUIRE(settls_order >= 0, "lc_lcs_host: SETTLS_order must be >= 0");
     LC_REQUIRE(t0 >= 0 && nsteps >= 0 && t0 + nsteps <= nt - 1, "lc_lcs_host: steps [%d,%d) need levels up to %d, have %d",
                t0, t0 + nsteps, t0 + nsteps, nt);
@@ -659,35 +739,15 @@ extern "C" int lc_lcs_host(lc_ctx *ctx, const void *u_host, const void *v_host, 
         return LC_EUNSUPPORTED;
     }
     LC_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
     const size_t es = dtype == LC_F32 ? 4 : 8;
-    const size_t fbytes = (size_t)nt * ny_f * nx_f * es;
-    const size_t pbytes = lc_packed_elems(nt, ny_f, nx_f) * es;
-    const size_t sbytes = (size_t)ny * nx * es;
-    double lat_min, lat_max, lon_min, lon_max, s_lat0, s_lat1, s_lon0, s_lon1;
-    if (dtype == LC_F32) {
-        coord_extremes<float>(lat_f_host, ny_f, &lat_min, &lat_max);
-        coord_extremes<float>(lon_f_host, nx_f, &lon_min, &lon_max);
-        s_lat0 = ((const float *)seed_lat_host)[0];
-        s_lat1 = ((const float *)seed_lat_host)[ny > 1 ? 1 : 0];
-        s_lon0 = ((const float *)seed_lon_host)[0];
-        s_lon1 = ((const float *)seed_lon_host)[nx > 1 ? 1 : 0];
-    } else {
-        coord_extremes<double>(lat_f_host, ny_f, &lat_min, &lat_max);
-        coord_extremes<double>(lon_f_host, nx_f, &lon_min, &lon_max);
-        s_lat0 = ((const double *)seed_lat_host)[0];
-        s_lat1 = ((const double *)seed_lat_host)[ny > 1 ? 1 : 0];
-        s_lon0 = ((const double *)seed_lon_host)[0];
-        s_lon1 = ((const double *)seed_lon_host)[nx > 1 ? 1 : 0];
-    }
-    // spacing in the coordinate dtype, as lat[1]-lat[0] evaluates in numpy (tools.py:255-256)
-    const double dlat = dtype == LC_F32 ? (double)((float)s_lat1 - (float)s_lat0) : s_lat1 - s_lat0;
-    const double dlon = dtype == LC_F32 ? (double)((float)s_lon1 - (float)s_lon0) : s_lon1 - s_lon0;
+    const size_t lvl_bytes = (size_t)ny_f * nx_f * es, sbytes = (size_t)ny * nx * es, tbytes = sbytes * (size_t)(nsteps + 1);
 
     // LCS_HOST_TIMING: wall-clock marks of this call (ms since entry) -- allocations done, last upload piece handed to the DMA
     // engine, kernels finished, results in the caller's buffers
     const auto t_enter = std::chrono::steady_clock::now();
     auto ms_since = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enter).count(); };
-    double t_alloc = 0, t_up = 0, t_kernels = 0;
+    double t_kernels = 0;
     struct ExitMark {  // (declared before the buffers: runs after they have been freed)
         const std::chrono::steady_clock::time_point t0;
         bool on;
@@ -696,224 +756,115 @@ extern "C" int lc_lcs_host(lc_ctx *ctx, const void *u_host, const void *v_host, 
                                  std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
         }
     } exit_mark{t_enter, ctx->host_timing != 0};
-    DevBuf u, v, lin, cub, ext, slat, slon, x, y, tx, ty, sig, gx, gy, gtmp;
-    if (ctx->host_cache) {
-        if (!ctx->host_ws) ctx->host_ws = new (std::nothrow) HostWorkspace;
-        for (DevBuf *b : {&u, &v, &lin, &cub, &ext, &slat, &slon, &x, &y, &tx, &ty, &sig, &gx, &gy, &gtmp}) b->ws = (HostWorkspace *)ctx->host_ws;
-    }
-    LC_TRY(u.alloc(fbytes));
-    LC_TRY(v.alloc(fbytes));
-    const bool need_lin = host_route_needs_lin(dtype, interp_order);
-    if (need_lin) LC_TRY(lin.alloc(pbytes));
-    if (interp_order != 1) LC_TRY(cub.alloc(pbytes));
+
+    // ---- allocate ----------------------------------------------------------------------------------------------------------------
+    if (ctx->host_cache && !ctx->host_ws) ctx->host_ws = new (std::nothrow) HostWorkspace;
+    HostWorkspace *ws = ctx->host_cache ? (HostWorkspace *)ctx->host_ws : nullptr;
+    DevBuf u(ws), v(ws), slat(ws), slon(ws), x(ws), y(ws), tx(ws), ty(ws);
+    HostImages img(ctx, ws, dtype, interp_order, settls_order, ny, nx);
+    SigmaStage sigma(ws);
+    LC_TRY(u.alloc((size_t)nt * lvl_bytes));
+    LC_TRY(v.alloc((size_t)nt * lvl_bytes));
+    const CoordAxis la = coord_axis(lat_f_host, ny_f, dtype), lo = coord_axis(lon_f_host, nx_f, dtype);
+    const lc_dev_wind wind = {u.p, v.p, dtype, nt, ny_f, nx_f, la.first, la.last, lo.first, lo.last};
+    LC_TRY(img.alloc(wind));
     LC_TRY(slat.alloc(ny * es));
     LC_TRY(slon.alloc(nx * es));
+    const lc_dev_seeds seeds = {slat.p, slon.p, ny, nx, coord_axis(seed_lat_host, ny, dtype).step, coord_axis(seed_lon_host, nx, dtype).step};
     LC_TRY(x.alloc(sbytes));
     LC_TRY(y.alloc(sbytes));
     if (traj_x) {
-        LC_TRY(tx.alloc(sbytes * (size_t)(nsteps + 1)));
-        LC_TRY(ty.alloc(sbytes * (size_t)(nsteps + 1)));
+        LC_TRY(tx.alloc(tbytes));
+        LC_TRY(ty.alloc(tbytes));
     }
-    hipStream_t st = ctx->stream;
-    // one combined sample per SETTLS iteration (ext image of the matching order) in float32, and in float64 beyond the
-    // size / setting where the reference's own operation order is kept (lc_ctx_set_f64_fidelity)
-    const bool fusable = (interp_order == 1 || interp_order == 3) && !f64_exact_order(ctx, dtype, ny, nx);
-    if (settls_order > 0 && fusable) LC_TRY(ext.alloc(lc_packed_elems(nt - 1, ny_f, nx_f) * es));
-    if (sigma_out) LC_TRY(sig.alloc(sbytes));
+    if (sigma_out) LC_TRY(sigma.sig.alloc(sbytes));
+    // the results, in the order they travel down: the departure points while nothing else does; sigma (0.07 ms of kernel) last
+    std::vector<lc_host_xfer::Range> results;
+    if (x_out) results.push_back({x_out, x.p, sbytes});
+    if (y_out) results.push_back({y_out, y.p, sbytes});
+    if (sigma_out) results.push_back({sigma_out, sigma.sig.p, sbytes});
+    if (traj_x) {
+        results.push_back({traj_x, tx.p, tbytes});
+        results.push_back({traj_y, ty.p, tbytes});
+    }
 
-    // ---- transfers: the staging ring (hostxfer.h), or plain hipMemcpyAsync when it cannot be had / is switched off --------
-    lc_host_xfer *hx = host_xfer_of(ctx);  // (NULL: switched off, or no pinned memory / stream to be had -- the plain copies below)
-    // the ring is the device's, shared by every context: this call's until it returns (declared before `drain`: released last)
-    std::unique_lock<std::mutex> ring;
-    if (hx) ring = std::unique_lock<std::mutex>(hx->use);
-    // whatever happens below, no DMA of this call is left running into / out of buffers that are about to be freed
-    struct Drain {
-        lc_host_xfer *hx;
-        hipStream_t st;
-        ~Drain() {
-            if (hx) hx->drain();
-            (void)hipStreamSynchronize(st);
-        }
-    } drain{hx, st};
-    lc_prefault touch;  // (declared after `drain`: joined first)
-    hipEvent_t ev_ready = nullptr, ev_up = nullptr, ev_done = nullptr;
-    struct Events {
-        hipEvent_t *e[3];
-        ~Events() {
-            for (auto p : e)
-                if (*p) (void)hipEventDestroy(*p);
-        }
-    } events{{&ev_ready, &ev_up, &ev_done}};
-    auto up = [&](void *dev, const void *host, size_t bytes) -> int {
-        if (!bytes) return LC_OK;
-        if (hx) {
-            LC_HIP_CHECK(hx->upload(dev, host, bytes));
-        } else {
-            LC_HIP_CHECK(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, st));
-        }
-        return LC_OK;
-    };
-    auto down = [&](void *host, const void *dev, size_t bytes) -> int {
-        if (hx) {
-            LC_HIP_CHECK(hx->download(host, dev, bytes));
-        } else {
-            LC_HIP_CHECK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
-        }
-        return LC_OK;
-    };
-    if (hx) {
-        LC_HIP_CHECK(hipEventCreateWithFlags(&ev_ready, hipEventDisableTiming));
-        LC_HIP_CHECK(hipEventCreateWithFlags(&ev_up, hipEventDisableTiming));
-        LC_HIP_CHECK(hipEventCreateWithFlags(&ev_done, hipEventDisableTiming));
-        // the copy stream starts after whatever the caller's stream was doing with this memory (nothing, normally)
-        LC_HIP_CHECK(hipEventRecord(ev_ready, st));
-        LC_HIP_CHECK(hipStreamWaitEvent(hx->copy, ev_ready, 0));
-        std::vector<std::pair<void *, size_t>> outs;
-        if (sigma_out) outs.emplace_back(sigma_out, sbytes);
-        if (x_out) outs.emplace_back(x_out, sbytes);
-        if (y_out) outs.emplace_back(y_out, sbytes);
-        if (traj_x) {
-            outs.emplace_back(traj_x, sbytes * (size_t)(nsteps + 1));
-            outs.emplace_back(traj_y, sbytes * (size_t)(nsteps + 1));
-        }
-        touch.start(outs);
-    }
-    t_alloc = ms_since();
-    LC_TRY(up(slat.p, seed_lat_host, ny * es));
-    LC_TRY(up(slon.p, seed_lon_host, nx * es));
+    // ---- transfers set up --------------------------------------------------------------------------------------------------------
+    HostTransfers xfer(host_xfer_of(ctx), st);  // (NULL ring: switched off, or no pinned memory / stream to be had -- plain copies)
+    LC_TRY(xfer.begin(results));
+    const double t_alloc = ms_since();
+    LC_TRY(xfer.up(slat.p, seed_lat_host, ny * es));
+    LC_TRY(xfer.up(slon.p, seed_lon_host, nx * es));
 
     // ---- upload || pack + advect, level chunk by level chunk ------------------------------------------------------------------
     // Chunk c covers the steps [s0, s1): it needs the wind levels t0 + s0 ... t0 + s1 (the first of them arrived with chunk
     // c - 1), packs the images of exactly those levels (lc_field_pack on the sub-range: the level two chunks share is packed by
-    // both, same values) and continues the advection in place (lc_advect_from: LCS/trajectory.py:80-126 carries only the
+    // both, same values) and continues the advection in place (x_start / y_start: LCS/trajectory.py:80-126 carries only the
     // positions from level to level) -- bit-identical to the serial form.  While its kernels run on the context's stream, the
     // host threads and the DMA engine are already moving chunk c + 1.  Only the levels the call uses travel.
     // Serial form (one upload of the used levels, one pack, one advect): the reference's non-cyclic outer-product clamp (it
     // restarts the series), trajectories, the exact-order float64 form, orders other than 1 / 3, short series.
-    const size_t lvl_bytes = (size_t)ny_f * nx_f * es, le = lc_packed_elems(1, ny_f, nx_f);
     // Chunk lengths HALVE towards the end of the series (96 steps: 32, 24, 16, 12, 8, 4): what is left to compute when the last
     // upload lands is the last chunk alone, so it is the shortest; a chunk's kernels (0.07 ms per level on configs[2]) are done
     // well before the next, at least half as long, has travelled (0.14 ms per level).
     const int PIPE_LEVELS = 16, PIPE_LAST = 4;
-    const bool piped = hx && cyclic_x == LC_X_CYCLIC && ext.p && !traj_x && nsteps >= 2 * PIPE_LEVELS;
+    const bool piped = xfer.hx && cyclic_x == LC_X_CYCLIC && img.has_ext && !traj_x && nsteps >= 2 * PIPE_LEVELS;
     auto chunk_len = [&](int left) { return left <= PIPE_LAST ? left : std::max(PIPE_LAST, (left / 3 + 3) / 4 * 4); };
-    auto pack_levels = [&](int l0, int nlev) -> int {  // images of wind levels [l0, l0 + nlev), ext of [l0, l0 + nlev - 1)
-        const char *ul = (const char *)u.p + (size_t)l0 * lvl_bytes, *vl = (const char *)v.p + (size_t)l0 * lvl_bytes;
-        void *el = ext.p ? (char *)ext.p + (size_t)l0 * le * es : nullptr;
-        if (need_lin || (interp_order == 1 && ext.p))
-            LC_TRY(lc_field_pack(ctx, ul, vl, dtype, nlev, ny_f, nx_f, 1, lin.p ? (char *)lin.p + (size_t)l0 * le * es : nullptr,
-                                 interp_order == 1 ? el : nullptr));
-        if (interp_order != 1)
-            LC_TRY(lc_field_pack(ctx, ul, vl, dtype, nlev, ny_f, nx_f, interp_order, (char *)cub.p + (size_t)l0 * le * es, el));
-        return LC_OK;
+    auto up_levels = [&](int l0, int nlev) -> int {  // wind levels [l0, l0 + nlev) of both components
+        const size_t off = (size_t)l0 * lvl_bytes, n = (size_t)nlev * lvl_bytes;
+        LC_TRY(xfer.up((char *)u.p + off, (const char *)u_host + off, n));
+        LC_TRY(xfer.up((char *)v.p + off, (const char *)v_host + off, n));
+        return xfer.uploaded();
     };
+    lc_advect_args a = lc_whole_grid_args(wind, img.dev(), seeds, {timestep, settls_order, interp_order, cyclic_x});
+    a.x_out = x.p;
+    a.y_out = y.p;
     if (piped) {
         for (int s0 = 0, s1; s0 < nsteps; s0 = s1) {
             s1 = s0 + chunk_len(nsteps - s0);
             const int first = t0 + s0 + (s0 ? 1 : 0), last = t0 + s1;
-            LC_TRY(up((char *)u.p + (size_t)first * lvl_bytes, (const char *)u_host + (size_t)first * lvl_bytes, (size_t)(last - first + 1) * lvl_bytes));
-            LC_TRY(up((char *)v.p + (size_t)first * lvl_bytes, (const char *)v_host + (size_t)first * lvl_bytes, (size_t)(last - first + 1) * lvl_bytes));
-            LC_HIP_CHECK(hipEventRecord(ev_up, hx->copy));
-            LC_HIP_CHECK(hipStreamWaitEvent(st, ev_up, 0));
-            LC_TRY(pack_levels(t0 + s0, s1 - s0 + 1));
-            lc_advect_args a = {};
-            a.struct_size = sizeof(a);
-            a.packed_lin = lin.p;
-            a.packed_cub = cub.p;
-            a.packed_ext = ext.p;
-            a.u_raw = u.p;
-            a.v_raw = v.p;
-            a.dtype = dtype;
-            a.nt = nt;
-            a.ny_f = ny_f;
-            a.nx_f = nx_f;
-            a.lat_min = lat_min;
-            a.lat_max = lat_max;
-            a.lon_min = lon_min;
-            a.lon_max = lon_max;
-            a.seed_lat_dev = slat.p;
-            a.ny = ny;
-            a.seed_lon_dev = slon.p;
-            a.nx = nx;
-            a.row0 = 0;
-            a.ny_global = ny;
+            LC_TRY(up_levels(first, last - first + 1));
+            LC_TRY(img.pack(ctx, wind, t0 + s0, s1 - s0 + 1));
             a.x_start = s0 ? x.p : nullptr;
             a.y_start = s0 ? y.p : nullptr;
-            a.timestep = timestep;
-            a.settls_order = settls_order;
-            a.interp_order = interp_order;
-            a.cyclic_x = cyclic_x;
             a.t0 = t0 + s0;
             a.nsteps = s1 - s0;
-            a.n_members = 1;
-            a.x_out = x.p;
-            a.y_out = y.p;
             LC_TRY(lc_advect_ex(ctx, &a));
         }
     } else {
         // only the levels [t0, t0 + nsteps] are read (the pack of the whole series below touches the others' device memory:
         // they travel too unless the call uses a sub-range, in which case the images of the used levels alone are packed)
-        const bool sub = hx && nsteps >= 1 && (t0 > 0 || t0 + nsteps < nt - 1) && cyclic_x != LC_X_CLAMP_REFERENCE_OUTER;
+        const bool sub = xfer.hx && nsteps >= 1 && (t0 > 0 || t0 + nsteps < nt - 1) && cyclic_x != LC_X_CLAMP_REFERENCE_OUTER;
         const int l0 = sub ? t0 : 0, nlev = sub ? nsteps + 1 : nt;
-        LC_TRY(up((char *)u.p + (size_t)l0 * lvl_bytes, (const char *)u_host + (size_t)l0 * lvl_bytes, (size_t)nlev * lvl_bytes));
-        LC_TRY(up((char *)v.p + (size_t)l0 * lvl_bytes, (const char *)v_host + (size_t)l0 * lvl_bytes, (size_t)nlev * lvl_bytes));
-        if (hx) {
-            LC_HIP_CHECK(hipEventRecord(ev_up, hx->copy));
-            LC_HIP_CHECK(hipStreamWaitEvent(st, ev_up, 0));
-        }
-        LC_TRY(pack_levels(l0, nlev));
-        LC_TRY(advect_with_raw(ctx, lin.p, cub.p, ext.p, u.p, v.p, dtype, nt, ny_f, nx_f, lat_min, lat_max, lon_min, lon_max, slat.p, ny,
-                               slon.p, nx, timestep, settls_order, interp_order, cyclic_x, t0, nsteps, x.p, y.p, tx.p, ty.p));
+        LC_TRY(up_levels(l0, nlev));
+        LC_TRY(img.pack(ctx, wind, l0, nlev));
+        a.t0 = t0;
+        a.nsteps = nsteps;
+        a.traj_x = tx.p;
+        a.traj_y = ty.p;
+        LC_TRY(lc_advect_ex(ctx, &a));
     }
-    if (sigma_out) {
-        const void *xs = x.p, *ys = y.p;
-        if (gauss_sigma > 1e-15) {  // sigma = 0: scipy returns an unsmoothed copy
-            LC_TRY(gx.alloc(sbytes));
-            LC_TRY(gy.alloc(sbytes));
-            LC_TRY(gtmp.alloc(sbytes));
-            LC_TRY(lc_gaussian_filter(ctx, x.p, dtype, ny, nx, gauss_sigma, gtmp.p, gx.p));
-            LC_TRY(lc_gaussian_filter(ctx, y.p, dtype, ny, nx, gauss_sigma, gtmp.p, gy.p));
-            xs = gx.p;
-            ys = gy.p;
-        }
-        LC_TRY(lc_sigma(ctx, xs, ys, dtype, 0, ny, nx, ny, slat.p, dlat, dlon, fd_fp32_cast, tensor_layout, 0, ny,
-                        sig.p));
-    }
-    t_up = ms_since();
-    // ---- results down: the departure points travel while nothing else does; sigma (0.07 ms of kernel) last ---------------
-    if (hx) {
-        LC_HIP_CHECK(hipEventRecord(ev_done, st));
-        LC_HIP_CHECK(hipStreamWaitEvent(hx->copy, ev_done, 0));
-        touch.join();
-        LC_HIP_CHECK(hipEventSynchronize(ev_done));   // (the first download DMA waits for this event anyway: the host has nothing else to do)
-        t_kernels = ms_since();
-    }
-    {
-        std::vector<lc_host_xfer::Range> res;
-        if (x_out) res.push_back({x_out, x.p, sbytes});
-        if (y_out) res.push_back({y_out, y.p, sbytes});
-        if (sigma_out) res.push_back({sigma_out, sig.p, sbytes});
-        if (traj_x) {
-            res.push_back({traj_x, tx.p, sbytes * (size_t)(nsteps + 1)});
-            res.push_back({traj_y, ty.p, sbytes * (size_t)(nsteps + 1)});
-        }
-        if (hx) {
-            LC_HIP_CHECK(hx->download(res));   // one pipelined sequence of pieces over all of them
-        } else {
-            for (auto &r : res) LC_TRY(down(r.host, r.dev, r.bytes));
-        }
-    }
+
+    // ---- sigma stage ---------------------------------------------------------------------------------------------------------------
+    if (sigma_out) LC_TRY(sigma.run(ctx, x.p, y.p, dtype, seeds, gauss_sigma, fd_fp32_cast, tensor_layout));
+    const double t_up = ms_since();
+
+    // ---- results down --------------------------------------------------------------------------------------------------------------
+    LC_TRY(xfer.kernels_done());
+    if (xfer.hx) t_kernels = ms_since();
+    LC_TRY(xfer.down(results));
     LC_HIP_CHECK(hipStreamSynchronize(st));
+
+    // ---- marks -----------------------------------------------------------------------------------------------------------------------
     ctx->host_marks[0] = t_alloc;
     ctx->host_marks[1] = t_up;
-    ctx->host_marks[2] = hx ? t_kernels : 0.0;
+    ctx->host_marks[2] = t_kernels;
     ctx->host_marks[3] = ms_since();
     if (ctx->host_timing)
         std::fprintf(stderr, "lc_lcs_host: %s, buffers allocated %.2f ms, uploads and launches issued %.2f, kernels done %.2f, results down %.2f"
                              " (download: %.2f waiting for DMAs, %.2f copying out of the ring)\n",
-                     piped ? "pipelined" : (hx ? "staged" : "plain copies"), t_alloc, t_up, t_kernels, ms_since(),
-                     hx ? hx->last_down_wait_ms : 0.0, hx ? hx->last_down_copy_ms : 0.0);
-    return LC_OK;  // `drain` waits for both streams, then the DevBuf destructors free
+                     piped ? "pipelined" : (xfer.hx ? "staged" : "plain copies"), t_alloc, t_up, t_kernels, ms_since(),
+                     xfer.hx ? xfer.hx->last_down_wait_ms : 0.0, xfer.hx ? xfer.hx->last_down_copy_ms : 0.0);
+    return LC_OK;  // `xfer` waits for both streams, then the DevBuf destructors free
 }
 
 // ---------------------------------------------------------------------------
@@ -971,7 +922,9 @@ extern "C" int lc_lcs_global_host(lc_ctx *ctx, const void *u_host, const void *v
     if (truncation >= 0) LC_TRY(lc_inspect_gridtype(lat.data(), ny, &gridtype));  // windspharm's grid inspection, LCS.py:116 via VectorWind
     const size_t es = wdtype == LC_F32 ? 4 : 8;
     const size_t nw = (size_t)nt * ny * nx, sbytes = (size_t)ny * nx * es;
-    DevBuf uin, vin, ur, vr, ut, vt, lin, cub, ext, slat, slon, x, y, sig, gx, gy, gtmp;
+    DevBuf uin, vin, ur, vr, ut, vt, slat, slon, x, y;
+    HostImages img(ctx, nullptr, wdtype, interp_order, settls_order, ny, nx);
+    SigmaStage sigma(nullptr);
     LC_TRY(uin.alloc(nin * es_in));
     LC_TRY(vin.alloc(nin * es_in));
     LC_HIP_CHECK(hipMemcpyAsync(uin.p, u_host, nin * es_in, hipMemcpyHostToDevice, st));
@@ -1006,39 +959,22 @@ extern "C" int lc_lcs_global_host(lc_ctx *ctx, const void *u_host, const void *v
     LC_HIP_CHECK(hipMemcpyAsync(slat.p, hl.data(), ny * es, hipMemcpyHostToDevice, st));
     LC_HIP_CHECK(hipMemcpyAsync(slon.p, ho.data(), nx * es, hipMemcpyHostToDevice, st));
     LC_HIP_CHECK(hipStreamSynchronize(st));  // hl / ho are pageable locals
-    const size_t pbytes = lc_packed_elems(nt, ny, nx) * es;
-    const bool need_lin = host_route_needs_lin(wdtype, interp_order);
-    if (need_lin) LC_TRY(lin.alloc(pbytes));
-    if (interp_order != 1) LC_TRY(cub.alloc(pbytes));
-    const bool fusable = (interp_order == 1 || interp_order == 3) && !f64_exact_order(ctx, wdtype, ny, nx);
-    if (settls_order > 0 && fusable) LC_TRY(ext.alloc(lc_packed_elems(nt - 1, ny, nx) * es));
-    if (need_lin || (interp_order == 1 && ext.p))
-        LC_TRY(lc_field_pack(ctx, uw, vw, wdtype, nt, ny, nx, 1, lin.p, interp_order == 1 ? ext.p : nullptr));
-    if (interp_order != 1) LC_TRY(lc_field_pack(ctx, uw, vw, wdtype, nt, ny, nx, interp_order, cub.p, ext.p));
+    const CoordAxis la = coord_axis(hl.data(), ny, wdtype), lo = coord_axis(ho.data(), nx, wdtype);
+    const lc_dev_wind wind = {uw, vw, wdtype, nt, ny, nx, la.first, la.last, lo.first, lo.last};
+    const lc_dev_seeds seeds = {slat.p, slon.p, ny, nx, la.step, lo.step};
+    LC_TRY(img.alloc(wind));
+    LC_TRY(img.pack(ctx, wind, 0, nt));
     LC_TRY(x.alloc(sbytes));
     LC_TRY(y.alloc(sbytes));
-    const double lat_min = wdtype == LC_F32 ? (double)(float)lat[0] : lat[0], lat_max = wdtype == LC_F32 ? (double)(float)lat[ny - 1] : lat[ny - 1];
-    const double lon_min = wdtype == LC_F32 ? (double)(float)lon[0] : lon[0], lon_max = wdtype == LC_F32 ? (double)(float)lon[nx - 1] : lon[nx - 1];
-    LC_TRY(advect_with_raw(ctx, lin.p, cub.p, ext.p, uw, vw, wdtype, nt, ny, nx, lat_min, lat_max, lon_min, lon_max, slat.p, ny,
-                           slon.p, nx, timestep, settls_order, interp_order, LC_X_CYCLIC /* LCS.py:119 */, 0, nt - 1, x.p, y.p,
-                           nullptr, nullptr));
+    lc_advect_args a = lc_whole_grid_args(wind, img.dev(), seeds, {timestep, settls_order, interp_order, LC_X_CYCLIC /* LCS.py:119 */});
+    a.nsteps = nt - 1;
+    a.x_out = x.p;
+    a.y_out = y.p;
+    LC_TRY(lc_advect_ex(ctx, &a));
     if (sigma_out) {
         LC_REQUIRE(ny >= 5 && nx >= 5, "lc_lcs_global_host: sigma needs at least a 5x5 grid");
-        LC_TRY(sig.alloc(sbytes));
-        const void *xs = x.p, *ys = y.p;
-        if (gauss_sigma > 1e-15) {
-            LC_TRY(gx.alloc(sbytes));
-            LC_TRY(gy.alloc(sbytes));
-            LC_TRY(gtmp.alloc(sbytes));
-            LC_TRY(lc_gaussian_filter(ctx, x.p, wdtype, ny, nx, gauss_sigma, gtmp.p, gx.p));
-            LC_TRY(lc_gaussian_filter(ctx, y.p, wdtype, ny, nx, gauss_sigma, gtmp.p, gy.p));
-            xs = gx.p;
-            ys = gy.p;
-        }
-        const double dlat = wdtype == LC_F32 ? (double)((float)lat[1] - (float)lat[0]) : lat[1] - lat[0];
-        const double dlon = wdtype == LC_F32 ? (double)((float)lon[1] - (float)lon[0]) : lon[1] - lon[0];
-        LC_TRY(lc_sigma(ctx, xs, ys, wdtype, 0, ny, nx, ny, slat.p, dlat, dlon, fd_fp32_cast, tensor_layout, 0, ny, sig.p));
-        LC_HIP_CHECK(hipMemcpyAsync(sigma_out, sig.p, sbytes, hipMemcpyDeviceToHost, st));
+        LC_TRY(sigma.run(ctx, x.p, y.p, wdtype, seeds, gauss_sigma, fd_fp32_cast, tensor_layout));
+        LC_HIP_CHECK(hipMemcpyAsync(sigma_out, sigma.sig.p, sbytes, hipMemcpyDeviceToHost, st));
     }
     if (x_out) LC_HIP_CHECK(hipMemcpyAsync(x_out, x.p, sbytes, hipMemcpyDeviceToHost, st));
     if (y_out) LC_HIP_CHECK(hipMemcpyAsync(y_out, y.p, sbytes, hipMemcpyDeviceToHost, st));

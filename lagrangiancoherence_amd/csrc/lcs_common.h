@@ -81,6 +81,60 @@ static inline size_t lc_level_elems(int ny_f, int nx_f) {
     return (size_t)(ny_f + LC_PAD) * (size_t)(nx_f + LC_PAD) * 2;
 }
 
+// A wind on the device, a seed grid on the device, the packed images of the wind (NULL where there is none) and the path's
+// options: what a whole-grid advect call is described by.  The coordinate extremes are rounded to the wind's dtype; dlat / dlon
+// are the seed spacings as numpy evaluates lat[1] - lat[0] in the coordinate dtype (lc_sigma's; lc_advect does not read them).
+struct lc_dev_wind {
+    const void *u, *v;  // the raw planes [nt][ny_f][nx_f], or NULL
+    int dtype, nt, ny_f, nx_f;
+    double lat_min, lat_max, lon_min, lon_max;
+};
+struct lc_dev_seeds {
+    const void *lat, *lon;
+    int ny, nx;
+    double dlat, dlon;
+};
+struct lc_dev_images {
+    const void *lin, *cub, *ext;
+};
+struct lc_path_options {
+    double timestep;
+    int settls_order, interp_order, cyclic_x;
+};
+
+// lc_advect_args of one member over the whole seed grid from level 0, zero steps, no outputs: a caller sets what its call
+// differs in (t0, nsteps, x_start / y_start, n_members, t0_stride, a row block, the outputs and trajectories).  The one fill
+// of the structure in the library (lc_advect_batch, the one-call host routes): a new field is given its value here.
+static inline lc_advect_args lc_whole_grid_args(const lc_dev_wind &w, const lc_dev_images &img, const lc_dev_seeds &s,
+                                                const lc_path_options &o) {
+    lc_advect_args a = {};
+    a.struct_size = sizeof(a);
+    a.packed_lin = img.lin;
+    a.packed_cub = img.cub;
+    a.packed_ext = img.ext;
+    a.u_raw = w.u;
+    a.v_raw = w.v;
+    a.dtype = w.dtype;
+    a.nt = w.nt;
+    a.ny_f = w.ny_f;
+    a.nx_f = w.nx_f;
+    a.lat_min = w.lat_min;
+    a.lat_max = w.lat_max;
+    a.lon_min = w.lon_min;
+    a.lon_max = w.lon_max;
+    a.seed_lat_dev = s.lat;
+    a.ny = s.ny;
+    a.seed_lon_dev = s.lon;
+    a.nx = s.nx;
+    a.ny_global = s.ny;
+    a.timestep = o.timestep;
+    a.settls_order = o.settls_order;
+    a.interp_order = o.interp_order;
+    a.cyclic_x = o.cyclic_x;
+    a.n_members = 1;
+    return a;
+}
+
 // kernel launchers implemented in the .hip files
 int lc_launch_pack(lc_ctx *ctx, const void *u, const void *v, int dtype, int nt, int ny_f, int nx_f,
                    int order, void *packed, void *ext);
