@@ -38,7 +38,7 @@ extern "C" {
  * client built against 100 must be rebuilt), lc_ctx_get_level_chunk, lc_ctx_set/get_f64_fidelity, lc_advect_ex and
  * lc_sample_raw added, lc_field_pack accepts packed_dev == NULL at order 1 (fused-level image only).  lc_version() returns the value the LIBRARY
  * was built with: compare it with this macro before any other call (tests/c/abi_smoke.c, _capi.load do). */
-#define LC_VERSION 104 /* 0.1.4: + lc_strain, lc_ctx_last_strain_kernel, + lc_advect_series_dirs, + lc_advect_series, lc_sigma_batch, + lc_tracer_sample, lc_ctx_last_tracer_kernel (additive: no argument list changed), + lc_ctx_set_host_pipeline, lc_copy_to_device, lc_copy_to_host, lc_ctx_set_host_cache, lc_ctx_trim, lc_ctx_last_host_marks, lc_ctx_set_xcd_split (0.1.3: + lc_ctx_last_pack_kernel; 0.1.2: + lc_ctx_set_verify, lc_ctx_read_verify, LC_F64_WIND_F32_LIN32) */
+#define LC_VERSION 104 /* 0.1.4: + lc_label_components, lc_label_work_elems, lc_component_sums, lc_component_apply, + lc_strain, lc_ctx_last_strain_kernel, + lc_advect_series_dirs, + lc_advect_series, lc_sigma_batch, + lc_tracer_sample, lc_ctx_last_tracer_kernel (additive: no argument list changed), + lc_ctx_set_host_pipeline, lc_copy_to_device, lc_copy_to_host, lc_ctx_set_host_cache, lc_ctx_trim, lc_ctx_last_host_marks, lc_ctx_set_xcd_split (0.1.3: + lc_ctx_last_pack_kernel; 0.1.2: + lc_ctx_set_verify, lc_ctx_read_verify, LC_F64_WIND_F32_LIN32) */
 
 typedef struct lc_ctx lc_ctx;
 
@@ -587,6 +587,53 @@ int lc_gaussian_filter(lc_ctx *ctx, const void *in_dev, int dtype, int ny, int n
 int lc_ridge_classify(lc_ctx *ctx, const void *hxx, const void *hxy, const void *hyy,
                       const void *gx, const void *gy, size_t n, double tolerance,
                       void *mask_out, void *eigmin_out, void *dt_out, void *eigvec_out);
+
+/* ---- connected components of a ridge mask (filter_ridges) ----------------------------
+ * What the driver does with the raw mask before it uses it (LCS/area_of_influence.py:210-242): label its connected
+ * components, measure each, keep those that pass a threshold.  The function the driver imports for it comes from a package
+ * outside the reference, so the meaning is fixed here; scipy.ndimage.label and numpy are what it is tested against.
+ * n_members independent planes [n_members][ny*nx] per call, every stage one launch for all of them.
+ *
+ * Foreground: a pixel whose value is != 0 and not NaN (negative values are foreground).  mask: `dtype` elements, LC_F32 or
+ * LC_F64.  A plane of 2^31 pixels or more is refused.
+ *
+ * lc_label_components
+ *   connectivity  1: pixels that share an edge; 2: an edge or a corner (scipy's generate_binary_structure(2, connectivity))
+ *   cyclic_x      != 0: column nx-1 is the western neighbour of column 0 (rows r-1 .. r+1 at connectivity 2)
+ *   labels_out    int32 [n_members][ny*nx]: 0 on background, else 1 .. N, the components of each plane numbered in the order of
+ *                 their first pixel in raster order -- the numbering of scipy.ndimage.label
+ *   counts_out    int32 [n_members]: N of each plane
+ *   work_dev      int32 [lc_label_work_elems(ny, nx, n_members)] scratch (0 elements for bad sizes)
+ * No kernel of these calls waits for another workgroup. */
+size_t lc_label_work_elems(int ny, int nx, int n_members);
+int lc_label_components(lc_ctx *ctx, const void *mask, int dtype, int ny, int nx, int n_members,
+                        int connectivity, int cyclic_x, void *labels_out, void *counts_out, void *work_dev);
+
+/* Sums over the pixels of every component, per compact label: entry [m][l-1] belongs to label l of plane m; labels above
+ * min(counts[m], n_max) are not measured, entries without a component hold area 0, root -1 and NaN extrema.
+ *   root_out     int32: the component's first pixel in raster order, as a linear index into its plane
+ *   area_out     int64: pixels
+ *   moments_out  int64 [5][n_members][n_max]: sums of dr, dc, dr^2, dr*dc, dc^2 with dr = row - row of the root, dc = column -
+ *                column of the root; with cyclic_x dc is first wrapped into [-(nx/2), nx - nx/2).  Exact.
+ *   sum_out      float64: sum of the intensity (order of summation not fixed: last bits may differ from run to run)
+ *   max_out, min_out  float64: extrema of the intensity, exact; NaN if the component holds a NaN (its sum is NaN too)
+ * intensity: `dtype` elements [n_members][ny*nx], or NULL: sum_out, max_out and min_out are then not written and may be NULL. */
+typedef struct lc_component_sums_args {
+    size_t struct_size; /* sizeof(lc_component_sums_args): checked first */
+    const void *labels; /* int32 [n_members][ny*nx], as lc_label_components wrote them */
+    const void *counts; /* int32 [n_members] */
+    const void *intensity;
+    int dtype, ny, nx, n_members;
+    int cyclic_x;
+    int n_max; /* capacity per plane of every output */
+    void *root_out, *area_out, *moments_out, *sum_out, *max_out, *min_out;
+} lc_component_sums_args;
+int lc_component_sums(lc_ctx *ctx, const lc_component_sums_args *args);
+
+/* mask_out[p] = mask[p] where keep[m][label[p]-1] != 0, else fill (on background pixels and on labels above n_max too).
+ * keep: uint8 [n_members][n_max]; mask, mask_out: `dtype` elements, two distinct buffers. */
+int lc_component_apply(lc_ctx *ctx, const void *labels, const void *mask, int dtype, int ny, int nx, int n_members,
+                       const void *keep, int n_max, double fill, void *mask_out);
 
 /* ---- multi-GPU: halo exchange on RCCL ----------------------------------------
  * New (the reference is single-process).  One process per GPU,

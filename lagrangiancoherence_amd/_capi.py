@@ -133,6 +133,22 @@ class TracerArgs(C.Structure):
 
 PROTOTYPES["lc_tracer_sample"] = (_i, [_vp, C.POINTER(TracerArgs)])
 
+
+class ComponentSumsArgs(C.Structure):
+    """``lc_component_sums_args`` of include/lcs_hip.h, field for field."""
+    _fields_ = [("struct_size", _sz),
+                ("labels", _vp), ("counts", _vp), ("intensity", _vp),
+                ("dtype", _i), ("ny", _i), ("nx", _i), ("n_members", _i),
+                ("cyclic_x", _i), ("n_max", _i),
+                ("root_out", _vp), ("area_out", _vp), ("moments_out", _vp),
+                ("sum_out", _vp), ("max_out", _vp), ("min_out", _vp)]
+
+
+PROTOTYPES["lc_label_work_elems"] = (_sz, [_i, _i, _i])
+PROTOTYPES["lc_label_components"] = (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp])
+PROTOTYPES["lc_component_sums"] = (_i, [_vp, C.POINTER(ComponentSumsArgs)])
+PROTOTYPES["lc_component_apply"] = (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _d, _vp])
+
 _lib = None
 
 

@@ -904,6 +904,143 @@ class Engine:
                                                self._ptr(vec) if return_eigvec else None), self.lib)
         return (mask, eigmin, dt, vec) if return_eigvec else (mask, eigmin, dt)
 
+    # ------------------------------------------------------------------ connected components of a mask (filter_ridges)
+    COMPONENT_PROPS = ("area", "mean_intensity", "max_intensity", "min_intensity", "major_axis_length", "minor_axis_length")
+
+    def _planes(self, a, dtype=None):
+        """``a`` (2-D, or 3-D with a leading member dimension) on the device as ``(n_members, ny, nx)``; ``dtype`` None: its own
+        (float32 / float64 kept, anything else float64)."""
+        if dtype is None:
+            dtype = np.dtype(str(a.dtype).replace("torch.", ""))
+            dtype = dtype if dtype in _NP2LC else np.dtype(np.float64)
+        t = self.to_device(a, dtype)
+        if t.dim() not in (2, 3) or t.numel() == 0:
+            raise ValueError("a plane (ny, nx) or a stack of planes (n_members, ny, nx), none of them empty")
+        return t if t.dim() == 3 else t[None]
+
+    def label_components(self, mask, connectivity=2, cyclic=False):
+        """Connected components of ``mask`` (``lc_label_components``): ``(labels, counts)``.
+
+        A pixel is foreground when it is ``!= 0`` and not NaN.  ``labels``: int32 device tensor shaped like ``mask`` --
+        ``(ny, nx)``, or ``(n_members, ny, nx)``, every plane labelled on its own in the same launches -- 0 on background,
+        else ``1..N`` in the order of each component's first pixel in raster order: ``scipy.ndimage.label(mask,
+        generate_binary_structure(2, connectivity))``'s numbering.  ``counts``: int32 ``(n_members,)``, N of each plane.
+        ``cyclic``: the last column is the western neighbour of the first (a global longitude axis)."""
+        m = self._planes(mask)
+        n, ny, nx = (int(s) for s in m.shape)
+        labels = self.torch.empty((n, ny, nx), dtype=self.torch.int32, device=self.device)
+        counts = self.torch.empty((n,), dtype=self.torch.int32, device=self.device)
+        work = self.torch.empty((max(1, int(self.lib.lc_label_work_elems(ny, nx, n))),), dtype=self.torch.int32, device=self.device)
+        self._use_current_stream()
+        _capi.check(self.lib.lc_label_components(self.ctx, self._ptr(m), _NP2LC[np.dtype(str(m.dtype).replace("torch.", ""))], ny, nx, n,
+                                                 int(connectivity), int(bool(cyclic)), self._ptr(labels), self._ptr(counts),
+                                                 self._ptr(work)), self.lib)
+        return (labels if len(mask.shape) == 3 else labels[0]), counts
+
+    def component_sums(self, labels, counts, intensity=None, cyclic=False, n_max=None):
+        """``lc_component_sums``: the exact per-component sums :meth:`component_props` is computed from, as a dict of device
+        tensors ``(n_members, n_max)`` -- ``root`` (int32, first pixel), ``area`` (int64), ``moments`` (int64, ``(5, n_members,
+        n_max)``: sums of dr, dc, dr^2, dr dc, dc^2 about the root pixel) and, with an ``intensity``, ``sum``, ``max``, ``min``
+        (float64).  ``n_max`` None: the largest count, read back from the device (one synchronisation)."""
+        torch = self.torch
+        lab = labels if labels.dim() == 3 else labels[None]
+        if lab.dtype != torch.int32 or not lab.is_contiguous():
+            raise ValueError("labels: the int32 tensor label_components returned")
+        n, ny, nx = (int(s) for s in lab.shape)
+        if n_max is None:
+            n_max = int(counts.max().item())
+        n_max = max(1, int(n_max))
+        inten = None
+        if intensity is not None:
+            inten = self._planes(intensity)
+            if tuple(inten.shape) != (n, ny, nx):
+                raise ValueError("intensity and labels differ in shape")
+        out = {"root": torch.empty((n, n_max), dtype=torch.int32, device=self.device),
+               "area": torch.empty((n, n_max), dtype=torch.int64, device=self.device),
+               "moments": torch.empty((5, n, n_max), dtype=torch.int64, device=self.device)}
+        if inten is not None:
+            out.update({k: self._empty((n, n_max), np.float64) for k in ("sum", "max", "min")})
+        a = _capi.ComponentSumsArgs(struct_size=C.sizeof(_capi.ComponentSumsArgs))
+        a.labels, a.counts, a.intensity = lab.data_ptr(), counts.data_ptr(), inten.data_ptr() if inten is not None else None
+        a.dtype = _NP2LC[np.dtype(str(inten.dtype).replace("torch.", ""))] if inten is not None else _capi.LC_F64
+        a.ny, a.nx, a.n_members, a.cyclic_x, a.n_max = ny, nx, n, int(bool(cyclic)), n_max
+        a.root_out, a.area_out, a.moments_out = (out[k].data_ptr() for k in ("root", "area", "moments"))
+        if inten is not None:
+            a.sum_out, a.max_out, a.min_out = (out[k].data_ptr() for k in ("sum", "max", "min"))
+        self._use_current_stream()
+        _capi.check(self.lib.lc_component_sums(self.ctx, C.byref(a)), self.lib)
+        return out
+
+    def component_props(self, labels, counts, intensity=None, cyclic=False):
+        """Properties of every component of :meth:`label_components`' result, as a dict of float64 device tensors ``(n_max,)``
+        (``(n_members, n_max)`` for a stack; ``n_max`` = the largest count; entries past a plane's own count are NaN, area 0):
+
+        ``area`` (int64), ``mean_intensity``, ``max_intensity``, ``min_intensity`` (NaN for all three where the component holds
+        a NaN; present with an ``intensity``), ``centroid`` (``(..., 2)``: row, column), ``major_axis_length``,
+        ``minor_axis_length`` and ``axis_moments`` (``(..., 2)``: the ``l1, l2`` below).
+
+        The axis lengths are DEFINED here by formula -- the one ``skimage.measure.regionprops`` documents; skimage is not at
+        hand to check against: with the central moments per pixel ``a = mu_rr / area, b = mu_rc / area, c = mu_cc / area``,
+        ``l1, l2 = (a + c) / 2 +- sqrt(((a - c) / 2)^2 + b^2)``, ``major = 4 sqrt(l1)``, ``minor = 4 sqrt(max(l2, 0))``, in index
+        units.  The moments come from exact integer sums about each component's first pixel (``mu_rr = sum dr^2 -
+        (sum dr)^2 / area``): nothing large is subtracted from anything large.  ``cyclic``: column offsets are taken the shorter
+        way round, so a component that straddles the seam is measured as the one piece it is."""
+        torch = self.torch
+        s = self.component_sums(labels, counts, intensity, cyclic)
+        nx = int(labels.shape[-1])
+        area = s["area"]
+        valid = area > 0
+        nan = torch.full(area.shape, float("nan"), dtype=torch.float64, device=self.device)
+        n = torch.where(valid, area, torch.ones_like(area)).to(torch.float64)
+        sr, sc, srr, src, scc = (m.to(torch.float64) for m in s["moments"])
+        a = (srr - sr * sr / n) / n
+        b = (src - sr * sc / n) / n
+        c = (scc - sc * sc / n) / n
+        mid, rad = (a + c) / 2, torch.sqrt(((a - c) / 2) ** 2 + b * b)
+        l1, l2 = mid + rad, mid - rad
+        root = s["root"].clamp(min=0)
+        row = torch.div(root, nx, rounding_mode="floor")
+        col = (root - row * nx).to(torch.float64) + sc / n
+        if cyclic:
+            col = torch.remainder(col, float(nx))
+        props = {"area": area,
+                 "centroid": torch.where(valid[..., None], torch.stack([row.to(torch.float64) + sr / n, col], dim=-1), nan[..., None]),
+                 "major_axis_length": torch.where(valid, 4 * torch.sqrt(l1), nan),
+                 "minor_axis_length": torch.where(valid, 4 * torch.sqrt(l2.clamp(min=0)), nan),
+                 "axis_moments": torch.where(valid[..., None], torch.stack([l1, l2], dim=-1), nan[..., None])}
+        if intensity is not None:
+            props.update(mean_intensity=torch.where(valid, s["sum"] / n, nan), max_intensity=s["max"], min_intensity=s["min"])
+        return props if labels.dim() == 3 else {k: v[0] for k, v in props.items()}
+
+    def filter_components(self, mask, intensity, criteria, thresholds, connectivity=2, cyclic=False, fill=0.0):
+        """``mask`` with every connected component that fails a threshold replaced by ``fill`` (background becomes ``fill``
+        too): a component is kept when ``prop >= threshold`` for every ``(criterion, threshold)`` pair -- criteria from
+        :attr:`COMPONENT_PROPS`, measured on ``intensity`` -- and a NaN property fails.  Label, sums and apply run on the
+        device (``lc_label_components``, ``lc_component_sums``, ``lc_component_apply``); the counts are read back once in
+        between, to size the per-component arrays.  Returns a device tensor shaped and typed like ``mask``."""
+        criteria, thresholds = list(criteria), list(thresholds)
+        if len(criteria) != len(thresholds):
+            raise ValueError("criteria and thresholds differ in length")
+        for k in criteria:
+            if k not in self.COMPONENT_PROPS:
+                raise ValueError(f"criterion {k!r}: one of {', '.join(self.COMPONENT_PROPS)}")
+            if intensity is None and k.endswith("_intensity"):
+                raise ValueError(f"criterion {k!r} needs an intensity")
+        torch = self.torch
+        m = self._planes(mask)
+        n, ny, nx = (int(s) for s in m.shape)
+        labels, counts = self.label_components(m, connectivity, cyclic)
+        props = self.component_props(labels, counts, intensity, cyclic)
+        keep = props["area"] > 0
+        for k, th in zip(criteria, thresholds):
+            keep = keep & (props[k] >= float(th))          # a NaN compares False
+        keep = keep.to(torch.uint8).contiguous()
+        out = self._empty((n, ny, nx), np.dtype(str(m.dtype).replace("torch.", "")))
+        self._use_current_stream()
+        _capi.check(self.lib.lc_component_apply(self.ctx, self._ptr(labels), self._ptr(m), _NP2LC[np.dtype(str(m.dtype).replace("torch.", ""))],
+                                                ny, nx, n, self._ptr(keep), int(keep.shape[1]), float(fill), self._ptr(out)), self.lib)
+        return out if len(mask.shape) == 3 else out[0]
+
     # ------------------------------------------------------------------ multi-GPU (RCCL through the C ABI)
     COMM_ID_BYTES = 128
 

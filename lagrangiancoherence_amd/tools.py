@@ -5,6 +5,8 @@
 * ``fourth_order_derivative``      LCS/tools.py:190-245 (plain arrays in the reference)
 
 * ``find_ridges_spherical_hessian`` LCS/tools.py:52-155 (the consumer of the FTLE field)
+* ``filter_ridges``                 the filter LCS/area_of_influence.py:210-242 passes every raw mask through (imported there
+                                    from a package outside the reference: defined here, see its docstring)
 
 The remaining functions of that module (IDW regridding, harvesine, latlonsel) have no caller on the
 path.
@@ -17,7 +19,7 @@ from .dropin import _coord, _make, _to_np, get_engine
 from .engine import common_dtype
 
 __all__ = ["xr_map_coordinates", "fourth_order_derivative", "derivative_spherical_coords",
-           "find_ridges_spherical_hessian"]
+           "find_ridges_spherical_hessian", "filter_ridges"]
 
 
 def xr_map_coordinates(da, new_x, new_y, isglobal=True, order=1):
@@ -121,3 +123,44 @@ def find_ridges_spherical_hessian(da, sigma=.5, scheme='first_order', tolerance_
     vec_masked = torch.where((eigmin < 0)[None], vec, torch.zeros_like(vec))           # tools.py:133
     return (out(mask), out(eigmin), out(dt), out(vec_masked, "eigvectors", ["d2dadxdy", "d2dadydx"]),
             out(torch.stack([ddadx, ddady]), "elements", ["ddadx", "ddady"]), out(angle))
+
+
+def filter_ridges(ridges, ftle, criteria, thresholds, verbose=True, connectivity=2, cyclic=False, fill=0.0):
+    """Keep the connected components of ``ridges`` whose properties, measured on ``ftle``, reach the thresholds.
+    The call LCS/area_of_influence.py:210-211 makes: ``filter_ridges(ridges, ftle, criteria=['mean_intensity',
+    'major_axis_length'], thresholds=[1.2, 30])``.
+
+    ``ridges`` and ``ftle`` are labelled arrays over the same ``latitude`` and ``longitude`` (sorted ascending here, as
+    ``find_ridges_spherical_hessian`` sorts), 2-D, or 3-D with one more dimension (time, member): every plane is then filtered
+    on its own, all of them in the same kernel launches.  A pixel is part of a ridge when it is ``!= 0`` and not NaN;
+    components are joined over edges (``connectivity=1``) or edges and corners (``2``), and with ``cyclic`` across the seam
+    of a global longitude axis.  ``criteria``: names out of ``area``, ``mean_intensity``, ``max_intensity``,
+    ``min_intensity``, ``major_axis_length``, ``minor_axis_length`` (index units; ``Engine.component_props`` states the
+    formulas); a component is kept when every property is ``>=`` its threshold, a NaN property fails.  Pixels of dropped
+    components and the background become ``fill``: ``fill=np.nan`` is the form the driver's next line expects
+    (``ridges.where(~isnan(ridges), 0)``).  ``verbose`` is accepted for the driver's signature.
+
+    Returns the filtered mask in the caller's class and dimension order, in ``ridges``' dtype (float64 unless float32)."""
+    dims = tuple(ridges.dims)
+    lead = [d for d in dims if d not in ("latitude", "longitude")]
+    if len(lead) > 1 or len(dims) - len(lead) != 2:
+        raise ValueError("ridges: dims (latitude, longitude) and at most one more")
+    if set(ftle.dims) != set(dims):
+        raise ValueError("ridges and ftle differ in their dims")
+    order = (*lead, "latitude", "longitude")
+    lat, lon = _coord(ridges, "latitude"), _coord(ridges, "longitude")
+    if not (np.array_equal(_coord(ftle, "latitude"), lat) and np.array_equal(_coord(ftle, "longitude"), lon)):
+        raise ValueError("ridges and ftle differ in their coordinates")
+    ilat, ilon = np.argsort(lat, kind="stable"), np.argsort(lon, kind="stable")
+
+    def sorted_values(da):
+        v = np.asarray(da.transpose(*order).values)
+        v = v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)
+        return np.ascontiguousarray(v[..., ilat, :][..., ilon])
+    eng = get_engine()
+    out = eng.filter_components(sorted_values(ridges), sorted_values(ftle), criteria, thresholds, connectivity=connectivity,
+                                cyclic=cyclic, fill=fill)
+    coords = {"latitude": lat[ilat], "longitude": lon[ilon]}
+    if lead:
+        coords[lead[0]] = _coord(ridges, lead[0])
+    return _make(ridges, _to_np(out), order, coords, getattr(ridges, "name", None)).transpose(*dims)
