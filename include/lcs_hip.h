@@ -635,6 +635,41 @@ int lc_component_sums(lc_ctx *ctx, const lc_component_sums_args *args);
 int lc_component_apply(lc_ctx *ctx, const void *labels, const void *mask, int dtype, int ny, int nx, int n_members,
                        const void *keep, int n_max, double fill, void *mask_out);
 
+/* ---- distance to the nearest ridge pixel (exact Euclidean distance transform) ----------
+ * The driver's next step after the filter (LCS/area_of_influence.py:231): scipy.ndimage.distance_transform_edt(~ridges_bool),
+ * of which it keeps `dist < 12` as the swath a ridge influences.  n_members independent planes [n_members][ny*nx] per call.
+ *
+ * Foreground: as above, a pixel whose value is != 0 and not NaN; mask: `dtype` elements, LC_F32 or LC_F64.
+ *   dist_out     float64 [n_members][ny*nx]: 0 on foreground, elsewhere sqrt of the smallest
+ *                cost = (dr * sampling_y)^2 + (dc * sampling_x)^2 over the foreground pixels, every product, the sum and the
+ *                root rounded once to float64 and nothing fused -- scipy's expression, and equal to its result bit for bit.
+ *                With cyclic_x the column offset is min(|dc|, nx - |dc|).
+ *   nearest_out  int32 [n_members][ny*nx], or NULL: the linear index into its plane of the foreground pixel that cost belongs
+ *                to (a pixel's own index on foreground).  Tie rule: among pixels of equal cost the smallest linear index.
+ *                (Inside a column the two candidates at equal |dr| go to the smaller row; the rule holds as long as different
+ *                |dr| of one column never round to one cost, i.e. (ny sy)^2 + (nx sx)^2 < 2^52 sy^2: any plane a user has.)
+ *   empty plane  a plane without a foreground pixel is +inf everywhere, nearest -1: our definition, scipy's answer there
+ *                has no meaning.
+ *   max_distance > 0: the result equals the unbounded one where that is <= max_distance and is +inf, nearest -1, elsewhere;
+ *                the search of every pixel ends at that radius.  <= 0: unbounded.
+ *   work_dev     int32 [lc_distance_work_elems(ny, nx, n_members)] scratch (0 elements for bad sizes)
+ * Width limit: nx <= 16384 (a row of int32 offsets is staged in LDS: 64 KiB, two workgroups per CU); a wider plane is refused
+ * with LC_EUNSUPPORTED, a plane of 2^31 pixels or more with LC_EINVAL, both before any HIP call.
+ * No kernel of this call waits for another workgroup. */
+size_t lc_distance_work_elems(int ny, int nx, int n_members);
+typedef struct lc_distance_args {
+    size_t struct_size; /* sizeof(lc_distance_args): checked before any other field */
+    const void *mask;
+    int dtype, ny, nx, n_members;
+    int cyclic_x;
+    double sampling_y, sampling_x; /* > 0 and finite */
+    double max_distance;           /* <= 0: unbounded */
+    void *dist_out;                /* float64 [n_members][ny*nx] */
+    void *nearest_out;             /* int32, or NULL */
+    void *work_dev;
+} lc_distance_args;
+int lc_distance_transform(lc_ctx *ctx, const lc_distance_args *args);
+
 /* ---- multi-GPU: halo exchange on RCCL ----------------------------------------
  * New (the reference is single-process).  One process per GPU,
  * seed rows block-partitioned, wind replicated; lc_advect needs no communication

@@ -149,6 +149,22 @@ PROTOTYPES["lc_label_components"] = (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp,
 PROTOTYPES["lc_component_sums"] = (_i, [_vp, C.POINTER(ComponentSumsArgs)])
 PROTOTYPES["lc_component_apply"] = (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _d, _vp])
 
+
+
+class DistanceArgs(C.Structure):
+    """``lc_distance_args`` of include/lcs_hip.h, field for field."""
+    _fields_ = [("struct_size", _sz),
+                ("mask", _vp),
+                ("dtype", _i), ("ny", _i), ("nx", _i), ("n_members", _i),
+                ("cyclic_x", _i),
+                ("sampling_y", _d), ("sampling_x", _d),
+                ("max_distance", _d),
+                ("dist_out", _vp), ("nearest_out", _vp), ("work_dev", _vp)]
+
+
+PROTOTYPES["lc_distance_work_elems"] = (_sz, [_i, _i, _i])
+PROTOTYPES["lc_distance_transform"] = (_i, [_vp, C.POINTER(DistanceArgs)])
+
 _lib = None
 
 

@@ -1041,6 +1041,43 @@ class Engine:
                                                 ny, nx, n, self._ptr(keep), int(keep.shape[1]), float(fill), self._ptr(out)), self.lib)
         return out if len(mask.shape) == 3 else out[0]
 
+    # ------------------------------------------------------------------ distance to the nearest pixel of a mask
+    def distance_transform(self, mask, cyclic=False, sampling=None, max_distance=None, return_nearest=False):
+        """Exact Euclidean distance from every pixel to the nearest foreground pixel of ``mask`` (``lc_distance_transform``):
+        ``scipy.ndimage.distance_transform_edt(~foreground, sampling=sampling)`` bit for bit, as a float64 device tensor shaped
+        like ``mask`` -- ``(ny, nx)``, or ``(n_members, ny, nx)``, every plane on its own in the same launches.
+
+        A pixel is foreground when it is ``!= 0`` and not NaN (float32 / float64 kept, any other dtype converted to float64).
+        ``sampling``: the pixel spacing, a scalar or ``(sy, sx)``, default 1.  ``cyclic``: the column offset is taken the
+        shorter way round a global longitude axis.  ``max_distance`` (> 0): pixels further away than that are ``+inf`` and
+        nobody searches beyond it; None: unbounded.  A plane without foreground is ``+inf`` everywhere.
+        ``return_nearest``: also the int32 linear index, into its plane, of the nearest foreground pixel (the smallest index
+        among equally near ones; -1 where the distance is ``+inf``)."""
+        if sampling is None:
+            sampling = 1.0
+        sy, sx = (float(s) for s in (np.broadcast_to(np.asarray(sampling, dtype=np.float64), (2,))))
+        if max_distance is not None and not float(max_distance) > 0:
+            raise ValueError(f"max_distance {max_distance!r}: a positive number, or None for no bound")
+        m = self._planes(mask)
+        n, ny, nx = (int(s) for s in m.shape)
+        torch = self.torch
+        dist = self._empty((n, ny, nx), np.float64)
+        nearest = torch.empty((n, ny, nx), dtype=torch.int32, device=self.device) if return_nearest else None
+        elems = int(self.lib.lc_distance_work_elems(ny, nx, n))
+        # the call's own checks refuse what cannot be sized (a plane too large or too wide) before they touch the buffer
+        work = torch.empty((max(1, elems if nx <= 16384 and ny * nx < 2 ** 31 else 1),), dtype=torch.int32, device=self.device)
+        a = _capi.DistanceArgs(struct_size=C.sizeof(_capi.DistanceArgs))
+        a.mask, a.dtype = m.data_ptr(), _NP2LC[np.dtype(str(m.dtype).replace("torch.", ""))]
+        a.ny, a.nx, a.n_members, a.cyclic_x = ny, nx, n, int(bool(cyclic))
+        a.sampling_y, a.sampling_x = sy, sx
+        a.max_distance = 0.0 if max_distance is None else float(max_distance)
+        a.dist_out, a.nearest_out, a.work_dev = dist.data_ptr(), nearest.data_ptr() if return_nearest else None, work.data_ptr()
+        self._use_current_stream()
+        _capi.check(self.lib.lc_distance_transform(self.ctx, C.byref(a)), self.lib)
+        if len(mask.shape) != 3:
+            dist, nearest = dist[0], nearest[0] if return_nearest else None
+        return (dist, nearest) if return_nearest else dist
+
     # ------------------------------------------------------------------ multi-GPU (RCCL through the C ABI)
     COMM_ID_BYTES = 128
 

@@ -7,6 +7,8 @@
 * ``find_ridges_spherical_hessian`` LCS/tools.py:52-155 (the consumer of the FTLE field)
 * ``filter_ridges``                 the filter LCS/area_of_influence.py:210-242 passes every raw mask through (imported there
                                     from a package outside the reference: defined here, see its docstring)
+* ``distance_to_ridges``            LCS/area_of_influence.py:230-244: ``distance_transform_edt(~ridges_bool)``, of which the
+                                    driver keeps ``dist < 12`` as the swath a ridge influences
 
 The remaining functions of that module (IDW regridding, harvesine, latlonsel) have no caller on the
 path.
@@ -19,7 +21,7 @@ from .dropin import _coord, _make, _to_np, get_engine
 from .engine import common_dtype
 
 __all__ = ["xr_map_coordinates", "fourth_order_derivative", "derivative_spherical_coords",
-           "find_ridges_spherical_hessian", "filter_ridges"]
+           "find_ridges_spherical_hessian", "filter_ridges", "distance_to_ridges"]
 
 
 def xr_map_coordinates(da, new_x, new_y, isglobal=True, order=1):
@@ -164,3 +166,50 @@ def filter_ridges(ridges, ftle, criteria, thresholds, verbose=True, connectivity
     if lead:
         coords[lead[0]] = _coord(ridges, lead[0])
     return _make(ridges, _to_np(out), order, coords, getattr(ridges, "name", None)).transpose(*dims)
+
+
+def distance_to_ridges(ridges, cyclic=False, sampling=None, max_distance=None, return_labels=False, connectivity=2):
+    """Distance from every grid point to the nearest ridge pixel: ``scipy.ndimage.distance_transform_edt(~ridges_bool)`` of
+    LCS/area_of_influence.py:231, bit for bit, on the device (``Engine.distance_transform``).
+
+    ``ridges`` is a labelled array over ``latitude`` and ``longitude`` (sorted ascending here, as ``filter_ridges`` sorts),
+    2-D, or 3-D with one more dimension (time, member): every plane is then transformed on its own, all of them in the same
+    kernel launches.  A pixel is part of a ridge when it is ``!= 0`` and not NaN.  Distances are in INDEX units times
+    ``sampling`` (a scalar or ``(latitude step, longitude step)``, default 1), as the driver's are; a latitude-dependent
+    metric (great-circle distance) is out of scope.  ``cyclic``: longitude offsets are taken the shorter way round a global
+    axis.  ``max_distance``: points further away are ``+inf`` and cost no search -- ``max_distance=12`` is the driver's
+    ``dist.where(dist < 12)`` up to the points at exactly 12, which it drops and this keeps.  A plane without a ridge is
+    ``+inf`` everywhere.
+
+    ``return_labels=True`` also returns, per point, the label of the ridge its nearest pixel belongs to (0 where the distance
+    is ``+inf``): ``Engine.label_components(ridges, connectivity, cyclic)`` gathered through the nearest-pixel index, on the
+    device.  Among equally near pixels the one of smallest (latitude, longitude) index decides.  That is the partition of the
+    plane into every ridge's own area of influence, which the driver approximates by dilation and a second filter.
+
+    Returns float64 distances (and int32 labels) in the caller's class and dimension order."""
+    dims = tuple(ridges.dims)
+    lead = [d for d in dims if d not in ("latitude", "longitude")]
+    if len(lead) > 1 or len(dims) - len(lead) != 2:
+        raise ValueError("ridges: dims (latitude, longitude) and at most one more")
+    order = (*lead, "latitude", "longitude")
+    lat, lon = _coord(ridges, "latitude"), _coord(ridges, "longitude")
+    ilat, ilon = np.argsort(lat, kind="stable"), np.argsort(lon, kind="stable")
+    v = np.asarray(ridges.transpose(*order).values)
+    v = v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)
+    v = np.ascontiguousarray(v[..., ilat, :][..., ilon])
+    eng = get_engine()
+    mask = eng.to_device(v, v.dtype)
+    coords = {"latitude": lat[ilat], "longitude": lon[ilon]}
+    if lead:
+        coords[lead[0]] = _coord(ridges, lead[0])
+
+    def out(t):
+        return _make(ridges, _to_np(t), order, coords, getattr(ridges, "name", None)).transpose(*dims)
+    if not return_labels:
+        return out(eng.distance_transform(mask, cyclic, sampling, max_distance))
+    dist, nearest = eng.distance_transform(mask, cyclic, sampling, max_distance, return_nearest=True)
+    labels, _ = eng.label_components(mask, connectivity, cyclic)
+    planes = labels.reshape(-1, labels.shape[-2] * labels.shape[-1])
+    index = nearest.reshape(planes.shape).to(eng.torch.int64)
+    owner = eng.torch.where(index >= 0, planes.gather(1, index.clamp(min=0)), eng.torch.zeros_like(planes))
+    return out(dist), out(owner.reshape(labels.shape))
