@@ -148,6 +148,20 @@ int lc_ctx_set_level_chunk(lc_ctx *ctx, int levels);
 /* The value in force (what lc_ctx_set_level_chunk was last given, or what LCS_LEVEL_CHUNK set at creation): a caller
  * that changes it for one call restores THIS, not a guess. */
 int lc_ctx_get_level_chunk(const lc_ctx *ctx, int *levels_out);
+/* Graded level counts (additive: LC_VERSION stays 104).  With the by-size level chunk (lc_ctx_set_level_chunk(-1), the
+ * default) the float32 order-1 two-seed kernel -- one member, no trajectories, cyclic or per-point boundaries -- may give
+ * the workgroups at the END of a launch's dispatch order fewer levels than `chunk`, so that a launch ends at once instead
+ * of draining through one workgroup lifetime; they make the levels up in the next launch, which starts them early.
+ *   chunk  levels per launch where the grading applies (0 = the by-size chunk; > 0 also on grids the by-size rule runs in
+ *          one launch: tests);
+ *   zone   workgroups at a launch's end that are cut short (-1 = the default for the device; rounded down to a multiple
+ *          of 8 and to what the launch count allows);
+ *   depth  levels the last workgroup loses, linearly less before it (-1 = the default; 0 = off: uniform chunks).
+ * Results are bit-identical whatever the values: positions at a level's end are the kernel's whole state.  Every other
+ * kernel, and any explicit lc_ctx_set_level_chunk(n >= 0), runs uniform chunks.  lc_ctx_last_advect_launches counts the
+ * launches as before.  No environment variable; no reference counterpart (LCS/trajectory.py:80-126 is one loop). */
+int lc_ctx_set_level_grading(lc_ctx *ctx, int chunk, int zone, int depth);
+int lc_ctx_get_level_grading(const lc_ctx *ctx, int *chunk_out, int *zone_out, int *depth_out);
 /* float64 on the ONE-CALL host routes (lc_lcs_host, lc_lcs_global_host -- what a reference-side binding calls, where a
  * user expects the reference's numbers): which form of the SETTLS iteration they take.
  *   LC_F64_EXACT_ORDER  numpy / scipy's operation order (two samples per iteration, true divisions, scipy's tap sums;

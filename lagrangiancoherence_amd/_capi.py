@@ -36,6 +36,8 @@ PROTOTYPES = {
     "lc_ctx_set_sigma_march": (_i, [_vp, _i]),
     "lc_ctx_set_level_chunk": (_i, [_vp, _i]),
     "lc_ctx_get_level_chunk": (_i, [_vp, C.POINTER(_i)]),
+    "lc_ctx_set_level_grading": (_i, [_vp, _i, _i, _i]),
+    "lc_ctx_get_level_grading": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "lc_ctx_set_f64_fidelity": (_i, [_vp, _i]),
     "lc_ctx_get_f64_fidelity": (_i, [_vp, C.POINTER(_i)]),
     "lc_ctx_set_host_pipeline": (_i, [_vp, _i]),

@@ -92,6 +92,16 @@ struct AdvectArgs {
     unsigned *verify;      // NULL, or the context's 16 wave-state counters (lc_ctx_set_verify: the one-seed order-1 LDS kernel's VERIFY instances)
     int member_dirs;       // lc_advect_series_dirs, sub-step kernels of the outer clamp: 1 = member 2w + d is window w (level
                            // t0 + w * member_t0_stride), d = 1 with -timestep (member_direction)
+    // Graded level counts (lcplan::Grading; advect_impl decides): a workgroup of the two-seed order-1 kernel takes its levels
+    // from lcplan::graded_range of its dispatch position instead of t0 / nsteps (which stay the uniform chunk's: the pole
+    // workgroups go by them).  grade.n = 0: uniform chunks.
+    lcplan::Grading grade;
+    int grade_launch, grade_t0;              // this launch's index, the call's first level
+    const T *grade_x_start, *grade_y_start;  // the call's start positions (NULL: the seed grid): where a range that begins at level 0 starts
+#ifdef LCS_TIMELINE  // diagnostic build only
+    unsigned long long *timeline;  // NULL, or [launch][block][4]: first stamp, last stamp, dispatch position, levels (lc_debug_read_timeline)
+    int timeline_launch;
+#endif
 };
 
 // Tile of a workgroup.  Hardware deals workgroups to the 8 XCDs round-robin (blockIdx % 8), each with its own L2.
@@ -1907,10 +1917,36 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
     // PATCH_LINES: two slabs (alternating by level) of the workgroup's 16 x 32 longitudes and latitudes
     __shared__ __attribute__((aligned(16))) float s_slab[2][2][LINES ? 16 * SLAB_PITCH : 4];
     if (GROUP ? pole_block_group(A) : pole_block<float, POLE_LIN>(A)) return;
-    const int tile_id = xcd_tile_id(A);
-    if (tile_id >= A.ntiles) return;  // whole block
+    // This workgroup's tile, levels [t0, t0 + nsteps) and start positions: the launch's -- or, with graded level counts (tall
+    // patches without trajectories; launch_plan.h), those of its dispatch position: fewer levels towards the end of the
+    // dispatch order, made up in the next launch, which continues from x_out / y_out unless the range begins at the call's
+    // first level.  An empty range stores nothing: its seeds' positions are where the previous launch (or the caller) left them.
+    int tile_id, t0 = A.t0, nsteps = A.nsteps;
+    const float *x_from = A.x_start, *y_from = A.y_start;
+    if (MODE == PATCH_TALL && A.grade.n > 0) {
+        const int d = (int)blockIdx.x - A.pole_blocks;
+        tile_id = lcplan::tile_of_block(lcplan::graded_slot(A.grade, A.grade_launch, d), A.ntiles, A.ntx, A.xcd_chunk, A.tile_order);
+        if (tile_id >= A.ntiles) return;
+        const lcplan::Range r = lcplan::graded_range(A.grade, A.grade_launch, d);
+        if (r.b <= r.a) return;
+        t0 = A.grade_t0 + r.a;
+        nsteps = r.b - r.a;
+        x_from = r.a == 0 ? A.grade_x_start : A.x_out;
+        y_from = r.a == 0 ? A.grade_y_start : A.y_out;
+    } else {
+        tile_id = xcd_tile_id(A);
+        if (tile_id >= A.ntiles) return;  // whole block
+    }
     const int tyi = tile_id / A.ntx, txi = tile_id - tyi * A.ntx;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#ifdef LCS_TIMELINE
+    unsigned long long *const tl_rec = A.timeline ? A.timeline + ((size_t)A.timeline_launch * gridDim.x + blockIdx.x) * 4 : nullptr;
+    if (tl_rec && threadIdx.x == 0) {
+        tl_rec[0] = wall_clock64();
+        tl_rec[2] = blockIdx.x;
+        tl_rec[3] = (unsigned long long)nsteps;
+    }
+#endif
     // workgroup origin and the lane's first seed (see enum Patch)
     const int ix0 = WIDE ? txi * (TILE_W * SPL) + SPL * (lane % TILE_W)
                   : LINES ? txi * (TILE_W * 4) + wave * TILE_W + (lane % TILE_W) : txi * TILE_W + (lane % TILE_W);
@@ -1944,8 +1980,8 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
         // lanes without a seed shadow a neighbouring one so that they follow the same path; only their stores are masked
         const int sx_i = min(ix, A.nx - 1), sy_i = min(iy, A.ny - 1);
         const size_t moff = (GROUP && q < cnt) ? (size_t)q * A.pair_plane : 0;  // member q's planes
-        p[q] = (f2){A.x_start ? A.x_start[moff + (size_t)sy_i * A.nx + sx_i] : A.seed_lon[sx_i],
-                    A.y_start ? A.y_start[moff + (size_t)sy_i * A.nx + sx_i] : A.seed_lat[sy_i]};
+        p[q] = (f2){x_from ? x_from[moff + (size_t)sy_i * A.nx + sx_i] : A.seed_lon[sx_i],
+                    y_from ? y_from[moff + (size_t)sy_i * A.nx + sx_i] : A.seed_lat[sy_i]};
         const float ys = A.seed_lat[sy_i];  // conversion_x is a function of the SEED latitude (Q5), wherever the parcel is now
         const float cx_conv =
             180.0f / ((float)(3.141592653589793 * 6371000.0) * fabsf(cosf((ys * (float)3.141592653589793) / 180.0f)));
@@ -1994,8 +2030,8 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
     auto to_index = [&](f2 v) { return (v - pmin) * sc; };  // subtract first: exact 0 at the grid origin
     const float xlo = A.x_min, xhi = A.x_max;
     auto x_needs_care = [&](float x) { return CYCLIC ? !(fabsf(x) < 180.0f) : !((x > xlo) & (x < xhi)); };
-    const float *lvl = A.img + (size_t)A.t0 * A.level_elems;
-    const float *elv = A.ext + (size_t)A.t0 * A.level_elems;
+    const float *lvl = A.img + (size_t)t0 * A.level_elems;
+    const float *elv = A.ext + (size_t)t0 * A.level_elems;
     const int pad_cols = A.pitch, pad_rows = A.ny_f + LC_PAD;
     const float kpred = 0.5f * (float)(K > 0 ? K - 1 : 0);
     const int st_row = min(lane / G::LANES_PER_ROW, LT_ROWS - 1), st_col = (lane % G::LANES_PER_ROW) * 2;
@@ -2008,7 +2044,7 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
     constexpr int CENTRE = (WIDE || GROUP) ? TILE_W / 2 + TILE_W * 4 : TILE_W / 2 + TILE_W * 7;
     f2 dprev = {0.0f, 0.0f};
     // member groups: level iterations of this workgroup (a short last group stops with its last member's steps)
-    const int nlev = GROUP ? lcplan::group_levels(A.nsteps, A.pair_l0, A.pair_n, A.pair_d, cnt) : A.nsteps;
+    const int nlev = GROUP ? lcplan::group_levels(A.nsteps, A.pair_l0, A.pair_n, A.pair_d, cnt) : nsteps;
 #ifdef LCS_STAMPS
     long long acc_t[5] = {0, 0, 0, 0, 0}, last_t = __builtin_amdgcn_s_memtime();
     unsigned long long acc_n[3] = {0, 0, 0};
@@ -2295,6 +2331,9 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
             }
         }
     }
+#ifdef LCS_TIMELINE
+    if (tl_rec && lane == 0) atomicMax(tl_rec + 1, (unsigned long long)wall_clock64());  // the workgroup's last wave to end
+#endif
 }
 
 // ======================================================================================
@@ -4484,13 +4523,64 @@ int advect_impl(lc_ctx *ctx, const lc_advect_args &a, const AdvectCall &call) {
         lc_set_error("lc_advect: the flag all-reduce of LC_X_CLAMP_REFERENCE_OUTER failed (lc_ctx_set_flag_allreduce callback returned non-zero)");
         return LC_ERCCL;
     };
-    const int chunk = lcplan::level_chunk(ctx->level_chunk, outer, (long long)ny * nx, n_launch, K, total, sizeof(T) == 8 && order == 1);
+    int chunk = lcplan::level_chunk(ctx->level_chunk, outer, (long long)ny * nx, n_launch, K, total, sizeof(T) == 8 && order == 1);
+    // Graded level counts (launch_plan.h; lc_ctx_set_level_grading): under the by-size chunk, the tall-patch two-seed order-1
+    // kernel of ONE member without trajectories takes each workgroup's levels from its dispatch position -- the launches stay
+    // n_chunks(total, chunk), their workgroups at the end of the dispatch order do fewer levels and make them up in the next
+    // launch.  Everything else -- an explicit level chunk, the outer clamp's fixed chunks and collectives, ensembles, member
+    // groups, trajectories, the other patch modes, pole rows inside the tiles (their seeds go by the launch's uniform range,
+    // so a workgroup may not leave early) -- keeps uniform chunks: GR.n = 0.
+    lcplan::Grading GR{};
+    if constexpr (sizeof(T) == 4) {
+        const bool tiles_have_poles = A.pole_blocks == 0 && (A.row0 < A.order || A.row0 + ny > A.ny_global - A.order);
+        if (order == 1 && use_lds && n_members == 1 && order1_two_seed_applies(A, ctx->lds_tiles)) {
+            AdvectArgs<float> P = A;
+            int g2 = 0;
+            const int mode = two_seed_patch_grid(P, P.patch_mode < PATCH_PAIR, g2);
+            if (ctx->level_chunk < 0 && !outer && !a.traj_x && !tiles_have_poles && mode == PATCH_TALL) {
+                const int gchunk = ctx->grade_chunk > 0 ? ctx->grade_chunk : chunk;
+                const int zone = ctx->grade_zone >= 0 ? ctx->grade_zone : lcplan::GRADE_ZONE_PER_CU * ctx->n_cus;
+                const int depth = ctx->grade_depth >= 0 ? ctx->grade_depth : lcplan::grade_depth_default(gchunk);
+                GR = lcplan::grading(total, gchunk, zone, depth, g2 - A.pole_blocks);
+                if (GR.zone > 0)
+                    chunk = gchunk;
+                else
+                    GR.n = 0;
+            }
+#ifdef LCS_TIMELINE
+            const size_t recs = (size_t)lcplan::n_chunks(total, chunk) * (size_t)g2;
+            if (recs > ctx->timeline_cap) {
+                if (ctx->timeline_dev) (void)hipFree(ctx->timeline_dev);
+                ctx->timeline_dev = nullptr;
+                ctx->timeline_cap = 0;
+                if (hipMalloc((void **)&ctx->timeline_dev, recs * 4 * sizeof(unsigned long long)) == hipSuccess) ctx->timeline_cap = recs;
+                else (void)hipGetLastError();
+            }
+            if (ctx->timeline_dev) {
+                (void)hipMemsetAsync(ctx->timeline_dev, 0, recs * 4 * sizeof(unsigned long long), ctx->stream);
+                A.timeline = ctx->timeline_dev;
+                ctx->timeline_launches = lcplan::n_chunks(total, chunk);
+                ctx->timeline_grid = g2;
+            }
+#endif
+        }
+    }
     for (int ci = 0, nci = lcplan::n_chunks(total, chunk); ci < nci; ++ci) {
         const int s0 = lcplan::chunk_first(ci, chunk);
         AdvectArgs<T> C = A;
         C.t0 = a.t0 + s0;
         C.nsteps = lcplan::chunk_levels(ci, total, chunk);
         C.pair_l0 = s0;
+        if (GR.n > 0) {
+            C.grade = GR;
+            C.grade_launch = ci;
+            C.grade_t0 = a.t0;
+            C.grade_x_start = A.x_start;
+            C.grade_y_start = A.y_start;
+        }
+#ifdef LCS_TIMELINE
+        C.timeline_launch = ci;
+#endif
         if (s0 > 0) {
             C.x_start = A.x_out;
             C.y_start = A.y_out;
@@ -4784,6 +4874,22 @@ extern "C" int lc_debug_read_stamps(unsigned long long *out8, int reset) {
         if (hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z, sizeof(z)) != hipSuccess) return -1;
     }
     return 0;
+}
+#endif
+
+#ifdef LCS_TIMELINE
+// Diagnostic build only: the workgroup records of the context's last two-seed order-1 advect call, [launch][block][4] =
+// first stamp, last stamp (100 MHz wall clock, one counter for all XCDs), block index, levels done (all 0: a pole workgroup, a
+// block without a tile, an empty range).  out = NULL: the sizes only.
+extern "C" int lc_debug_read_timeline(lc_ctx *ctx, unsigned long long *out, size_t cap_records, int *launches_out, int *grid_out) {
+    if (!ctx || !launches_out || !grid_out) return -1;
+    *launches_out = ctx->timeline_launches;
+    *grid_out = ctx->timeline_grid;
+    const size_t recs = (size_t)ctx->timeline_launches * (size_t)ctx->timeline_grid;
+    if (!out) return 0;
+    if (!ctx->timeline_dev || cap_records < recs) return -1;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return -1;
+    return hipMemcpy(out, ctx->timeline_dev, recs * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
 }
 #endif
 

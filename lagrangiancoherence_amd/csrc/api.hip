@@ -70,6 +70,14 @@ extern "C" int lc_ctx_create(int device, lc_ctx **out) {
     if (const char *ev = getenv("LCS_SIGMA_MARCH")) c->sigma_march = ev[0] == '0' ? 0 : (ev[0] == '1' ? 1 : 2);  // read once, here
     c->level_chunk = -1;  // by size (advect.hip: 32 levels per launch from 2^22 seeds per call)
     if (const char *ev = getenv("LCS_LEVEL_CHUNK")) c->level_chunk = atoi(ev) >= 0 ? atoi(ev) : -1;  // read once, here
+    c->grade_chunk = 0;   // graded level counts: the by-size chunk, the built-in zone and depth (advect.hip; no environment variable)
+    c->grade_zone = -1;
+    c->grade_depth = -1;
+#ifdef LCS_TIMELINE
+    c->timeline_dev = nullptr;
+    c->timeline_cap = 0;
+    c->timeline_launches = c->timeline_grid = 0;
+#endif
     c->f64_fidelity = LC_F64_AUTO;
     if (const char *ev = getenv("LCS_F64_FIDELITY")) c->f64_fidelity = ev[0] == 'e' ? LC_F64_EXACT_ORDER : (ev[0] == 'f' ? LC_F64_FAST : LC_F64_AUTO);  // read once, here
     c->patch_mode = -1;
@@ -171,6 +179,24 @@ extern "C" int lc_ctx_set_level_chunk(lc_ctx *ctx, int levels) {
     return LC_OK;
 }
 
+extern "C" int lc_ctx_set_level_grading(lc_ctx *ctx, int chunk, int zone, int depth) {
+    LC_REQUIRE(ctx, "lc_ctx_set_level_grading: null context");
+    LC_REQUIRE(chunk >= 0 && zone >= -1 && depth >= -1,
+               "lc_ctx_set_level_grading: chunk must be >= 0 (0 = by size), zone and depth >= -1 (-1 = the default; depth 0 = off)");
+    ctx->grade_chunk = chunk;
+    ctx->grade_zone = zone;
+    ctx->grade_depth = depth;
+    return LC_OK;
+}
+
+extern "C" int lc_ctx_get_level_grading(const lc_ctx *ctx, int *chunk_out, int *zone_out, int *depth_out) {
+    LC_REQUIRE(ctx && chunk_out && zone_out && depth_out, "lc_ctx_get_level_grading: null pointer");
+    *chunk_out = ctx->grade_chunk;
+    *zone_out = ctx->grade_zone;
+    *depth_out = ctx->grade_depth;
+    return LC_OK;
+}
+
 // Wave-state audit of the one-seed order-1 LDS kernel (advect.hip, VERIFY instances): 16 counters in device memory.
 extern "C" int lc_ctx_set_verify(lc_ctx *ctx, int mode) {
     LC_REQUIRE(ctx, "lc_ctx_set_verify: null context");
@@ -227,6 +253,9 @@ extern "C" int lc_ctx_destroy(lc_ctx *ctx) {
     lc_host_xfer::release(ctx->xfer);
     host_ws_destroy(ctx);
     if (ctx->verify_dev) (void)hipFree(ctx->verify_dev);
+#ifdef LCS_TIMELINE
+    if (ctx->timeline_dev) (void)hipFree(ctx->timeline_dev);
+#endif
     (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return LC_OK;

@@ -155,6 +155,95 @@ LCP_HD int chunk_levels(int i, int total, int chunk) {
     return left < chunk ? imax(left, 0) : chunk;
 }
 
+// ---- graded level counts ----------------------------------------------------------------------------------------------------
+// With uniform chunks every workgroup of a launch does the same number of levels: the ones dispatched last finish a whole
+// workgroup lifetime after the queue has run dry, and the chip drains through that time before the next launch may start.
+// Graded: the workgroups at the END of a launch's dispatch order get fewer levels (the last `zone` positions lose 1 ...
+// `depth` levels, linearly), so that they finish with the ones before them; a tile that was cut short makes the levels up in
+// the next launch, whose dispatch order is ROTATED so that it is not among the last again; the tiles that end the LAST launch
+// have done their extra levels in the launch before it, where they sat well before the end.
+//   dispatch position d   blockIdx.x minus the pole blocks: the order in which the hardware starts the workgroups of a launch
+//                         (tile_of_block's own `d` orders the tiles of ONE XCD; the eight XCDs take their blocks side by side).
+//   slot                  what tile_of_block is given in place of the block: slot = d in launch 0; launch i runs slot
+//                         (d - rot_i) mod blocks at position d.  rot_i is a multiple of 8: a slot, and so a tile, stays on
+//                         its XCD in every launch, and neighbouring tiles stay neighbours.
+//   rot_i                 i * zone for every launch but the last, (n + 1) * zone for the last one: the `zone` tiles a launch
+//                         cut short start the next one (the last launch: they follow two zones in), and the tiles that end the
+//                         last launch sat three to four zones before the end of the one before it.
+//   boundaries            launch i runs a slot's levels [B_i, B_i+1):  B_0 = 0, B_n = total,
+//                         B_i = i * chunk - cut(position in launch i - 1) [+ cut(position in launch n - 1) for i = n - 1],
+//                         cut(p) = depth * (p - (blocks - zone) + 1) / zone for the last `zone` positions, 0 before them.
+// grading() normalises a caller's wish: zone a multiple of 8 with (n + 2) * zone <= blocks (no rotation wraps; a slot is in
+// at most ONE of the zones that enter a boundary, and at most one of its two boundaries in a launch is moved outwards), depth
+// <= chunk, both 0 when either is or when the call is one launch.  Then for every slot the ranges are consecutive, in order,
+// from 0 to total (tests/c/level_grading_test.cpp, exhaustively over small cases), and
+//   the LONGEST range is chunk + depth <= 2 * chunk levels (graded_longest): a tile that makes up `depth` levels, or one that
+//   works `depth` levels ahead -- never both.  Resident workgroups of a launch are therefore within 2 * chunk levels of each
+//   other instead of chunk (what level chunks exist to limit), and only the 2 * zone tiles at the two ends are.
+// zone = 0 (or depth = 0) is chunk_first / chunk_levels exactly.
+// Defaults where the context sets none (lc_ctx_set_level_grading): the zone is GRADE_ZONE_PER_CU workgroups per compute
+// unit -- three rounds of the seven a compute unit holds --, the depth the whole chunk (the last workgroup of a launch has
+// nothing left to do in it).  Measured on C3 (advect call, ms; profiles/level_grading/level_grading_ab.txt): uniform chunks of 32
+// 5.88-5.91; zone 1024 / 1792 / 3584 / 5376 at depth 32: 5.75-5.76 / 5.70-5.74 / 5.74-5.76 / 5.69-5.72, at depth 8 5.77-5.88,
+// 16 5.71-5.81, 24 5.68-5.76; chunks of 16 / 24 / 48 graded 5.90-5.97 / 5.77-5.81 / 5.74-5.81 (uniform 6.08-6.10 / 5.94-5.99 /
+// 5.90-5.94): 32 stays.  200 steps and C4 (7 and 12 launches; the zone is capped at blocks / (launches + 2)): within the
+// run-to-run spread of uniform chunks, 13.3-13.5 and 91.7-92.7 ms.
+constexpr int GRADE_ZONE_PER_CU = 21;
+LCP_HD int grade_depth_default(int chunk) { return chunk; }
+struct Grading {
+    int n;       // launches of the call
+    int total;   // levels of the call
+    int chunk;   // levels per launch of the uniform plan
+    int zone;    // dispatch positions at the end of a launch that are cut short (a multiple of 8; 0: uniform chunks)
+    int depth;   // levels the last position loses (1 .. chunk; 0: uniform chunks)
+    int blocks;  // dispatch positions of a launch (the grid without the pole blocks)
+};
+struct Range { int a, b; };  // levels [a, b)
+LCP_HD Grading grading(int total, int chunk, int zone, int depth, int n_blocks) {
+    Grading g;
+    g.n = n_chunks(total, chunk);
+    g.total = total;
+    g.chunk = chunk;
+    g.blocks = n_blocks;
+    g.zone = g.n > 1 && depth > 0 ? imin(imax(zone, 0), n_blocks / (g.n + 2)) / XCDS * XCDS : 0;
+    g.depth = g.zone > 0 ? imin(depth, chunk) : 0;
+    return g;
+}
+LCP_HD int graded_longest(const Grading &g) { return g.chunk + g.depth; }
+LCP_HD int graded_rotation(const Grading &g, int launch) { return (launch < g.n - 1 ? launch : g.n + 1) * g.zone; }  // < blocks
+// The per-launch permutation: the slot that dispatch position d runs in `launch`, and its inverse.
+LCP_HD int graded_slot(const Grading &g, int launch, int d) {
+    const int s = d - graded_rotation(g, launch);
+    return s < 0 ? s + g.blocks : s;
+}
+LCP_HD int graded_position(const Grading &g, int launch, int slot) {
+    const int p = slot + graded_rotation(g, launch);
+    return p >= g.blocks ? p - g.blocks : p;
+}
+LCP_HD int graded_cut(const Grading &g, int p) {
+    const int k = p - (g.blocks - g.zone);
+    return k < 0 ? 0 : g.depth * (k + 1) / g.zone;
+}
+// First level of `slot` in launch i (i = n: the end of the call).
+LCP_HD int graded_bound(const Grading &g, int i, int slot) {
+    if (i <= 0) return 0;
+    if (i >= g.n) return g.total;
+    int b = i * g.chunk;
+    if (g.zone > 0) {
+        b -= graded_cut(g, graded_position(g, i - 1, slot));
+        if (i == g.n - 1) b += graded_cut(g, graded_position(g, i, slot));
+    }
+    return imin(b, g.total);
+}
+// Levels [a, b) of the workgroup at dispatch position d of `launch` (it runs graded_slot(g, launch, d)); may be empty.
+LCP_HD Range graded_range(const Grading &g, int launch, int d) {
+    const int slot = graded_slot(g, launch, d);
+    Range r;
+    r.a = graded_bound(g, launch, slot);
+    r.b = graded_bound(g, launch + 1, slot);
+    return r;
+}
+
 // ---- member groups (lc_advect_batch, two members per lane) ---------------------------------------------------------------
 // Members 2p and 2p+1 share a lane.  A group's LEVEL window is [0, nsteps + (g - 1) d): member q of the group steps at the
 // window levels [q d, q d + nsteps) (d = t0_stride).  Grouping only pays (and is only correct as implemented) when the

@@ -46,6 +46,15 @@ struct lc_ctx {
     int host_piece_mb;          // staging ring: piece size in MB (0: 32; LCS_HOST_PIECE_MB at creation)
     int host_pipeline;          // lc_lcs_host: 1 (default) staged transfers, upload cut into level chunks and overlapped with pack + advect; 0 the serial round-5 form (LCS_HOST_PIPELINE at creation)
     const char *last_strain_kernel;  // what the last lc_strain launched (lc_ctx_last_strain_kernel)
+    // lc_advect, graded level counts (launch_plan.h; lc_ctx_set_level_grading): levels per launch where the grading applies
+    // (0: the by-size chunk), dispatch positions at a launch's end that are cut short, levels the last one loses (-1: the
+    // built-in defaults; depth 0: off).  Only with level_chunk = -1: an explicit level chunk is uniform chunks.
+    int grade_chunk, grade_zone, grade_depth;
+#ifdef LCS_TIMELINE  // diagnostic build only: start / end stamps of the two-seed order-1 kernel's workgroups (lc_debug_read_timeline)
+    unsigned long long *timeline_dev;
+    size_t timeline_cap;  // records allocated
+    int timeline_launches, timeline_grid;  // of the last call that wrote it
+#endif
 };
 
 void lc_set_error(const char *fmt, ...);

@@ -254,6 +254,20 @@ class Engine:
         _capi.check(self.lib.lc_ctx_get_level_chunk(self.ctx, C.byref(v)), self.lib)
         return v.value
 
+    def set_level_grading(self, chunk: int = 0, zone: int = -1, depth: int = -1):
+        """Graded level counts of the float32 order-1 two-seed kernel under the by-size level chunk: ``chunk`` levels per
+        launch (0: the by-size chunk), the last ``zone`` workgroups of a launch cut short by up to ``depth`` levels, made up
+        in the next launch (-1: the defaults; ``depth=0``: uniform chunks).  Results are bit-identical; it shapes the
+        launches only (``lc_ctx_set_level_grading``)."""
+        _capi.check(self.lib.lc_ctx_set_level_grading(self.ctx, int(chunk), int(zone), int(depth)), self.lib)
+
+    @property
+    def level_grading(self):
+        """``(chunk, zone, depth)`` as :meth:`set_level_grading` last set them (``lc_ctx_get_level_grading``)."""
+        c, z, d = C.c_int(), C.c_int(), C.c_int()
+        _capi.check(self.lib.lc_ctx_get_level_grading(self.ctx, C.byref(c), C.byref(z), C.byref(d)), self.lib)
+        return c.value, z.value, d.value
+
     _FIDELITY = {"auto": _capi.LC_F64_AUTO, "exact": _capi.LC_F64_EXACT_ORDER, "fast": _capi.LC_F64_FAST}
 
     def set_f64_fidelity(self, mode: str):
