@@ -20,6 +20,7 @@
 // the 2x2 (order 1) or 4x4 (order 3) tap window of a wrapped coordinate is
 // always in range and its (u,v) pairs are contiguous along x, so one sample
 // position costs 2 (order 1, float) wide loads per level instead of 8 scalars.
+#include <initializer_list>
 #include <type_traits>
 #include <vector>
 
@@ -125,13 +126,59 @@ template <typename T>
 static inline unsigned nmem(const AdvectArgs<T> &A) { return A.n_members > 1 ? (unsigned)A.n_members : 1u; }  // grid.y of an advect launch
 
 // The one launch form of the advect kernel families: `kernel` on grid x members workgroups of BLOCK threads, with A and
-// whatever the kernel takes after it.  Returns `name`: the kernel as a profiler prints it -- at every call a quoted literal,
-// which tests/kernel_routes.py's table and bench.py's profile matching read from this file.
+// whatever the kernel takes after it.  Returns `name`: the kernel as a profiler prints it, which tests/kernel_routes.py's
+// table and bench.py's profile matching go by.  A name is a string literal once the preprocessor has run (pieces joined by
+// literal concatenation: tests/test_kernel_routes.py reads them there), made by the macros below from the very tokens that
+// instantiate the kernel; only a site that launches one fixed instance spells its name out.
 template <typename K, typename T, typename... Extra>
 static inline const char *launch_kernel(K kernel, int grid, hipStream_t st, const AdvectArgs<T> &A, const char *name, const Extra &...extra) {
     hipLaunchKernelGGL(kernel, dim3(grid, nmem(A)), dim3(BLOCK), 0, st, A, extra...);
     return name;
 }
+
+// One instance of a kernel family that is compiled per SETTLS_order and x boundary: FAMILY<KF, CYC, tail...>, for the calls
+// with K == KF (KF = -1: whatever K, read at run time) and that boundary.
+template <typename T>
+struct Instance {
+    int K;
+    bool cyclic;
+    void (*kernel)(AdvectArgs<T>);
+    const char *name;
+};
+#define LC_STR(...) #__VA_ARGS__
+// ... named by its template arguments as typed (a patch mode or a source goes in as its number) ...
+#define LC_INSTANCE(KF, CYC, FAMILY, ...) {KF, CYC, FAMILY<KF, CYC, ##__VA_ARGS__>, #FAMILY "<" LC_STR(KF, CYC, ##__VA_ARGS__) ">"}
+// ... or with WORD in the name where the trailing arguments stand
+#define LC_INSTANCE_AS(KF, CYC, FAMILY, WORD, ...) {KF, CYC, FAMILY<KF, CYC, __VA_ARGS__>, #FAMILY "<" #KF ", " #CYC ", " #WORD ">"}
+// The usual four: SETTLS_order 4 (the setting the reference's example and drivers use) and the run-time K, per boundary
+#define LC_K4(INSTANCE, ...) INSTANCE(4, true, __VA_ARGS__), INSTANCE(4, false, __VA_ARGS__), INSTANCE(-1, true, __VA_ARGS__), INSTANCE(-1, false, __VA_ARGS__)
+
+// Launches the instance compiled for the call's K and boundary, else the run-time-K instance of its boundary: a family's
+// list says which K have an instance of their own, per boundary, and the fall-back is stated here alone.
+template <typename T>
+static inline const char *launch_by_k(std::initializer_list<Instance<T>> family, int grid, hipStream_t st, const AdvectArgs<T> &A) {
+    const Instance<T> *pick = nullptr;
+    for (const Instance<T> &i : family)
+        if (i.cyclic == (A.cyclic != 0) && (i.K == A.K || (i.K == -1 && !pick))) pick = &i;
+    return launch_kernel(pick->kernel, grid, st, A, pick->name);
+}
+
+// The generic float64 kernel advect_kernel<double, ORD, FUSED, SRC> on `grid` workgroups of stream `st` (SRC: SRC_IMAGES = 0,
+// SRC_RAW_EULER = 1, SRC_RAW_ALL = 2), named with all four template arguments, as a profiler prints them
+#define LC_ADVECT_F64(ORD, FUSED, SRC) \
+    launch_kernel(advect_kernel<double, ORD, FUSED, SRC>, grid, st, A, "advect_kernel<double, " #ORD ", " #FUSED ", " #SRC ">")
+
+// One statement per interpolation order (scipy's 1 .. 5, checked at the intake): M(ORD) with ORD the order as a token
+#define LC_ORDERS_2_TO_5(M) \
+    case 2: M(2); break;    \
+    case 3: M(3); break;    \
+    case 4: M(4); break;    \
+    case 5: M(5); break;
+#define LC_BY_ORDER(ORDER_VALUE, M) \
+    switch (ORDER_VALUE) {          \
+        LC_ORDERS_2_TO_5(M)         \
+        default: M(1); break;       \
+    }
 
 template <typename T>
 struct Pair {
@@ -597,6 +644,7 @@ constexpr int POLE_LIN = 0, POLE_EITHER = 1, POLE_RAW = 2;
 // float64 at order 1, where the samples come from: packed images (lin + ext) / raw planes for the Euler sample + ext image /
 // raw planes for both (the fused-level value formed node by node)
 constexpr int SRC_IMAGES = 0, SRC_RAW_EULER = 1, SRC_RAW_ALL = 2;
+static_assert(SRC_IMAGES == 0 && SRC_RAW_EULER == 1 && SRC_RAW_ALL == 2, "the launch sites write a source as its number (LC_ADVECT_F64, LC_INSTANCE)");
 template <bool WRAP>
 __device__ void advect_seed_w32(const AdvectArgs<double> &A, int iy, int ix);  // (below: the float32 wind's own order-1 path)
 template <typename T, int SRC>
@@ -2674,67 +2722,40 @@ struct LdsLaunch<float, ORDER> {
         if (ORDER == 1 && A.pair_d >= 0) {
             // an ensemble, two MEMBERS per lane (advect_impl checked order1_two_seed_applies): the one-seed kernel's 8 x 32-seed workgroups
             A.tile_order = A.tile_order_two_seed;
-            if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds2_kernel<4, true, PATCH_PAIR>, grid, st, A, "advect_lds2_kernel<4, true, 3>");
-            if (A.K == 4) return launch_kernel(advect_lds2_kernel<4, false, PATCH_PAIR>, grid, st, A, "advect_lds2_kernel<4, false, 3>");
-            if (A.cyclic) return launch_kernel(advect_lds2_kernel<-1, true, PATCH_PAIR>, grid, st, A, "advect_lds2_kernel<-1, true, 3>");
-            return launch_kernel(advect_lds2_kernel<-1, false, PATCH_PAIR>, grid, st, A, "advect_lds2_kernel<-1, false, 3>");
+            return launch_by_k({LC_K4(LC_INSTANCE, advect_lds2_kernel, 3 /* PATCH_PAIR */)}, grid, st, A);
         }
         if (ORDER == 1 && order1_two_seed_applies(A, mode)) {
             // two seeds per lane; a workgroup covers 8 x 64 seeds (PATCH_TALL), 16 x 32 (PATCH_WIDE) or 32 x 16 (PATCH_LINES)
             int g2;
             const int mode = two_seed_patch_grid(A, A.patch_mode < PATCH_PAIR, g2);  // (PATCH_PAIR is the ensemble's, above)
             A.tile_order = A.tile_order_two_seed;
-            if (mode == PATCH_LINES) {
-                if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds2_kernel<4, true, PATCH_LINES>, g2, st, A, "advect_lds2_kernel<4, true, 2>");
-                if (A.K == 4) return launch_kernel(advect_lds2_kernel<4, false, PATCH_LINES>, g2, st, A, "advect_lds2_kernel<4, false, 2>");
-                if (A.cyclic) return launch_kernel(advect_lds2_kernel<-1, true, PATCH_LINES>, g2, st, A, "advect_lds2_kernel<-1, true, 2>");
-                return launch_kernel(advect_lds2_kernel<-1, false, PATCH_LINES>, g2, st, A, "advect_lds2_kernel<-1, false, 2>");
-            }
-            if (mode == PATCH_WIDE) {
-                if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds2_kernel<4, true, PATCH_WIDE>, g2, st, A, "advect_lds2_kernel<4, true, 1>");
-                if (A.K == 4) return launch_kernel(advect_lds2_kernel<4, false, PATCH_WIDE>, g2, st, A, "advect_lds2_kernel<4, false, 1>");
-                if (A.cyclic) return launch_kernel(advect_lds2_kernel<-1, true, PATCH_WIDE>, g2, st, A, "advect_lds2_kernel<-1, true, 1>");
-                return launch_kernel(advect_lds2_kernel<-1, false, PATCH_WIDE>, g2, st, A, "advect_lds2_kernel<-1, false, 1>");
-            }
-            // (SETTLS_order = 0, the library default, compiled as such: no tile, no iteration blocks -- C3 1.73 -> 1.69 ms against the run-time-K instance)
-            if (A.K == 0 && A.cyclic) return launch_kernel(advect_lds2_kernel<0, true, PATCH_TALL>, g2, st, A, "advect_lds2_kernel<0, true, 0>");
-            if (A.K == 0) return launch_kernel(advect_lds2_kernel<0, false, PATCH_TALL>, g2, st, A, "advect_lds2_kernel<0, false, 0>");   // (cyclic_xboundary=False is the reference's default too)
-            // (SETTLS_order 1, 2, 3 compiled as such too: the iteration loop unrolls and the kernel keeps the K = 4 instance's 59 registers
-            // instead of the run-time-K instance's 71 -- C3 at K = 1: 3.28 -> 2.91 ms, K = 2: 4.26 -> 3.93)
-            if (A.K == 1 && A.cyclic) return launch_kernel(advect_lds2_kernel<1, true, PATCH_TALL>, g2, st, A, "advect_lds2_kernel<1, true, 0>");
-            if (A.K == 2 && A.cyclic) return launch_kernel(advect_lds2_kernel<2, true, PATCH_TALL>, g2, st, A, "advect_lds2_kernel<2, true, 0>");
-            if (A.K == 3 && A.cyclic) return launch_kernel(advect_lds2_kernel<3, true, PATCH_TALL>, g2, st, A, "advect_lds2_kernel<3, true, 0>");
-            if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds2_kernel<4, true, PATCH_TALL>, g2, st, A, "advect_lds2_kernel<4, true, 0>");
-            if (A.K == 4) return launch_kernel(advect_lds2_kernel<4, false, PATCH_TALL>, g2, st, A, "advect_lds2_kernel<4, false, 0>");
-            if (A.cyclic) return launch_kernel(advect_lds2_kernel<-1, true, PATCH_TALL>, g2, st, A, "advect_lds2_kernel<-1, true, 0>");
-            return launch_kernel(advect_lds2_kernel<-1, false, PATCH_TALL>, g2, st, A, "advect_lds2_kernel<-1, false, 0>");
+            if (mode == PATCH_LINES) return launch_by_k({LC_K4(LC_INSTANCE, advect_lds2_kernel, 2 /* PATCH_LINES */)}, g2, st, A);
+            if (mode == PATCH_WIDE) return launch_by_k({LC_K4(LC_INSTANCE, advect_lds2_kernel, 1 /* PATCH_WIDE */)}, g2, st, A);
+            return launch_by_k({   // PATCH_TALL = 0
+                // (SETTLS_order = 0, the library default, compiled as such: no tile, no iteration blocks -- C3 1.73 -> 1.69 ms against the run-time-K instance)
+                LC_INSTANCE(0, true, advect_lds2_kernel, 0),
+                LC_INSTANCE(0, false, advect_lds2_kernel, 0),   // (cyclic_xboundary=False is the reference's default too)
+                // (SETTLS_order 1, 2, 3 compiled as such too: the iteration loop unrolls and the kernel keeps the K = 4 instance's 59 registers
+                // instead of the run-time-K instance's 71 -- C3 at K = 1: 3.28 -> 2.91 ms, K = 2: 4.26 -> 3.93)
+                LC_INSTANCE(1, true, advect_lds2_kernel, 0),
+                LC_INSTANCE(2, true, advect_lds2_kernel, 0),
+                LC_INSTANCE(3, true, advect_lds2_kernel, 0),
+                LC_K4(LC_INSTANCE, advect_lds2_kernel, 0)}, g2, st, A);
         }
         // (order 3 also with SETTLS_order = 0, the reference's default: the Euler sample alone already gains from its LDS tile)
         if (ORDER == 3 && two_seed && (A.ext || A.K == 0) && A.nx_f + LC_PAD >= TileGeom<3>::COLS && A.ny_f + LC_PAD >= TileGeom<3>::ROWS) {
             // order 3, two seeds per lane: the same patches and patch modes as above
             int g2;
             const int mode = two_seed_patch_grid(A, true, g2);
-            if (mode == PATCH_LINES) {
-                if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds2_o3_kernel<4, true, PATCH_LINES>, g2, st, A, "advect_lds2_o3_kernel<4, true, 2>");
-                if (A.K == 4) return launch_kernel(advect_lds2_o3_kernel<4, false, PATCH_LINES>, g2, st, A, "advect_lds2_o3_kernel<4, false, 2>");
-                if (A.cyclic) return launch_kernel(advect_lds2_o3_kernel<-1, true, PATCH_LINES>, g2, st, A, "advect_lds2_o3_kernel<-1, true, 2>");
-                return launch_kernel(advect_lds2_o3_kernel<-1, false, PATCH_LINES>, g2, st, A, "advect_lds2_o3_kernel<-1, false, 2>");
-            }
-            if (mode == PATCH_WIDE) {
-                if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds2_o3_kernel<4, true, PATCH_WIDE>, g2, st, A, "advect_lds2_o3_kernel<4, true, 1>");
-                if (A.K == 4) return launch_kernel(advect_lds2_o3_kernel<4, false, PATCH_WIDE>, g2, st, A, "advect_lds2_o3_kernel<4, false, 1>");
-                if (A.cyclic) return launch_kernel(advect_lds2_o3_kernel<-1, true, PATCH_WIDE>, g2, st, A, "advect_lds2_o3_kernel<-1, true, 1>");
-                return launch_kernel(advect_lds2_o3_kernel<-1, false, PATCH_WIDE>, g2, st, A, "advect_lds2_o3_kernel<-1, false, 1>");
-            }
-            // (interp_order = 3 with SETTLS_order = 0 are the reference's DEFAULT arguments: compiled as such, 85 registers instead of
-            // 94 + scratch and no iteration blocks -- C3 3.26 -> 3.10 ms against the run-time-K instance)
-            if (A.K == 0 && A.cyclic) return launch_kernel(advect_lds2_o3_kernel<0, true, PATCH_TALL>, g2, st, A, "advect_lds2_o3_kernel<0, true, 0>");
-            if (A.K == 0) return launch_kernel(advect_lds2_o3_kernel<0, false, PATCH_TALL>, g2, st, A, "advect_lds2_o3_kernel<0, false, 0>");   // (... with cyclic_xboundary=False, its default)
-            // (order-3 instances for K = 1, 2: measured, < 1 %)
-            if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds2_o3_kernel<4, true, PATCH_TALL>, g2, st, A, "advect_lds2_o3_kernel<4, true, 0>");
-            if (A.K == 4) return launch_kernel(advect_lds2_o3_kernel<4, false, PATCH_TALL>, g2, st, A, "advect_lds2_o3_kernel<4, false, 0>");
-            if (A.cyclic) return launch_kernel(advect_lds2_o3_kernel<-1, true, PATCH_TALL>, g2, st, A, "advect_lds2_o3_kernel<-1, true, 0>");
-            return launch_kernel(advect_lds2_o3_kernel<-1, false, PATCH_TALL>, g2, st, A, "advect_lds2_o3_kernel<-1, false, 0>");
+            if (mode == PATCH_LINES) return launch_by_k({LC_K4(LC_INSTANCE, advect_lds2_o3_kernel, 2 /* PATCH_LINES */)}, g2, st, A);
+            if (mode == PATCH_WIDE) return launch_by_k({LC_K4(LC_INSTANCE, advect_lds2_o3_kernel, 1 /* PATCH_WIDE */)}, g2, st, A);
+            return launch_by_k({   // PATCH_TALL = 0
+                // (interp_order = 3 with SETTLS_order = 0 are the reference's DEFAULT arguments: compiled as such, 85 registers instead of
+                // 94 + scratch and no iteration blocks -- C3 3.26 -> 3.10 ms against the run-time-K instance)
+                LC_INSTANCE(0, true, advect_lds2_o3_kernel, 0),
+                LC_INSTANCE(0, false, advect_lds2_o3_kernel, 0),   // (... with cyclic_xboundary=False, its default)
+                // (order-3 instances for K = 1, 2: measured, < 1 %)
+                LC_K4(LC_INSTANCE, advect_lds2_o3_kernel, 0)}, g2, st, A);
         }
         // the fixed-size tile must fit inside one padded time level
         if ((!A.ext && !(ORDER == 3 && A.K == 0)) || A.nx_f + LC_PAD < TileGeom<ORDER>::COLS || A.ny_f + LC_PAD < TileGeom<ORDER>::ROWS) return nullptr;
@@ -2753,23 +2774,15 @@ struct LdsLaunch<float, ORDER> {
             A.xcd_chunk = lcplan::xcd_chunk_tiles(A.ntx, nty, A.xcd_rows, A.xcd_split);
             g1 = lcplan::xcd_grid(A.ntiles, A.xcd_chunk) + A.pole_blocks;
         }
-        // K = 4 is the setting the reference's example and drivers use
-        if (lines) {
-            if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds_kernel<ORDER, 4, true, true>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, 4, true, lines>" : "advect_lds_kernel<1, 4, true, lines>");
-            if (A.K == 4) return launch_kernel(advect_lds_kernel<ORDER, 4, false, true>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, 4, false, lines>" : "advect_lds_kernel<1, 4, false, lines>");
-            if (A.cyclic) return launch_kernel(advect_lds_kernel<ORDER, -1, true, true>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, -1, true, lines>" : "advect_lds_kernel<1, -1, true, lines>");
-            return launch_kernel(advect_lds_kernel<ORDER, -1, false, true>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, -1, false, lines>" : "advect_lds_kernel<1, -1, false, lines>");
-        }
-        if (A.verify) {  // lc_ctx_set_verify: the instances that audit each wave's tile and slot level by level
-            if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds_kernel<ORDER, 4, true, false, true>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, 4, true, verify>" : "advect_lds_kernel<1, 4, true, verify>");
-            if (A.K == 4) return launch_kernel(advect_lds_kernel<ORDER, 4, false, false, true>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, 4, false, verify>" : "advect_lds_kernel<1, 4, false, verify>");
-            if (A.cyclic) return launch_kernel(advect_lds_kernel<ORDER, -1, true, false, true>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, -1, true, verify>" : "advect_lds_kernel<1, -1, true, verify>");
-            return launch_kernel(advect_lds_kernel<ORDER, -1, false, false, true>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, -1, false, verify>" : "advect_lds_kernel<1, -1, false, verify>");
-        }
-        if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds_kernel<ORDER, 4, true, false>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, 4, true>" : "advect_lds_kernel<1, 4, true>");
-        if (A.K == 4) return launch_kernel(advect_lds_kernel<ORDER, 4, false, false>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, 4, false>" : "advect_lds_kernel<1, 4, false>");
-        if (A.cyclic) return launch_kernel(advect_lds_kernel<ORDER, -1, true, false>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, -1, true>" : "advect_lds_kernel<1, -1, true>");
-        return launch_kernel(advect_lds_kernel<ORDER, -1, false, false>, g1, st, A, ORDER == 3 ? "advect_lds_kernel<3, -1, false>" : "advect_lds_kernel<1, -1, false>");
+        // advect_lds_kernel<ORDER, KF, CYC, LINES, VERIFY>, named <order, KF, CYC> and what TAIL says of the rest
+#define LC_LDS1(KF, CYC, TAIL, ...)                                                                                   \
+    {KF, CYC, advect_lds_kernel<ORDER, KF, CYC, __VA_ARGS__>,                                                         \
+     ORDER == 3 ? "advect_lds_kernel<3, " #KF ", " #CYC TAIL ">" : "advect_lds_kernel<1, " #KF ", " #CYC TAIL ">"}
+        if (lines) return launch_by_k({LC_K4(LC_LDS1, ", lines", true)}, g1, st, A);
+        // lc_ctx_set_verify: the instances that audit each wave's tile and slot level by level
+        if (A.verify) return launch_by_k({LC_K4(LC_LDS1, ", verify", false, true)}, g1, st, A);
+        return launch_by_k({LC_K4(LC_LDS1, "", false)}, g1, st, A);
+#undef LC_LDS1
     }
 };
 
@@ -3799,6 +3812,7 @@ template <typename T>
 struct Lds64Launch {
     static const char *launch(const AdvectArgs<T> &, int, hipStream_t, int) { return nullptr; }
     static const char *launch_o3(const AdvectArgs<T> &, int, hipStream_t, int) { return nullptr; }
+    static const char *launch_lin32(const AdvectArgs<T> &, int, hipStream_t, int) { return nullptr; }
 };
 template <>
 struct Lds64Launch<double> {
@@ -3806,6 +3820,9 @@ struct Lds64Launch<double> {
     // the wind is float32-valued (numpy promotion path), K = 0, or the field is smaller than a tile
     static const char *launch(const AdvectArgs<double> &A, int grid, hipStream_t st, int mode) {
         if (mode == 0 || A.wind_f32 || A.K == 0 || !(A.ext || A.ext_raw) || A.nx_f + LC_PAD < T64_COLS || A.ny_f + LC_PAD < T64_ROWS) return nullptr;
+        // (names as a profiler prints them; the last argument: 0 = lin + ext images, 1 = raw planes for the Euler sample + ext
+        // image, 2 = raw planes for both, the fused-level value formed node by node: lc_advect_ex)
+        const int sr = A.ext_raw ? 2 : (A.u_raw ? 1 : 0);
         if (A.wg64 && A.nx_f + LC_PAD >= W64_COLS && A.ny_f + LC_PAD >= W64_ROWS) {   // one tile per workgroup (LCS_F64_WG_TILE=1: measured, off by default)
             AdvectArgs<double> B = A;
             B.ntx = (A.nx + W64_SIDE - 1) / W64_SIDE;
@@ -3813,73 +3830,55 @@ struct Lds64Launch<double> {
             B.ntiles = B.ntx * nty;
             B.xcd_chunk = lcplan::xcd_chunk_tiles(B.ntx, nty, A.xcd_rows, A.xcd_split);
             const int gw = lcplan::xcd_grid(B.ntiles, B.xcd_chunk) + B.pole_blocks;
-            const int sr = A.ext_raw ? 2 : (A.u_raw ? 1 : 0);
-            if (A.K == 4 && A.cyclic && sr == 2) return launch_kernel(advect_wg64_kernel<4, true, 2>, gw, st, B, "advect_wg64_kernel<4, true, 2>");
-            if (A.K == 4 && A.cyclic && sr == 1) return launch_kernel(advect_wg64_kernel<4, true, 1>, gw, st, B, "advect_wg64_kernel<4, true, 1>");
-            if (A.K == 4 && A.cyclic) return launch_kernel(advect_wg64_kernel<4, true, 0>, gw, st, B, "advect_wg64_kernel<4, true, 0>");
-            if (A.cyclic && sr == 2) return launch_kernel(advect_wg64_kernel<-1, true, 2>, gw, st, B, "advect_wg64_kernel<-1, true, 2>");
-            if (A.cyclic && sr == 1) return launch_kernel(advect_wg64_kernel<-1, true, 1>, gw, st, B, "advect_wg64_kernel<-1, true, 1>");
-            if (A.cyclic) return launch_kernel(advect_wg64_kernel<-1, true, 0>, gw, st, B, "advect_wg64_kernel<-1, true, 0>");
-            if (sr == 2) return launch_kernel(advect_wg64_kernel<-1, false, 2>, gw, st, B, "advect_wg64_kernel<-1, false, 2>");
-            if (sr == 1) return launch_kernel(advect_wg64_kernel<-1, false, 1>, gw, st, B, "advect_wg64_kernel<-1, false, 1>");
-            return launch_kernel(advect_wg64_kernel<-1, false, 0>, gw, st, B, "advect_wg64_kernel<-1, false, 0>");
+            // (no <4, false, *> instance: SETTLS_order 4 without the cyclic boundary takes the run-time K)
+#define LC_WG64(SRC) {LC_INSTANCE(4, true, advect_wg64_kernel, SRC), LC_INSTANCE(-1, true, advect_wg64_kernel, SRC), LC_INSTANCE(-1, false, advect_wg64_kernel, SRC)}
+            if (sr == 2) return launch_by_k(LC_WG64(2), gw, st, B);
+            if (sr == 1) return launch_by_k(LC_WG64(1), gw, st, B);
+            return launch_by_k(LC_WG64(0), gw, st, B);
+#undef LC_WG64
         }
-        // (names as a profiler prints them; the last argument: 0 = lin + ext images, 1 = raw planes for the Euler sample + ext
-        // image, 2 = raw planes for both, the fused-level value formed node by node: lc_advect_ex)
-        if (A.ext_raw) {
-            if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds64_kernel<4, true, 2>, grid, st, A, "advect_lds64_kernel<4, true, 2>");
-            if (A.K == 4) return launch_kernel(advect_lds64_kernel<4, false, 2>, grid, st, A, "advect_lds64_kernel<4, false, 2>");
-            if (A.cyclic) return launch_kernel(advect_lds64_kernel<-1, true, 2>, grid, st, A, "advect_lds64_kernel<-1, true, 2>");
-            return launch_kernel(advect_lds64_kernel<-1, false, 2>, grid, st, A, "advect_lds64_kernel<-1, false, 2>");
-        }
-        if (A.u_raw) {
-            if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds64_kernel<4, true, 1>, grid, st, A, "advect_lds64_kernel<4, true, 1>");
-            if (A.K == 4) return launch_kernel(advect_lds64_kernel<4, false, 1>, grid, st, A, "advect_lds64_kernel<4, false, 1>");
-            if (A.cyclic) return launch_kernel(advect_lds64_kernel<-1, true, 1>, grid, st, A, "advect_lds64_kernel<-1, true, 1>");
-            return launch_kernel(advect_lds64_kernel<-1, false, 1>, grid, st, A, "advect_lds64_kernel<-1, false, 1>");
-        }
-        if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds64_kernel<4, true, 0>, grid, st, A, "advect_lds64_kernel<4, true, 0>");
-        if (A.K == 4) return launch_kernel(advect_lds64_kernel<4, false, 0>, grid, st, A, "advect_lds64_kernel<4, false, 0>");
-        if (A.cyclic) return launch_kernel(advect_lds64_kernel<-1, true, 0>, grid, st, A, "advect_lds64_kernel<-1, true, 0>");
-        return launch_kernel(advect_lds64_kernel<-1, false, 0>, grid, st, A, "advect_lds64_kernel<-1, false, 0>");
+        if (sr == 2) return launch_by_k({LC_K4(LC_INSTANCE, advect_lds64_kernel, 2)}, grid, st, A);
+        if (sr == 1) return launch_by_k({LC_K4(LC_INSTANCE, advect_lds64_kernel, 1)}, grid, st, A);
+        return launch_by_k({LC_K4(LC_INSTANCE, advect_lds64_kernel, 0)}, grid, st, A);
     }
     // order 3 (SETTLS_order = 0 included: the Euler sample has its own tile)
     static const char *launch_o3(const AdvectArgs<double> &A, int grid, hipStream_t st, int mode) {
         if (mode == 0 || A.wind_f32 || !(A.ext || A.ext_cub) || A.nx_f + LC_PAD < T64O3 || A.ny_f + LC_PAD < T64O3) return nullptr;
-        if (A.ext_cub) {  // no ext image: the iteration tile is formed from img[t], img[t+1] while it is staged
-            if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds64_o3_kernel<4, true, true>, grid, st, A, "advect_lds64_o3_kernel<4, true, cub>");
-            if (A.K == 4) return launch_kernel(advect_lds64_o3_kernel<4, false, true>, grid, st, A, "advect_lds64_o3_kernel<4, false, cub>");
-            if (A.cyclic) return launch_kernel(advect_lds64_o3_kernel<-1, true, true>, grid, st, A, "advect_lds64_o3_kernel<-1, true, cub>");
-            return launch_kernel(advect_lds64_o3_kernel<-1, false, true>, grid, st, A, "advect_lds64_o3_kernel<-1, false, cub>");
+        // no ext image (EXTCUB = true, "cub"): the iteration tile is formed from img[t], img[t+1] while it is staged
+        if (A.ext_cub) return launch_by_k({LC_K4(LC_INSTANCE_AS, advect_lds64_o3_kernel, cub, true)}, grid, st, A);
+        return launch_by_k({LC_K4(LC_INSTANCE, advect_lds64_o3_kernel)}, grid, st, A);
+    }
+    // LC_F64_WIND_F32_LIN32 (the wind as float32 images or planes; NULL: not such a call, or order 3 without its tiles)
+    static const char *launch_lin32(const AdvectArgs<double> &A, int grid, hipStream_t st, int mode) {
+        if (A.lin32) {  // order 1: per-wave LDS tiles of levels t and t + 1, or direct gathers
+            if (mode != 0 && A.K > 0 && A.nx_f + LC_PAD >= TW_COLS && A.ny_f + LC_PAD >= TW_ROWS)
+                return launch_by_k({LC_K4(LC_INSTANCE, advect_lds64w_kernel)}, grid, st, A);
+            return launch_kernel(advect_w32_kernel, grid, st, A, "advect_w32_kernel");
         }
-        if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds64_o3_kernel<4, true>, grid, st, A, "advect_lds64_o3_kernel<4, true>");
-        if (A.K == 4) return launch_kernel(advect_lds64_o3_kernel<4, false>, grid, st, A, "advect_lds64_o3_kernel<4, false>");
-        if (A.cyclic) return launch_kernel(advect_lds64_o3_kernel<-1, true>, grid, st, A, "advect_lds64_o3_kernel<-1, true>");
-        return launch_kernel(advect_lds64_o3_kernel<-1, false>, grid, st, A, "advect_lds64_o3_kernel<-1, false>");
+        // order 3: tiles of the float64 coefficients of levels t and t + 1 (else: the generic kernel, whose pole rows read the
+        // float32 planes)
+        if (A.u_raw32 && A.order == 3 && mode != 0 && A.nx_f + LC_PAD >= TW3 && A.ny_f + LC_PAD >= TW3)
+            return launch_by_k({LC_K4(LC_INSTANCE, advect_lds64w_o3_kernel)}, grid, st, A);
+        return nullptr;
     }
 };
 
+// The direct-gather kernel of interpolation order ORDER (launch_fused names it: f64 / f32 as a profiler prints the instance)
 template <typename T, int ORDER>
 struct DirectLaunch {
-    static const char *launch(const AdvectArgs<T> &A, int grid, hipStream_t st) {
+    static const char *launch(const AdvectArgs<T> &A, int grid, hipStream_t st, const char *f64, const char *) {
         if constexpr (ORDER == 1 && sizeof(T) == 8) {
             // exact order with the raw planes as the order-1 source (lc_advect_ex)
-            if (A.u_raw) return launch_kernel(advect_kernel<T, 1, false, SRC_RAW_EULER>, grid, st, A, "advect_kernel<double, 1, false, 1>");
+            if (A.u_raw) return LC_ADVECT_F64(1, false, 1);
         }
-        // (as a profiler prints them: all four template arguments)
-        return launch_kernel(advect_kernel<T, ORDER>, grid, st, A,
-                             ORDER == 1 ? "advect_kernel<double, 1, false, 0>" : ORDER == 2 ? "advect_kernel<double, 2, false, 0>"
-                           : ORDER == 3 ? "advect_kernel<double, 3, false, 0>" : ORDER == 4 ? "advect_kernel<double, 4, false, 0>"
-                                                                                            : "advect_kernel<double, 5, false, 0>");
+        return launch_kernel(advect_kernel<T, ORDER>, grid, st, A, f64);
     }
 };
 template <int ORDER>
 struct DirectLaunch<float, ORDER> {
-    static const char *launch(const AdvectArgs<float> &A, int grid, hipStream_t st) {
-        if (ORDER == 1) return launch_kernel(advect_kernel_f32<ORDER>, grid, st, A, "advect_kernel_f32<1>");
-        return launch_kernel(advect_kernel_f32_wide<ORDER>, grid, st, A,
-                             ORDER == 2 ? "advect_kernel_f32_wide<2>" : ORDER == 3 ? "advect_kernel_f32_wide<3>"
-                           : ORDER == 4 ? "advect_kernel_f32_wide<4>" : "advect_kernel_f32_wide<5>");
+    static const char *launch(const AdvectArgs<float> &A, int grid, hipStream_t st, const char *, const char *f32) {
+        if (ORDER == 1) return launch_kernel(advect_kernel_f32<ORDER>, grid, st, A, f32);
+        return launch_kernel(advect_kernel_f32_wide<ORDER>, grid, st, A, f32);
     }
 };
 
@@ -4106,23 +4105,15 @@ __global__ void outer_store_batch_kernel(const AdvectArgs<T> A, const OuterArgs<
 // The sub-step kernels of an interpolation order (scipy's 1 .. 5: lc_advect_ex checked)
 template <typename T>
 static auto outer_substep_for(int order) {
-    switch (order) {
-        case 2: return outer_substep_kernel<T, 2>;
-        case 3: return outer_substep_kernel<T, 3>;
-        case 4: return outer_substep_kernel<T, 4>;
-        case 5: return outer_substep_kernel<T, 5>;
-        default: return outer_substep_kernel<T, 1>;
-    }
+#define LC_OUTER(ORD) return outer_substep_kernel<T, ORD>
+    LC_BY_ORDER(order, LC_OUTER)
+#undef LC_OUTER
 }
 template <typename T>
 static auto outer_substep_batch_for(int order) {
-    switch (order) {
-        case 2: return outer_substep_batch_kernel<T, 2>;
-        case 3: return outer_substep_batch_kernel<T, 3>;
-        case 4: return outer_substep_batch_kernel<T, 4>;
-        case 5: return outer_substep_batch_kernel<T, 5>;
-        default: return outer_substep_batch_kernel<T, 1>;
-    }
+#define LC_OUTER(ORD) return outer_substep_batch_kernel<T, ORD>
+    LC_BY_ORDER(order, LC_OUTER)
+#undef LC_OUTER
 }
 
 template <typename T>
@@ -4302,8 +4293,10 @@ struct AdvectCall {
     int dirs;                     // lc_advect_series_dirs: 2 = every window in both directions of time
 };
 
+// A checked call as the kernels read it: everything of AdvectArgs that does not change from launch to launch (advect_impl
+// sets the clamp flag, the level range and the member groups)
 template <typename T>
-int advect_impl(lc_ctx *ctx, const lc_advect_args &a, const AdvectCall &call) {
+static AdvectArgs<T> fill_advect_args(const lc_ctx *ctx, const lc_advect_args &a, const AdvectCall &call) {
     const int ny = a.ny, nx = a.nx, order = a.interp_order, K = a.settls_order, t0_stride = a.t0_stride;
     const int n_members = a.n_members * call.dirs;  // planes of x_out / y_out
     AdvectArgs<T> A{};
@@ -4341,22 +4334,9 @@ int advect_impl(lc_ctx *ctx, const lc_advect_args &a, const AdvectCall &call) {
     A.dtcy = (T)(a.timestep * conv_y);
     A.hdtcy = (T)((0.5 * a.timestep) * conv_y);
     A.K = K;
-    const bool outer = a.cyclic_x == LC_X_CLAMP_REFERENCE_OUTER;
     A.cyclic = a.cyclic_x == LC_X_CYCLIC;
     A.clamp_flag = nullptr;
     A.verify = sizeof(T) == 4 ? ctx->verify_dev : nullptr;
-    unsigned *clamp_flag = nullptr;
-    // lc_advect_series: one flag per member, decided per member (each keeps its fused result, or restarts at its own chunk)
-    const bool per_member = outer && call.series && n_members > 1;
-    const int n_flags = per_member ? n_members : 1;
-    if (outer) {
-        // fused kernel first, with a flag that says whether the clamp ever moved a parcel; if not, per-point and
-        // outer-product clamps coincide (both are no-ops) and the fused result IS the reference's
-        LC_HIP_CHECK(hipMallocAsync((void **)&clamp_flag, n_flags * sizeof(unsigned), ctx->stream));
-        (void)hipMemsetAsync(clamp_flag, 0, n_flags * sizeof(unsigned), ctx->stream);
-        A.clamp_flag = clamp_flag;
-        A.clamp_stride = per_member ? 1 : 0;
-    }
     A.t0 = a.t0;
     A.nsteps = a.nsteps;
     A.x_out = (T *)a.x_out;
@@ -4376,64 +4356,76 @@ int advect_impl(lc_ctx *ctx, const lc_advect_args &a, const AdvectCall &call) {
         A.pole_hi = pr.hi;
         A.pole_blocks = pr.blocks;
     }
-    const int grid = lcplan::xcd_grid(A.ntiles, A.xcd_chunk) + A.pole_blocks;
-    // Kernel choice (float + fused levels only; measured on MI355X, 4096^2 seeds, 96 steps, K=4, 8x8-seed waves):
-    //   order 1: direct gather 10.9 ms (vector-L1 lookup bound), LDS tiles 10.2 ms (VALU-issue bound);
-    //   order 3: direct gather 37.8 ms, LDS tiles 20.4 ms.
-    // With the wind scaled x4 / x10 (patches stretched far beyond a tile) the LDS kernel degrades to
-    // 10.7-11.9 ms against 11.0 for direct gathers: its global-gather fallback is per lane, so the worst
-    // case costs the tile bookkeeping only.  An adaptive "skip the tile when most lanes miss" vote was
-    // measured and dropped (it costs 5 % everywhere to save 8 % in that extreme).
-    // lc_ctx_set_lds_tiles / LCS_LDS_TILES (read once at context creation) override (profiling).
-    const bool use_lds = ctx->lds_tiles != 0;
+    return A;
+}
+
+// Kernel choice (float + fused levels only; measured on MI355X, 4096^2 seeds, 96 steps, K=4, 8x8-seed waves):
+//   order 1: direct gather 10.9 ms (vector-L1 lookup bound), LDS tiles 10.2 ms (VALU-issue bound);
+//   order 3: direct gather 37.8 ms, LDS tiles 20.4 ms.
+// With the wind scaled x4 / x10 (patches stretched far beyond a tile) the LDS kernel degrades to
+// 10.7-11.9 ms against 11.0 for direct gathers: its global-gather fallback is per lane, so the worst
+// case costs the tile bookkeeping only.  An adaptive "skip the tile when most lanes miss" vote was
+// measured and dropped (it costs 5 % everywhere to save 8 % in that extreme).
+// lc_ctx_set_lds_tiles / LCS_LDS_TILES (read once at context creation) override (profiling).
+// Launches the fused kernel of a call on `grid` workgroups; returns its name.
+template <typename T>
+static const char *launch_fused(const lc_ctx *ctx, const AdvectArgs<T> &A, int grid) {
+    hipStream_t st = ctx->stream;
+    const int mode = ctx->lds_tiles;
     const bool fused64 = sizeof(T) == 8 && (A.ext != nullptr || A.ext_raw || A.ext_cub);  // single-sample iterations in float64
-    auto launch = [&](const AdvectArgs<T> &A) -> const char * {  // the name of the kernel it launched
-        if constexpr (sizeof(T) == 8) {
-            if (A.lin32) {  // LC_F64_WIND_F32_LIN32: per-wave LDS tiles of levels t and t + 1, or direct gathers
-                const bool tiles = use_lds && A.K > 0 && A.nx_f + LC_PAD >= TW_COLS && A.ny_f + LC_PAD >= TW_ROWS;
-                if (tiles && A.K == 4 && A.cyclic) return launch_kernel(advect_lds64w_kernel<4, true>, grid, ctx->stream, A, "advect_lds64w_kernel<4, true>");
-                if (tiles && A.K == 4) return launch_kernel(advect_lds64w_kernel<4, false>, grid, ctx->stream, A, "advect_lds64w_kernel<4, false>");
-                if (tiles && A.cyclic) return launch_kernel(advect_lds64w_kernel<-1, true>, grid, ctx->stream, A, "advect_lds64w_kernel<-1, true>");
-                if (tiles) return launch_kernel(advect_lds64w_kernel<-1, false>, grid, ctx->stream, A, "advect_lds64w_kernel<-1, false>");
-                return launch_kernel(advect_w32_kernel, grid, ctx->stream, A, "advect_w32_kernel");
-            }
-            if (A.u_raw32 && order == 3 && use_lds && A.nx_f + LC_PAD >= TW3 && A.ny_f + LC_PAD >= TW3) {
-                // LC_F64_WIND_F32_LIN32 at order 3: tiles of the float64 coefficients of levels t and t + 1 (else: the generic kernel below,
-                // whose pole rows read the float32 planes)
-                if (A.K == 4 && A.cyclic) return launch_kernel(advect_lds64w_o3_kernel<4, true>, grid, ctx->stream, A, "advect_lds64w_o3_kernel<4, true>");
-                if (A.K == 4) return launch_kernel(advect_lds64w_o3_kernel<4, false>, grid, ctx->stream, A, "advect_lds64w_o3_kernel<4, false>");
-                if (A.cyclic) return launch_kernel(advect_lds64w_o3_kernel<-1, true>, grid, ctx->stream, A, "advect_lds64w_o3_kernel<-1, true>");
-                return launch_kernel(advect_lds64w_o3_kernel<-1, false>, grid, ctx->stream, A, "advect_lds64w_o3_kernel<-1, false>");
-            }
+    const char *name = Lds64Launch<T>::launch_lin32(A, grid, st, mode);
+    if (name) return name;
+    if (A.order == 3) {
+        if (fused64) {
+            name = Lds64Launch<T>::launch_o3(A, grid, st, mode);
+            // (with ext_cub too: advect_seed_fast64_o3 looks at it)
+            return name ? name : launch_kernel(advect_kernel<T, 3, sizeof(T) == 8>, grid, st, A, "advect_kernel<double, 3, true, 0>");
         }
-        const char *name = nullptr;
-        if (order == 2 || order == 4 || order == 5) {  // generic direct kernel, any dtype
-            name = order == 2 ? DirectLaunch<T, 2>::launch(A, grid, ctx->stream)
-                 : order == 4 ? DirectLaunch<T, 4>::launch(A, grid, ctx->stream) : DirectLaunch<T, 5>::launch(A, grid, ctx->stream);
-        } else if (order == 3) {
-            if (fused64) {
-                name = Lds64Launch<T>::launch_o3(A, grid, ctx->stream, ctx->lds_tiles);
-                // (with ext_cub too: advect_seed_fast64_o3 looks at it)
-                if (!name) return launch_kernel(advect_kernel<T, 3, sizeof(T) == 8>, grid, ctx->stream, A, "advect_kernel<double, 3, true, 0>");
-            } else if (!(use_lds && (name = LdsLaunch<T, 3>::launch(A, grid, ctx->stream, ctx->lds_tiles)))) {
-                name = DirectLaunch<T, 3>::launch(A, grid, ctx->stream);
+        if (mode != 0) name = LdsLaunch<T, 3>::launch(A, grid, st, mode);
+    } else if (A.order == 1) {
+        if (fused64) {
+            name = Lds64Launch<T>::launch(A, grid, st, mode);
+            if (name) return name;
+            if constexpr (sizeof(T) == 8) {
+                if (A.ext_raw) return LC_ADVECT_F64(1, true, 2);
+                if (A.u_raw) return LC_ADVECT_F64(1, true, 1);
+                return LC_ADVECT_F64(1, true, 0);
             }
-        } else {
-            if (fused64) {
-                name = Lds64Launch<T>::launch(A, grid, ctx->stream, ctx->lds_tiles);
-                if (!name) {
-                    if constexpr (sizeof(T) == 8) {
-                        if (A.ext_raw) return launch_kernel(advect_kernel<T, 1, true, SRC_RAW_ALL>, grid, ctx->stream, A, "advect_kernel<double, 1, true, 2>");
-                        if (A.u_raw) return launch_kernel(advect_kernel<T, 1, true, SRC_RAW_EULER>, grid, ctx->stream, A, "advect_kernel<double, 1, true, 1>");
-                        return launch_kernel(advect_kernel<T, 1, true>, grid, ctx->stream, A, "advect_kernel<double, 1, true, 0>");
-                    }
-                }
-            } else if (!(use_lds && (name = LdsLaunch<T, 1>::launch(A, grid, ctx->stream, ctx->lds_tiles)))) {
-                name = DirectLaunch<T, 1>::launch(A, grid, ctx->stream);
-            }
-        }
-        return name;
-    };
+        } else if (mode != 0)
+            name = LdsLaunch<T, 1>::launch(A, grid, st, mode);
+    }
+    if (name) return name;
+    // no LDS-tile kernel applies (orders 2, 4, 5: never): the direct-gather kernel of the order, named with all four template
+    // arguments in float64, as a profiler prints them
+#define LC_DIRECT(ORD) return DirectLaunch<T, ORD>::launch(A, grid, st, "advect_kernel<double, " #ORD ", false, 0>", "advect_kernel_f32_wide<" #ORD ">")
+    switch (A.order) {
+        LC_ORDERS_2_TO_5(LC_DIRECT)
+        default: return DirectLaunch<T, 1>::launch(A, grid, st, "advect_kernel<double, 1, false, 0>", "advect_kernel_f32<1>");
+    }
+#undef LC_DIRECT
+}
+
+template <typename T>
+int advect_impl(lc_ctx *ctx, const lc_advect_args &a, const AdvectCall &call) {
+    const int ny = a.ny, nx = a.nx, order = a.interp_order, K = a.settls_order, t0_stride = a.t0_stride;
+    const int n_members = a.n_members * call.dirs;  // planes of x_out / y_out
+    AdvectArgs<T> A = fill_advect_args<T>(ctx, a, call);
+    const bool outer = a.cyclic_x == LC_X_CLAMP_REFERENCE_OUTER;
+    unsigned *clamp_flag = nullptr;
+    // lc_advect_series: one flag per member, decided per member (each keeps its fused result, or restarts at its own chunk)
+    const bool per_member = outer && call.series && n_members > 1;
+    const int n_flags = per_member ? n_members : 1;
+    if (outer) {
+        // fused kernel first, with a flag that says whether the clamp ever moved a parcel; if not, per-point and
+        // outer-product clamps coincide (both are no-ops) and the fused result IS the reference's
+        LC_HIP_CHECK(hipMallocAsync((void **)&clamp_flag, n_flags * sizeof(unsigned), ctx->stream));
+        (void)hipMemsetAsync(clamp_flag, 0, n_flags * sizeof(unsigned), ctx->stream);
+        A.clamp_flag = clamp_flag;
+        A.clamp_stride = per_member ? 1 : 0;
+    }
+    const int grid = lcplan::xcd_grid(A.ntiles, A.xcd_chunk) + A.pole_blocks;
+    const bool use_lds = ctx->lds_tiles != 0;
+    auto launch = [&](const AdvectArgs<T> &C) { return launch_fused(ctx, C, grid); };
     const char *name = nullptr;
     // Level chunks (lc_ctx_set_level_chunk): the series runs as consecutive launches of at most `chunk` time levels,
     // each continuing from the positions the previous one left in x_out / y_out (a seed's start is read by the thread
@@ -4710,13 +4702,7 @@ int sample_impl(lc_ctx *ctx, const SampleCall &c) {
 #define LC_SAMPLE(ORD)                                                                                                     \
     hipLaunchKernelGGL((sample_kernel<T, ORD>), dim3(blocks), dim3(256), 0, ctx->stream, A, (const T *)c.px, (const T *)c.py, \
                        c.level, (T *)c.out_u, (T *)c.out_v)
-    switch (c.interp_order) {
-        case 2: LC_SAMPLE(2); break;
-        case 3: LC_SAMPLE(3); break;
-        case 4: LC_SAMPLE(4); break;
-        case 5: LC_SAMPLE(5); break;
-        default: LC_SAMPLE(1); break;
-    }
+    LC_BY_ORDER(c.interp_order, LC_SAMPLE)
 #undef LC_SAMPLE
     LC_HIP_CHECK(hipGetLastError());
     return LC_OK;
@@ -4821,22 +4807,15 @@ int tracer_impl(lc_ctx *ctx, const lc_tracer_args &a, const FieldSource &src) {
     O.count = a.mean_count;
     const size_t n = (size_t)a.ny * a.nx;
     const unsigned blocks = (unsigned)((n + 255) / 256);
-    static const char *const names[2][5] = {
-        {"tracer_kernel<float, 1>", "tracer_kernel<float, 2>", "tracer_kernel<float, 3>", "tracer_kernel<float, 4>", "tracer_kernel<float, 5>"},
-        {"tracer_kernel<double, 1>", "tracer_kernel<double, 2>", "tracer_kernel<double, 3>", "tracer_kernel<double, 4>", "tracer_kernel<double, 5>"}};
+    const char *name = nullptr;
 #define LC_TRACER(ORD)                                                                                                  \
     hipLaunchKernelGGL((tracer_kernel<T, ORD>), dim3(blocks), dim3(256), 0, ctx->stream, A, (const T *)a.traj_x,          \
-                       (const T *)a.traj_y, a.level0, a.n_levels, O)
-    switch (a.interp_order) {
-        case 2: LC_TRACER(2); break;
-        case 3: LC_TRACER(3); break;
-        case 4: LC_TRACER(4); break;
-        case 5: LC_TRACER(5); break;
-        default: LC_TRACER(1); break;
-    }
+                       (const T *)a.traj_y, a.level0, a.n_levels, O);                                                     \
+    name = sizeof(T) == 8 ? "tracer_kernel<double, " #ORD ">" : "tracer_kernel<float, " #ORD ">"
+    LC_BY_ORDER(a.interp_order, LC_TRACER)
 #undef LC_TRACER
     LC_HIP_CHECK(hipGetLastError());
-    ctx->last_tracer_kernel = names[sizeof(T) == 8][a.interp_order - 1];
+    ctx->last_tracer_kernel = name;
     return LC_OK;
 }
 

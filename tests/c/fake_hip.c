@@ -98,7 +98,7 @@ static int cmp_size(const void *a, const void *b) { size_t x = *(const size_t *)
 void fake_hip_trace_end(void) {                         /* the allocations since trace_begin, sorted; forgets the named host arrays */
     pthread_mutex_lock(&g_books);
     if (g_trace) {
-        qsort(g_trace_allocs, (size_t)g_ntrace_allocs, sizeof(size_t), cmp_size);
+        if (g_ntrace_allocs) qsort(g_trace_allocs, (size_t)g_ntrace_allocs, sizeof(size_t), cmp_size);   /* (never allocated: NULL) */
         fprintf(g_trace, "allocs");
         for (int i = 0; i < g_ntrace_allocs; ++i) fprintf(g_trace, " %zu", g_trace_allocs[i]);
         fprintf(g_trace, "\n");

@@ -30,8 +30,8 @@ LC_PAD = 3          # csrc/lcs_common.h: lc_level_elems = (ny_f + LC_PAD) * (nx_
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
 
 
-def build_driver(workdir):
-    """tests/c/host_route_trace.cpp linked with the host side of csrc/ and the recording runtime; the program's path."""
+def build_driver(workdir, driver="host_route_trace"):
+    """tests/c/<driver>.cpp linked with the host side of csrc/ and the recording runtime; the program's path."""
     workdir = str(workdir)
     objs, procs = [], []
     for u in UNITS:
@@ -49,10 +49,10 @@ def build_driver(workdir):
     clangxx = os.path.join(os.path.dirname(os.path.realpath(HIPCC)), "..", "lib", "llvm", "bin", "clang++")
     if not os.path.exists(clangxx):
         clangxx = "/opt/rocm/lib/llvm/bin/clang++"
-    drv = os.path.join(workdir, "host_route_trace.o")
-    subprocess.run([clangxx, "-std=c++17", "-Wall", "-Wextra", "-O1", "-c", os.path.join(ROOT, "tests", "c", "host_route_trace.cpp"), "-o", drv],
+    drv = os.path.join(workdir, driver + ".o")
+    subprocess.run([clangxx, "-std=c++17", "-Wall", "-Wextra", "-O1", "-c", os.path.join(ROOT, "tests", "c", driver + ".cpp"), "-o", drv],
                    check=True)
-    exe = os.path.join(workdir, "host_route_trace")
+    exe = os.path.join(workdir, driver)
     # (each host object refers to its own __hip_fatbin_<hash>, which only a device link defines: left unresolved, never read)
     r = subprocess.run([clangxx, drv, *objs, fake, "-o", exe, "-ldl", "-lm", "-lpthread", "-Wl,--unresolved-symbols=ignore-all"],
                        capture_output=True, text=True)

@@ -1,10 +1,14 @@
 """The route table (tests/kernel_routes.py) against the dispatchers' kernel-name literals.  No GPU, no build.
 
-Every advect / sigma launch site reports the kernel it launched as a string literal (``LC_LDS2(..., "name")``,
-``return "name";``, ``ctx->last_sigma_kernel = "name"``).  The set of those literals must equal ``ROUTES`` plus
-``UNREACHABLE``: a new instance without a route fails here, and so does a route whose kernel is gone."""
+Every advect / sigma launch site reports the kernel it launched as a string literal (``return "name";``,
+``ctx->last_sigma_kernel = "name"``), which advect.hip's launch macros put together from the tokens that instantiate the
+kernel (``#FAMILY "<" ... ">"``): a literal exists once the preprocessor has run.  So the sources are read after
+``hipcc --cuda-host-only -E -P`` with adjacent literals joined, as the compiler joins them.  The set of those literals must
+equal ``ROUTES`` plus ``UNREACHABLE``: a new instance without a route fails here, and so does a route whose kernel is gone."""
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
@@ -13,24 +17,36 @@ from tests import kernel_routes as KR
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "lagrangiancoherence_amd", "csrc")
 SOURCES = ("advect.hip", "sigma.hip")
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
 
 # a quoted kernel name as the dispatch macros and returns spell it: family, optional template arguments
 NAME_RE = re.compile(r'"((?:advect|outer_substep|tracer|sigma)\w*(?:<[^"<>]*>)?)"')
 
 
 def kernel_names(text):
-    """The kernel-name literals of one source text, code only (comments dropped)."""
+    """The kernel-name literals of one source text, code only (comments dropped), adjacent literals joined."""
     code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     code = re.sub(r"//[^\n]*", "", code)
+    code = re.sub(r'"\s+"', "", code)        # "a" "b" is "ab" (no name literal holds an escaped quote)
     return set(NAME_RE.findall(code))
 
 
+def preprocessed(path, *flags):
+    """A source file as the host compiler sees it after macro expansion (no line markers)."""
+    r = subprocess.run([HIPCC, "--cuda-host-only", "-E", "-P", "-std=c++17", *flags, path], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return r.stdout
+
+
+_DISPATCHED = []
+
+
 def dispatched_names():
-    names = set()
-    for f in SOURCES:
-        with open(os.path.join(CSRC, f)) as fh:
-            names |= kernel_names(fh.read())
-    return names
+    if not _DISPATCHED:
+        _DISPATCHED.append(set().union(*(kernel_names(preprocessed(os.path.join(CSRC, f))) for f in SOURCES)))
+    return set(_DISPATCHED[0])
 
 
 def check_complete(names, routes, unreachable):
@@ -51,11 +67,30 @@ def test_extractor_sees_the_dispatch_forms():
         ctx->last_sigma_kernel = fd_fp32_cast ? "sigma_kernel<double, float>" : "sigma_kernel<double, double>";
         return launch_kernel(advect_lds2_kernel<7, true, PATCH_TALL>, g2, st, A, "advect_lds2_kernel<7, true, 0>");   // "advect_in_a_comment<1>"
         lc_set_error("lc_advect: bad dtype %d", dtype);
+        {4, true, advect_lds64_kernel<4, true, 2>, "advect_lds64_kernel" "<" "4, true, 2" ">"},
+        {-1, false, advect_lds_kernel<ORDER, -1, false, false, true>, ORDER == 3 ? "advect_lds_kernel<3, " "-1" ", " "false" ", verify" ">" : "advect_lds_kernel<1, " "-1" ", "
+             "false" ", verify" ">"}
+        name = sizeof(T) == 8 ? "tracer_kernel<double, " "5" ">" : "tracer_kernel<float, " "5" ">";
     '''
     assert kernel_names(snippet) == {
         "advect_lds2_kernel<4, false, 2>", "advect_lds_kernel<3, -1, false, lines>", "advect_lds_kernel<1, -1, false, lines>",
         "advect_lds64_o3_kernel<4, true, cub>", "outer_substep_kernel", "sigma_kernel<double, float>",
-        "sigma_kernel<double, double>", "advect_lds2_kernel<7, true, 0>"}
+        "sigma_kernel<double, double>", "advect_lds2_kernel<7, true, 0>", "advect_lds64_kernel<4, true, 2>",
+        "advect_lds_kernel<3, -1, false, verify>", "advect_lds_kernel<1, -1, false, verify>", "tracer_kernel<double, 5>",
+        "tracer_kernel<float, 5>"}
+
+
+def test_the_preprocessor_makes_the_names_the_extractor_reads(tmp_path):
+    """The macros' own spelling through the real preprocessor: stringified tokens, with and without trailing arguments."""
+    src = tmp_path / "names.hip"
+    src.write_text('''
+        #define LC_STR(...) #__VA_ARGS__
+        #define LC_INSTANCE(KF, CYC, FAMILY, ...) {KF, CYC, FAMILY<KF, CYC, ##__VA_ARGS__>, #FAMILY "<" LC_STR(KF, CYC, ##__VA_ARGS__) ">"}
+        #define LC_K4(INSTANCE, ...) INSTANCE(4, true, __VA_ARGS__), INSTANCE(-1, false, __VA_ARGS__)
+        x = {LC_K4(LC_INSTANCE, advect_fake_kernel, 2 /* PATCH_LINES */), LC_K4(LC_INSTANCE, advect_bare_kernel)};
+    ''')
+    assert kernel_names(preprocessed(str(src), "-nogpuinc", "-nogpulib")) == {
+        "advect_fake_kernel<4, true, 2>", "advect_fake_kernel<-1, false, 2>", "advect_bare_kernel<4, true>", "advect_bare_kernel<-1, false>"}
 
 
 def test_a_new_launch_site_or_a_stale_route_is_caught():
