@@ -38,7 +38,7 @@ extern "C" {
  * client built against 100 must be rebuilt), lc_ctx_get_level_chunk, lc_ctx_set/get_f64_fidelity, lc_advect_ex and
  * lc_sample_raw added, lc_field_pack accepts packed_dev == NULL at order 1 (fused-level image only).  lc_version() returns the value the LIBRARY
  * was built with: compare it with this macro before any other call (tests/c/abi_smoke.c, _capi.load do). */
-#define LC_VERSION 104 /* 0.1.4: + lc_label_components, lc_label_work_elems, lc_component_sums, lc_component_apply, + lc_strain, lc_ctx_last_strain_kernel, + lc_advect_series_dirs, + lc_advect_series, lc_sigma_batch, + lc_tracer_sample, lc_ctx_last_tracer_kernel (additive: no argument list changed), + lc_ctx_set_host_pipeline, lc_copy_to_device, lc_copy_to_host, lc_ctx_set_host_cache, lc_ctx_trim, lc_ctx_last_host_marks, lc_ctx_set_xcd_split (0.1.3: + lc_ctx_last_pack_kernel; 0.1.2: + lc_ctx_set_verify, lc_ctx_read_verify, LC_F64_WIND_F32_LIN32) */
+#define LC_VERSION 104 /* 0.1.4: + lc_mask_morphology, lc_morph_work_elems (added without a bump), + lc_label_components, lc_label_work_elems, lc_component_sums, lc_component_apply, + lc_strain, lc_ctx_last_strain_kernel, + lc_advect_series_dirs, + lc_advect_series, lc_sigma_batch, + lc_tracer_sample, lc_ctx_last_tracer_kernel (additive: no argument list changed), + lc_ctx_set_host_pipeline, lc_copy_to_device, lc_copy_to_host, lc_ctx_set_host_cache, lc_ctx_trim, lc_ctx_last_host_marks, lc_ctx_set_xcd_split (0.1.3: + lc_ctx_last_pack_kernel; 0.1.2: + lc_ctx_set_verify, lc_ctx_read_verify, LC_F64_WIND_F32_LIN32) */
 
 typedef struct lc_ctx lc_ctx;
 
@@ -683,6 +683,51 @@ typedef struct lc_distance_args {
     void *work_dev;
 } lc_distance_args;
 int lc_distance_transform(lc_ctx *ctx, const lc_distance_args *args);
+
+/* ---- thinning and dilating a ridge mask (skeletonize_ridges, dilate_ridges) -------------
+ * The two morphological steps of the driver's chain: skeletonize(ridges.values) between the Hessian mask and the filter
+ * (LCS/area_of_influence.py:207) and binary_dilation(ridges.values) at its end (:233).  Both entry points were added at
+ * LC_VERSION 104 without a bump: nothing that existed changed.  n_members independent planes [n_members][ny*nx] per call,
+ * every launch for all of them; pixels outside a plane are background; cyclic_x != 0: column nx-1 is the western neighbour
+ * of column 0 (rows r-1 .. r+1).
+ *
+ * Foreground: as above, a pixel whose value is != 0 and not NaN; mask: `dtype` elements, LC_F32 or LC_F64.
+ *   out          uint8 [n_members][ny*nx]: 1 on the pixels of the result, else 0
+ *   LC_MORPH_THIN    a parallel two-sub-iteration thinning driven by a table.  The neighbourhood index of a pixel is
+ *                NW + 2 N + 4 NE + 8 E + 16 SE + 32 S + 64 SW + 128 W (north: row r-1); table[index] is a 2-bit code, bit 0
+ *                "delete in the first sub-iteration", bit 1 "in the second".  A sub-iteration reads the whole plane as the
+ *                one before left it and deletes every foreground pixel whose code has its bit; an iteration is the first
+ *                followed by the second; thinning ends when an iteration deletes nothing, or after max_iterations (<= 0:
+ *                unbounded).  table: HOST pointer to 256 bytes, read before the call returns; a code above 3 is refused.
+ *   LC_MORPH_DILATE  a background pixel becomes foreground when a neighbour named in `structure` (bits of the same index:
+ *                170 = N, E, S, W; 255 = all eight) is foreground; max_iterations (>= 1) times.
+ *   iterations_per_launch  0: the library's default (4 thinning iterations = 8 sub-steps, 8 dilations); 1 .. that many: fewer
+ *                per launch.  The result does not depend on it.
+ *   launches_out HOST int, or NULL: the step launches the call made
+ *   work_dev     int32 [lc_morph_work_elems(ny, nx, n_members)] scratch (0 elements for bad sizes)
+ * Convergence is found by the host side of the call: after each launch but the last it reads back one word (the OR of one
+ * flag per tile) and stops when nothing changed.  That is one stream synchronisation per launch, i.e. per 4 thinning
+ * iterations; the call returns with at most one copy still enqueued.
+ * A null context, a wrong struct_size, a bad op, a plane of 2^31 pixels or more and a table code above 3 are refused with
+ * LC_EINVAL before any HIP call.
+ * No kernel of this call waits for another workgroup. */
+enum lc_morph_op { LC_MORPH_THIN = 0, LC_MORPH_DILATE = 1 };
+size_t lc_morph_work_elems(int ny, int nx, int n_members);
+typedef struct lc_morph_args {
+    size_t struct_size; /* sizeof(lc_morph_args): checked before any other field */
+    const void *mask;
+    int dtype, ny, nx, n_members;
+    int op;                      /* enum lc_morph_op */
+    int cyclic_x;
+    const uint8_t *table;        /* LC_MORPH_THIN: host, 256 codes 0 .. 3 */
+    int structure;               /* LC_MORPH_DILATE: 1 .. 255 */
+    int max_iterations;
+    int iterations_per_launch;   /* 0: the library's default */
+    void *out;                   /* uint8 [n_members][ny*nx] */
+    int *launches_out;           /* host, or NULL */
+    void *work_dev;
+} lc_morph_args;
+int lc_mask_morphology(lc_ctx *ctx, const lc_morph_args *args);
 
 /* ---- multi-GPU: halo exchange on RCCL ----------------------------------------
  * New (the reference is single-process).  One process per GPU,

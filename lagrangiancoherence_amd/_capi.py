@@ -167,6 +167,23 @@ class DistanceArgs(C.Structure):
 PROTOTYPES["lc_distance_work_elems"] = (_sz, [_i, _i, _i])
 PROTOTYPES["lc_distance_transform"] = (_i, [_vp, C.POINTER(DistanceArgs)])
 
+LC_MORPH_THIN, LC_MORPH_DILATE = 0, 1
+
+
+class MorphArgs(C.Structure):
+    """``lc_morph_args`` of include/lcs_hip.h, field for field."""
+    _fields_ = [("struct_size", _sz),
+                ("mask", _vp),
+                ("dtype", _i), ("ny", _i), ("nx", _i), ("n_members", _i),
+                ("op", _i), ("cyclic_x", _i),
+                ("table", _vp),
+                ("structure", _i), ("max_iterations", _i), ("iterations_per_launch", _i),
+                ("out", _vp), ("launches_out", C.POINTER(_i)), ("work_dev", _vp)]
+
+
+PROTOTYPES["lc_morph_work_elems"] = (_sz, [_i, _i, _i])
+PROTOTYPES["lc_mask_morphology"] = (_i, [_vp, C.POINTER(MorphArgs)])
+
 _lib = None
 
 

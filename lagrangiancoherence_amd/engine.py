@@ -1092,6 +1092,108 @@ class Engine:
             dist, nearest = dist[0], nearest[0] if return_nearest else None
         return (dist, nearest) if return_nearest else dist
 
+    # ------------------------------------------------------------------ thinning and dilating a mask
+    THINNING_METHODS = ("guohall", "zhang")
+    STRUCTURES = {1: 2 + 8 + 32 + 128, 2: 255}   # connectivity -> the neighbours of lc_morph_args.structure (N, E, S, W; all eight)
+
+    @staticmethod
+    def thinning_table(method):
+        """The 256 codes of a shipped thinning rule as a ``numpy.uint8`` array: entry ``NW + 2 N + 4 NE + 8 E + 16 SE + 32 S +
+        64 SW + 128 W`` is 1 where the pixel is deleted in the first sub-iteration, 2 in the second, 3 in both, 0 in neither.
+
+        ``'zhang'``: Zhang & Suen 1984.  With P2..P9 = N, NE, E, SE, S, SW, W, NW, B their sum and A the 0 -> 1 steps round
+        the cycle: deletable when 2 <= B <= 6 and A = 1; first sub-iteration N E S = 0 and E S W = 0, second N E W = 0 and
+        N S W = 0.  ``'guohall'``: Guo & Hall 1989, the rule ``bwmorph('thin')`` documents.  With x1..x8 = E, NE, N, NW, W, SW,
+        S, SE: G1 exactly one k in {1, 3, 5, 7} with ``not x_k and (x_{k+1} or x_{k+2})``; G2 min(n1, n2) in {2, 3} for
+        n1 = sum (x_{2k-1} or x_{2k}), n2 = sum (x_{2k} or x_{2k+1}); first sub-iteration ``not ((x2 or x3 or not x8) and x1)``,
+        second ``not ((x6 or x7 or not x4) and x5)``."""
+        if method not in Engine.THINNING_METHODS:
+            raise ValueError(f"method {method!r}: one of {', '.join(Engine.THINNING_METHODS)}")
+        table = np.zeros(256, dtype=np.uint8)
+        for i in range(256):
+            nw, n, ne, e, se, s, sw, w = ((i >> k) & 1 for k in range(8))
+            if method == "zhang":
+                p = [n, ne, e, se, s, sw, w, nw]
+                b, a = sum(p), sum(1 for k in range(8) if not p[k] and p[(k + 1) % 8])
+                ok = 2 <= b <= 6 and a == 1
+                first, second = ok and not n * e * s and not e * s * w, ok and not n * e * w and not n * s * w
+            else:
+                x = [None, e, ne, n, nw, w, sw, s, se, e, ne]                 # x[1..8], x[9] = x[1], x[10] = x[2]
+                g1 = sum(1 for k in (1, 3, 5, 7) if not x[k] and (x[k + 1] or x[k + 2])) == 1
+                n1 = sum(1 for k in (1, 2, 3, 4) if x[2 * k - 1] or x[2 * k])
+                n2 = sum(1 for k in (1, 2, 3, 4) if x[2 * k] or x[2 * k + 1])
+                ok = g1 and min(n1, n2) in (2, 3)
+                first = ok and not ((x[2] or x[3] or not x[8]) and x[1])
+                second = ok and not ((x[6] or x[7] or not x[4]) and x[5])
+            table[i] = (1 if first else 0) | (2 if second else 0)
+        return table
+
+    @staticmethod
+    def checked_thinning_table(table):
+        """``table`` as the contiguous ``numpy.uint8`` array the library reads, or ``ValueError``: 256 integer codes 0 .. 3."""
+        table = np.asarray(table)
+        if table.shape != (256,) or table.dtype.kind not in "iub" or (table.astype(np.int64) < 0).any() or (table.astype(np.int64) > 3).any():
+            raise ValueError("table: 256 integer codes 0 .. 3")
+        return np.ascontiguousarray(table, dtype=np.uint8)
+
+    def _morphology(self, mask, op, table, structure, cyclic, iterations, iterations_per_launch):
+        m = self._planes(mask)
+        n, ny, nx = (int(s) for s in m.shape)
+        torch = self.torch
+        out = torch.empty((n, ny, nx), dtype=torch.uint8, device=self.device)
+        elems = int(self.lib.lc_morph_work_elems(ny, nx, n))
+        # (a plane the call refuses for its size is refused before the buffer is touched)
+        work = torch.empty((max(1, elems if ny * nx < 2 ** 31 else 1),), dtype=torch.int32, device=self.device)
+        launches = C.c_int(0)
+        a = _capi.MorphArgs(struct_size=C.sizeof(_capi.MorphArgs))
+        a.mask, a.dtype = m.data_ptr(), _NP2LC[np.dtype(str(m.dtype).replace("torch.", ""))]
+        a.ny, a.nx, a.n_members, a.op, a.cyclic_x = ny, nx, n, op, int(bool(cyclic))
+        a.table = table.ctypes.data if table is not None else None
+        a.structure, a.max_iterations, a.iterations_per_launch = structure, iterations, int(iterations_per_launch or 0)
+        a.out, a.launches_out, a.work_dev = out.data_ptr(), C.pointer(launches), work.data_ptr()
+        self._use_current_stream()
+        _capi.check(self.lib.lc_mask_morphology(self.ctx, C.byref(a)), self.lib)
+        self.last_morphology_launches = launches.value
+        return out if len(mask.shape) == 3 else out[0]
+
+    @staticmethod
+    def _per_launch(iterations_per_launch):
+        if iterations_per_launch is not None and int(iterations_per_launch) < 1:
+            raise ValueError(f"iterations_per_launch {iterations_per_launch!r}: >= 1, or None for the library's default")
+
+    def thin(self, mask, table, cyclic=False, max_iterations=None, iterations_per_launch=None):
+        """``mask`` thinned by the parallel two-sub-iteration rule ``table`` encodes (``lc_mask_morphology``, LC_MORPH_THIN): a
+        ``torch.uint8`` device tensor of 0 / 1 shaped like ``mask`` -- ``(ny, nx)``, or ``(n_members, ny, nx)``, every plane on
+        its own in the same launches.
+
+        A pixel is foreground when it is ``!= 0`` and not NaN (float32 / float64 kept, any other dtype converted to float64);
+        pixels outside a plane are background; ``cyclic``: the last column is the western neighbour of the first.  ``table``:
+        256 codes as :meth:`thinning_table` returns them (bit 0: delete in the first sub-iteration, bit 1: in the second).
+        Thinning ends when an iteration deletes nothing or after ``max_iterations``.  ``iterations_per_launch`` (default 4, the
+        most a launch can do) only changes how the sub-iterations are cut into launches, never the result; after each launch
+        one word is read back to see whether anything changed (one synchronisation per launch).
+        ``last_morphology_launches`` holds the number of step launches of the last call."""
+        table = self.checked_thinning_table(table)
+        if max_iterations is not None and int(max_iterations) < 1:
+            raise ValueError(f"max_iterations {max_iterations!r}: >= 1, or None for no bound")
+        self._per_launch(iterations_per_launch)
+        return self._morphology(mask, _capi.LC_MORPH_THIN, table, 0, cyclic,
+                                0 if max_iterations is None else int(max_iterations), iterations_per_launch)
+
+    def dilate(self, mask, iterations=1, connectivity=1, cyclic=False, iterations_per_launch=None):
+        """``mask`` dilated ``iterations`` times (``lc_mask_morphology``, LC_MORPH_DILATE): a background pixel becomes foreground
+        when one of its four edge neighbours (``connectivity=1``) or eight neighbours (``2``) is foreground --
+        ``scipy.ndimage.binary_dilation(foreground, generate_binary_structure(2, connectivity), iterations)``.  A ``torch.uint8``
+        device tensor of 0 / 1 shaped like ``mask``; foreground, planes, ``cyclic`` and ``iterations_per_launch`` (default 8) as
+        for :meth:`thin`."""
+        if connectivity not in self.STRUCTURES:
+            raise ValueError(f"connectivity {connectivity!r}: 1 (edges) or 2 (edges and corners)")
+        if int(iterations) < 1:
+            raise ValueError(f"iterations {iterations!r}: >= 1")
+        self._per_launch(iterations_per_launch)
+        return self._morphology(mask, _capi.LC_MORPH_DILATE, None, self.STRUCTURES[connectivity], cyclic, int(iterations),
+                                iterations_per_launch)
+
     # ------------------------------------------------------------------ multi-GPU (RCCL through the C ABI)
     COMM_ID_BYTES = 128
 

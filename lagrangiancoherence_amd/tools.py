@@ -9,6 +9,9 @@
                                     from a package outside the reference: defined here, see its docstring)
 * ``distance_to_ridges``            LCS/area_of_influence.py:230-244: ``distance_transform_edt(~ridges_bool)``, of which the
                                     driver keeps ``dist < 12`` as the swath a ridge influences
+* ``skeletonize_ridges``            LCS/area_of_influence.py:207: ``skeletonize(ridges.values)``, the thinning between the Hessian
+                                    mask and the filter (scikit-image there: the rule is defined here, see its docstring)
+* ``dilate_ridges``                 LCS/area_of_influence.py:233: ``binary_dilation(ridges.values)``
 
 The remaining functions of that module (IDW regridding, harvesine, latlonsel) have no caller on the
 path.
@@ -18,10 +21,10 @@ from __future__ import annotations
 import numpy as np
 
 from .dropin import _coord, _make, _to_np, get_engine
-from .engine import common_dtype
+from .engine import Engine, common_dtype
 
 __all__ = ["xr_map_coordinates", "fourth_order_derivative", "derivative_spherical_coords",
-           "find_ridges_spherical_hessian", "filter_ridges", "distance_to_ridges"]
+           "find_ridges_spherical_hessian", "filter_ridges", "distance_to_ridges", "skeletonize_ridges", "dilate_ridges"]
 
 
 def xr_map_coordinates(da, new_x, new_y, isglobal=True, order=1):
@@ -213,3 +216,81 @@ def distance_to_ridges(ridges, cyclic=False, sampling=None, max_distance=None, r
     index = nearest.reshape(planes.shape).to(eng.torch.int64)
     owner = eng.torch.where(index >= 0, planes.gather(1, index.clamp(min=0)), eng.torch.zeros_like(planes))
     return out(dist), out(owner.reshape(labels.shape))
+
+
+def _ridge_planes(ridges):
+    """What the two morphological functions share: ``ridges`` sorted as ``filter_ridges`` sorts it, on the device with the
+    extra dimension (if any) leading, and the way back to the caller's class, dimension order and dtype."""
+    dims = tuple(ridges.dims)
+    lead = [d for d in dims if d not in ("latitude", "longitude")]
+    if len(lead) > 1 or len(dims) - len(lead) != 2:
+        raise ValueError("ridges: dims (latitude, longitude) and at most one more")
+    order = (*lead, "latitude", "longitude")
+    lat, lon = _coord(ridges, "latitude"), _coord(ridges, "longitude")
+    ilat, ilon = np.argsort(lat, kind="stable"), np.argsort(lon, kind="stable")
+    v = np.asarray(ridges.transpose(*order).values)
+    dtype = v.dtype
+    v = v if dtype in (np.float32, np.float64) else v.astype(np.float64)
+    v = np.ascontiguousarray(v[..., ilat, :][..., ilon])
+    eng = get_engine()
+    coords = {"latitude": lat[ilat], "longitude": lon[ilon]}
+    if lead:
+        coords[lead[0]] = _coord(ridges, lead[0])
+
+    def out(t):
+        return _make(ridges, _to_np(t).astype(dtype, copy=False), order, coords, getattr(ridges, "name", None)).transpose(*dims)
+    return eng, eng.to_device(v, v.dtype), out
+
+
+def skeletonize_ridges(ridges, method='guohall', cyclic=False, max_iterations=None, table=None, fill=0.0):
+    """Thin every ridge of a mask to a line one pixel wide, on the device (``Engine.thin``): the step
+    ``skeletonize(ridges.values)`` of LCS/area_of_influence.py:207, between ``find_ridges_spherical_hessian`` -- whose mask is
+    several pixels wide -- and ``filter_ridges``, whose ``major_axis_length`` is meant for the thinned line.
+
+    ``ridges`` is a labelled array over ``latitude`` and ``longitude`` (sorted ascending here, as ``filter_ridges`` sorts),
+    2-D, or 3-D with one more dimension (time, member): every plane is then thinned on its own, all of them in the same
+    kernel launches.  A pixel is part of a ridge when it is ``!= 0`` and not NaN; pixels outside the plane are background;
+    with ``cyclic`` the last longitude is the western neighbour of the first.
+
+    The rule is a parallel thinning in two sub-iterations, driven by a table of 256 codes indexed by the neighbourhood
+    ``NW + 2 N + 4 NE + 8 E + 16 SE + 32 S + 64 SW + 128 W`` (N is row r - 1 of the plane as it is sorted): bit 0 of a code
+    deletes the pixel in the first sub-iteration, bit 1 in the second; every sub-iteration reads the whole plane as the one
+    before left it; it ends when an iteration deletes nothing, or after ``max_iterations``.  ``method`` names a shipped table
+    (``Engine.thinning_table`` states both rules): ``'guohall'`` (Guo & Hall 1989, the default) kept the number of
+    8-connected components on every mask it was tried on and leaves one pixel of a 2 x 2 block; ``'zhang'`` (Zhang & Suen
+    1984) deletes a 2 x 2 block entirely and so can lose small ridges, which would then silently be missing from
+    ``filter_ridges`` too.  ``table`` takes the caller's own 256 codes instead.  scikit-image's own table is NOT reproduced
+    here: the package is not a dependency of this project and was not at hand to generate or check it against; a user who
+    has it can pass its table (recoded to the two bits above) and get its skeleton.
+
+    Returns the mask in the caller's class, dimension order and dtype: the input's value on the pixels that survive,
+    ``fill`` elsewhere."""
+    if table is None:
+        table = Engine.thinning_table(method)          # ValueError for a method that is not shipped
+    table = Engine.checked_thinning_table(table)
+    if max_iterations is not None and int(max_iterations) < 1:
+        raise ValueError(f"max_iterations {max_iterations!r}: >= 1, or None for no bound")
+    eng, mask, out = _ridge_planes(ridges)
+    keep = eng.thin(mask, table, cyclic=cyclic, max_iterations=max_iterations)
+    return out(eng.torch.where(keep != 0, mask, eng.torch.full_like(mask, float(fill))))
+
+
+def dilate_ridges(ridges, iterations=1, connectivity=1, cyclic=False, fill=0.0):
+    """Grow every ridge of a mask by one pixel per iteration, on the device (``Engine.dilate``): ``binary_dilation(
+    ridges.values)`` of LCS/area_of_influence.py:233.  A background pixel becomes part of a ridge when one of its four edge
+    neighbours (``connectivity=1``: the default of ``skimage.morphology.binary_dilation``, which the driver uses, and of
+    ``scipy.ndimage.binary_dilation``) or of its eight neighbours (``2``) is; ``iterations`` times.
+
+    ``ridges``, foreground, planes and ``cyclic`` as for ``skeletonize_ridges``.  Returns the mask in the caller's class,
+    dimension order and dtype: the input's value on the pixels that were ridge already, 1 on the added ones, ``fill``
+    elsewhere."""
+    if connectivity not in Engine.STRUCTURES:
+        raise ValueError(f"connectivity {connectivity!r}: 1 (edges) or 2 (edges and corners)")
+    if int(iterations) < 1:
+        raise ValueError(f"iterations {iterations!r}: >= 1")
+    eng, mask, out = _ridge_planes(ridges)
+    torch = eng.torch
+    grown = eng.dilate(mask, iterations=iterations, connectivity=connectivity, cyclic=cyclic)
+    was = (mask != 0) & ~torch.isnan(mask)
+    added = torch.where(grown != 0, torch.ones_like(mask), torch.full_like(mask, float(fill)))
+    return out(torch.where(was, mask, added))
