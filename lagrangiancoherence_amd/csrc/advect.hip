@@ -1499,6 +1499,8 @@ __device__ __forceinline__ void clamp_position_c(const AdvectArgs<float> &A, f2 
 // applying both clamps to the position it was handed; the level ends with one clamp of each kind (stores, next Euler
 // sample).  Same values as clamping after every update (the clamps are pure functions of the position), one v_cmp + one
 // s_or fewer per sample: 10 VALU and 10 SALU of the 260 / 134 per wave-level.  -DLCS_LDS2_DEFER_X=0 is the round-5 form.
+// Cyclic: "outside [0, n-1)" holds for x <= -180 and x >= 180 only on longitudes that start at -180 and span at most a full
+// circle; the launcher checks that per call and sends every other cyclic call to the direct-gather kernels (lds_tiles_for).
 #ifndef LCS_LDS2_DEFER_X
 #define LCS_LDS2_DEFER_X 1
 #endif
@@ -4359,6 +4361,23 @@ static AdvectArgs<T> fill_advect_args(const lc_ctx *ctx, const lc_advect_args &a
     return A;
 }
 
+// The float32 LDS-tile kernels wrap the longitude once per time level (DEFER_X) and leave a longitude the reference would
+// rewrite inside a level -- x <= -180 or x >= 180, trajectory.py:93-94,119-120, whatever the field's longitudes are -- to the
+// next sample's window test, which accepts window origins in [1, nx_f - 2].  That test catches every such longitude only
+// where the index of -180 is below 1 and the index of +180 is at least nx_f - 1, in the kernels' own arithmetic
+// ((x - lon_min) * sx in float32, monotone in x): on longitudes that start at -180 and span up to a full circle.  On a
+// field that has the +-180 meridian inside it (0 ... 360, ERA5's own convention) x = 190 has an index in the middle of
+// the window range while the reference samples at -170, about two cells away through scipy's wrap.  Such a cyclic call
+// takes the direct-gather kernels, which wrap after every update (clamp_position_f): the mode is 0 for the whole call.
+template <typename T>
+static int lds_tiles_for(const lc_ctx *ctx, const AdvectArgs<T> &A) {
+    if constexpr (sizeof(T) == 4) {
+        const bool deferred_wrap_exact = A.lon_min >= -180.0f && (180.0f - A.lon_min) * A.sx >= (float)(A.nx_f - 1);
+        if (A.cyclic && !deferred_wrap_exact) return 0;
+    }
+    return ctx->lds_tiles;
+}
+
 // Kernel choice (float + fused levels only; measured on MI355X, 4096^2 seeds, 96 steps, K=4, 8x8-seed waves):
 //   order 1: direct gather 10.9 ms (vector-L1 lookup bound), LDS tiles 10.2 ms (VALU-issue bound);
 //   order 3: direct gather 37.8 ms, LDS tiles 20.4 ms.
@@ -4367,11 +4386,10 @@ static AdvectArgs<T> fill_advect_args(const lc_ctx *ctx, const lc_advect_args &a
 // case costs the tile bookkeeping only.  An adaptive "skip the tile when most lanes miss" vote was
 // measured and dropped (it costs 5 % everywhere to save 8 % in that extreme).
 // lc_ctx_set_lds_tiles / LCS_LDS_TILES (read once at context creation) override (profiling).
-// Launches the fused kernel of a call on `grid` workgroups; returns its name.
+// Launches the fused kernel of a call on `grid` workgroups; returns its name.  `mode` is the call's lds_tiles_for().
 template <typename T>
-static const char *launch_fused(const lc_ctx *ctx, const AdvectArgs<T> &A, int grid) {
+static const char *launch_fused(const lc_ctx *ctx, const AdvectArgs<T> &A, int grid, int mode) {
     hipStream_t st = ctx->stream;
-    const int mode = ctx->lds_tiles;
     const bool fused64 = sizeof(T) == 8 && (A.ext != nullptr || A.ext_raw || A.ext_cub);  // single-sample iterations in float64
     const char *name = Lds64Launch<T>::launch_lin32(A, grid, st, mode);
     if (name) return name;
@@ -4424,8 +4442,9 @@ int advect_impl(lc_ctx *ctx, const lc_advect_args &a, const AdvectCall &call) {
         A.clamp_stride = per_member ? 1 : 0;
     }
     const int grid = lcplan::xcd_grid(A.ntiles, A.xcd_chunk) + A.pole_blocks;
-    const bool use_lds = ctx->lds_tiles != 0;
-    auto launch = [&](const AdvectArgs<T> &C) { return launch_fused(ctx, C, grid); };
+    const int lds_mode = lds_tiles_for(ctx, A);
+    const bool use_lds = lds_mode != 0;
+    auto launch = [&](const AdvectArgs<T> &C) { return launch_fused(ctx, C, grid, lds_mode); };
     const char *name = nullptr;
     // Level chunks (lc_ctx_set_level_chunk): the series runs as consecutive launches of at most `chunk` time levels,
     // each continuing from the positions the previous one left in x_out / y_out (a seed's start is read by the thread
@@ -4467,7 +4486,7 @@ int advect_impl(lc_ctx *ctx, const lc_advect_args &a, const AdvectCall &call) {
     const int n_launch = n_members / n_dir;  // members of one fused launch
     A.n_members = n_launch;  // (the kernel choice by size counts a launch's members: lc_advect_series's for the same windows)
     const bool pairs_ok = n_launch > 1 && order == 1 && !outer && !a.traj_x && use_lds &&
-                          (ctx->patch_mode < 0 || ctx->patch_mode == PATCH_PAIR) && K > 0 && order1_two_seed_applies(A, ctx->lds_tiles);
+                          (ctx->patch_mode < 0 || ctx->patch_mode == PATCH_PAIR) && K > 0 && order1_two_seed_applies(A, lds_mode);
     const lcplan::Groups G = lcplan::member_groups(n_launch, t0_stride, a.nsteps, pairs_ok);
     const int total = G.total;
     A.member_plane = (size_t)n_dir * plane_elems;
@@ -4525,7 +4544,7 @@ int advect_impl(lc_ctx *ctx, const lc_advect_args &a, const AdvectCall &call) {
     lcplan::Grading GR{};
     if constexpr (sizeof(T) == 4) {
         const bool tiles_have_poles = A.pole_blocks == 0 && (A.row0 < A.order || A.row0 + ny > A.ny_global - A.order);
-        if (order == 1 && use_lds && n_members == 1 && order1_two_seed_applies(A, ctx->lds_tiles)) {
+        if (order == 1 && use_lds && n_members == 1 && order1_two_seed_applies(A, lds_mode)) {
             AdvectArgs<float> P = A;
             int g2 = 0;
             const int mode = two_seed_patch_grid(P, P.patch_mode < PATCH_PAIR, g2);

@@ -109,13 +109,17 @@ def dilate(mask_bad, r=2):
     return out
 
 
-def positions_check(eng, field, slat, slon, rows, cols, xg, yg, o32, o64, label, floors, interp_order=1, **tele_kw):
+def positions_check(eng, field, slat, slon, rows, cols, xg, yg, o32, o64, label, floors, interp_order=1, leave_out=None,
+                    **tele_kw):
     """Engine departure points at seeds (rows x cols) inside the float32 oracle's band around the float64
     answer.  A seed the engine is off by > 0.5 degrees on (and the oracle is not) must be a verified Q7
-    teleport; those (and the oracle's own) are left out of the statistics.  Returns the keep mask."""
+    teleport; those (and the oracle's own) are left out of the statistics.  `leave_out`: a mask of seeds the
+    caller takes out beforehand (they count neither as teleports nor in the band).  Returns the keep mask."""
     (x32, y32), (x64, y64) = o32, o64
     eg = np.maximum(lon_err(xg, x64), np.abs(np.asarray(yg, dtype=np.float64) - y64))
     eo = np.maximum(lon_err(x32, x64), np.abs(np.asarray(y32, dtype=np.float64) - y64))
+    if leave_out is not None:
+        eg, eo = np.where(leave_out, 0.0, eg), np.where(leave_out, 0.0, eo)
     cand, keep = split_teleports(eg, eo)
     assert len(cand) <= 3, f"{label}: {len(cand)} seeds off by > 0.5 degrees"
     if cand:
@@ -124,5 +128,7 @@ def positions_check(eng, field, slat, slon, rows, cols, xg, yg, o32, o64, label,
         print(f"{label}: {len(cand)} Q7 teleport(s) at {seeds} verified {ok}")
         assert all(ok), f"{label}: large position error that is NOT a Q7 teleport"
     keep &= split_teleports(eo, eg)[1]
+    if leave_out is not None:
+        keep &= ~np.asarray(leave_out, dtype=bool)
     band(eg[keep], eo[keep], f"{label} positions", *floors)
     return keep

@@ -18,6 +18,8 @@ An advect-side entry is a dict:
   ``set_sigma_march``, ``set_f64_fidelity``); ``env``: variables read once at context creation;
 - ``sibling``: the direct-gather route of the same dtype, order, K and boundary whose bits this one must equal
   (DESIGN.md: every kernel family of one dtype is bit-identical to the others), or None;
+- ``name_on``: ``{grid: kernel name}`` for the longitude grids of ``GRIDS`` on which the dispatcher sends the route's
+  settings to another kernel than on ``m180`` (itself a route of this table); empty for most;
 - ``tol``: ``exact64`` (numpy / scipy operation order: <= 1e-12 degrees), ``fast64`` (fused-level form: <= 1e-10 degrees),
   ``band32`` (inside the float32 oracle's own band: median, p99 and max).
 
@@ -25,6 +27,12 @@ Shared inputs (``FLOW``, ``SEEDS``, ``T0``, ``NSTEPS``, ``TIMESTEPS``, ``LEVEL_C
 a 45 x 76 seed grid spanning the field (ragged against every tile shape, the global first and last rows included, so
 the pole-row rule runs), 10 steps from level 1 in level chunks of 4, both signs of the time step.  Parcels cross +-180
 in cyclic routes and leave the box in the others.
+
+Longitude grids (``GRIDS``): offsets added to the flow's longitudes, the wind arrays unchanged (the flow is periodic), the
+seeds spanning the shifted coordinates.  The reference wraps at a hard-coded +-180 whatever the field's longitudes are (Q7),
+so on ``e0`` and ``seam_inside`` the wrap happens in the field's interior and the next sample reaches scipy's ``wrap`` map
+with an index a period below zero; the non-cyclic routes see ``lon_min != -180`` in the index transform and the clamp
+bounds.  Every advect-side route runs on all three; on the two added grids at the smallest and largest of its ``Ks``.
 """
 
 FLOW = dict(nt=14, ny=36, nx=72, dt_seconds=3600.0, scale=1.0)   # flows.era5_like; u, v times `scale`
@@ -33,6 +41,9 @@ T0, NSTEPS = 1, 10
 TIMESTEPS = (-1800.0, 1800.0)
 LEVEL_CHUNK = 4             # 10 steps = three launches wherever a route takes chunks
 MEMBERS = 3                 # ensembles / series windows, t0 stride 1
+GRIDS = {"m180": 0.0,            # -180 ... 175: the flow's own longitudes
+         "e0": 180.0,            # 0 ... 355: ERA5's convention, the +-180 meridian on a node in the middle of the field
+         "seam_inside": 97.5}    # -82.5 ... 272.5: the meridian off any node, lon_min no multiple of the cell
 
 TOL = {"exact64": 1e-12, "fast64": 1e-10, "sigma64": 1e-7, "sigma64_nocast": 1e-9}
 
@@ -47,7 +58,7 @@ def _xmode(cyc):
 def _add(name, **kw):
     assert name not in ROUTES, name
     r = dict(call="advect", dtype="float32", order=1, Ks=(4,), xmode="cyclic", prepare={}, traj=False, members=1,
-             setters={}, env={}, sibling=None, tol="band32")
+             setters={}, env={}, sibling=None, tol="band32", name_on={})
     r.update(kw)
     r["name"] = name
     ROUTES[name] = r
@@ -108,6 +119,14 @@ for _k in (1, 2, 3):   # compiled for SETTLS_order 1, 2, 3 (cyclic only)
 # the run-time-K tall instances: cyclic takes only SETTLS orders above 4 (0..4 have their own instances)
 _add("advect_lds2_kernel<-1, true, 0>", Ks=(5, 6), setters={"set_lds_tiles": 1}, sibling=_DIRECT32[1])
 _add("advect_lds2_kernel<-1, false, 0>", Ks=(1, 2, 3), xmode="pointwise", setters={"set_lds_tiles": 1}, sibling=_DIRECT32[1])
+
+# The float32 LDS-tile kernels wrap the longitude once per time level and rely on the next sample's window test in between,
+# which holds only on longitudes that start at -180: a cyclic float32 call on a grid with the +-180
+# meridian inside takes the direct-gather kernel of its order, whatever lc_ctx_set_lds_tiles says.
+_DIRECT32_NAME = {1: "advect_kernel_f32<1>", 3: "advect_kernel_f32_wide<3>"}
+for _r in ROUTES.values():
+    if _r["xmode"] == "cyclic" and _r["name"].startswith(("advect_lds_kernel<", "advect_lds2_kernel<", "advect_lds2_o3_kernel<")):
+        _r["name_on"] = {_g: _DIRECT32_NAME[_r["order"]] for _g in ("e0", "seam_inside")}
 
 # ------------------------------------------------------------------ float64, direct gathers
 _add("advect_kernel<double, 1, false, 0>", dtype="float64", Ks=(0, 4), prepare={"fuse_levels": False, "lin_image": True},
@@ -195,6 +214,18 @@ _sig("sigma_batch_kernel_f32", call="batch", setters={"set_sigma_march": 0})
 _sig("sigma_march_batch_kernel_f32", call="batch", setters={"set_sigma_march": 1}, widths=(64, 1440))
 _sig("sigma_batch_kernel<double, float>", call="batch", dtype="float64")
 _sig("sigma_batch_kernel<double, double>", call="batch", dtype="float64", fd_fp32_cast=False)
+
+
+def grid_ks(route, grid):
+    """The SETTLS orders a route runs on a grid: all of them on ``m180``, the smallest and the largest on the others."""
+    ks = route["Ks"]
+    return tuple(ks) if grid == "m180" else tuple(sorted({min(ks), max(ks)}))
+
+
+def name_on(route, grid):
+    """The kernel name the dispatcher must report for a route's settings on a grid."""
+    return route["name_on"].get(grid, route["name"])
+
 
 # the knobs a route may name, and where each lives
 SETTERS = ("set_lds_tiles", "set_verify", "set_level_chunk", "set_sigma_march", "set_f64_fidelity")

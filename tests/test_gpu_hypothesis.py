@@ -124,6 +124,58 @@ def test_float32_kernels_agree_with_each_other_and_the_oracle(fny, fnx, nt, K, o
         assert np.median(dx) < 1e-4 and np.median(dy) < 1e-4
 
 
+@settings(max_examples=30, deadline=None, derandomize=True, suppress_health_check=[HealthCheck.too_slow, HealthCheck.data_too_large, HealthCheck.filter_too_much])
+@given(fny=st.integers(12, 60), fnx=st.integers(20, 120), nt=st.integers(2, 6), K=st.integers(0, 5),
+       order=st.sampled_from([1, 3]), dt=st.sampled_from([-3600.0, -900.0, 900.0, 5400.0]),
+       offset=st.sampled_from([0.0, 90.0, 180.0, 262.5]), sny=st.integers(7, 90), snx=st.integers(7, 130),
+       seed=st.integers(0, 2 ** 31 - 1), wind=st.sampled_from([0.5, 1.0, 3.0]))
+def test_float32_cyclic_kernels_on_longitudes_that_start_anywhere(fny, fnx, nt, K, order, dt, offset, sny, snx, seed, wind):
+    """float32, cyclic, the field's longitudes shifted by `offset` (the wind arrays unchanged: the flow is periodic): the
+    reference wraps at a hard-coded +-180 (Q7), which lies inside the field unless it starts at -180.  Whatever kernel a
+    lc_ctx_set_lds_tiles setting reaches there, the three settings must agree as on the flow's own longitudes (1 and 2 bit
+    for bit, 0 to float32 rounding) and sit at float32 distance from the float64 oracle.  Seeds whose float64 position
+    comes within 1e-2 degrees of +-180 at any update are left out (float32 and float64 may wrap them on different
+    iterations and then sample two cells apart); a draw that leaves out more than 2 % is discarded."""
+    from hypothesis import assume
+    from lagrangiancoherence_amd import flows
+    from tests import _seam as S
+    eng = _engine()
+    u, v, lat, lon = flows.era5_like(nt=nt, ny=fny, nx=fnx, seed=seed)
+    u, v = (u * np.float32(wind)), (v * np.float32(wind))
+    lon = (lon.astype(np.float64) + offset).astype(np.float32)
+    slat, slon = flows.seed_grid(sny, snx, lat, lon)
+    f64 = [a.astype(np.float64) for a in (u, v, lat, lon, slat, slon)]
+    tx, ty, seam = S.propagate(*f64, dt, K, order, 0, nt - 1)     # the float64 oracle, restated to see inside a level
+    xo, yo = tx[-1], ty[-1]
+    near = seam < S.NEAR_SEAM
+    assume(near.mean() <= 0.02)
+    f = eng.prepare_field(u, v, lat, lon, order)
+    out = {}
+    try:
+        for flag in (0, 1, 2):
+            eng.set_lds_tiles(flag)
+            x, y = eng.advect(f, slat, slon, dt, SETTLS_order=K, interp_order=order, cyclic_xboundary=True)
+            out[flag] = (x.cpu().numpy().astype(np.float64), y.cpu().numpy().astype(np.float64))
+    finally:
+        eng.set_lds_tiles(-1)
+
+    def dist(a, b):
+        d = np.abs(a - b)
+        return np.minimum(d, np.abs(d - 360))
+    assert np.isfinite(out[1][0]).all() and np.isfinite(out[1][1]).all()
+    # seeds that start exactly on the index map's jump at c = n - 1 are left out, as in the test above
+    cy0 = fny * (f64[4] - f64[2][0]) / (f64[2][-1] - f64[2][0])
+    cx0 = fnx * (f64[5] - f64[3][0]) / (f64[3][-1] - f64[3][0])
+    ok = (np.abs(cy0 - (fny - 1)) > 1e-3)[:, None] & (np.abs(cx0 - (fnx - 1)) > 1e-3)[None, :] & ~near
+    assert np.array_equal(out[1][0], out[2][0]) and np.array_equal(out[1][1], out[2][1])
+    dxk, dyk = dist(out[0][0], out[1][0])[ok], np.abs(out[0][1] - out[1][1])[ok]
+    assert np.percentile(dxk, 99) < 2e-4 and np.percentile(dyk, 99) < 2e-4 and dxk.max() < 0.1 and dyk.max() < 0.1
+    for flag in (0, 1):
+        dx, dy = dist(out[flag][0], xo)[ok], np.abs(out[flag][1] - yo)[ok]
+        assert np.percentile(dx, 99) < 2e-3 and np.percentile(dy, 99) < 2e-3, (flag, offset, dx.max(), dy.max())
+        assert np.median(dx) < 1e-4 and np.median(dy) < 1e-4, (flag, offset)
+
+
 @settings(max_examples=30 * _SCALE, deadline=None, derandomize=_DERAND, suppress_health_check=[HealthCheck.too_slow, HealthCheck.data_too_large])
 @given(dtype=st.sampled_from(["float32", "float64"]), order=st.sampled_from([1, 3]), K=st.integers(0, 4),
        lds=st.sampled_from([-1, 0, 1, 2]), sny=st.integers(9, 140), snx=st.integers(9, 150), nt=st.integers(4, 9),

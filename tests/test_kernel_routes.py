@@ -10,6 +10,7 @@ import re
 import shutil
 import subprocess
 
+import numpy as np
 import pytest
 
 from tests import kernel_routes as KR
@@ -139,6 +140,11 @@ def test_every_knob_a_route_names_exists():
         assert r["xmode"] in ("cyclic", "pointwise", "reference_outer"), name
         assert r["order"] in (1, 2, 3, 4, 5) and r["Ks"] and all(k >= 0 for k in r["Ks"]), name
         assert r["tol"] in ("exact64", "fast64", "band32", "tracer"), name
+        assert set(r["name_on"]) <= set(KR.GRIDS) - {"m180"}, name
+        for g, other in r["name_on"].items():       # a grid's own kernel is itself a route, of the same dtype and order
+            o = KR.ROUTES[other]
+            assert other != name and (o["dtype"], o["order"], o["xmode"]) == (r["dtype"], r["order"], r["xmode"]), (name, g)
+            assert not o["name_on"] and "lds" not in other, (name, g)
         if r["sibling"] is not None:
             s = KR.ROUTES[r["sibling"]]
             assert s["sibling"] is None and s["order"] == r["order"] and "lds" not in r["sibling"], name
@@ -154,3 +160,78 @@ def test_route_inputs_meet_the_edges():
     assert nx % 4 == 0 and nx >= 32            # whole-line stores stay possible (PATCH_LINES, lines instances)
     assert KR.NSTEPS > 2 * KR.LEVEL_CHUNK      # at least three level chunks
     assert min(KR.TIMESTEPS) < 0 < max(KR.TIMESTEPS)
+
+
+def test_grids_and_their_settls_orders():
+    assert list(KR.GRIDS) == ["m180", "e0", "seam_inside"] and KR.GRIDS["m180"] == 0.0
+    assert KR.GRIDS["e0"] == 180.0 and KR.GRIDS["seam_inside"] == 97.5
+    cell = 360.0 / KR.FLOW["nx"]
+    assert (KR.GRIDS["seam_inside"] / cell) % 1 == 0.5         # +-180 half way between two nodes, lon_min off the cell grid
+    for name, r in KR.ROUTES.items():
+        if name.startswith("sigma"):
+            continue
+        assert KR.grid_ks(r, "m180") == tuple(r["Ks"]), name
+        for g in ("e0", "seam_inside"):
+            assert KR.grid_ks(r, g) == tuple(sorted({min(r["Ks"]), max(r["Ks"])})), name
+        assert KR.name_on(r, "m180") == name
+    # the float32 LDS-tile kernels defer the longitude wrap inside a level: every cyclic route of theirs is re-routed
+    lds32 = [n for n, r in KR.ROUTES.items() if n.startswith(("advect_lds_kernel<", "advect_lds2_")) and r["xmode"] == "cyclic"]
+    assert lds32 and all(set(KR.ROUTES[n]["name_on"]) == {"e0", "seam_inside"} for n in lds32)
+    assert all(not r.get("name_on") for n, r in KR.ROUTES.items() if n not in lds32)
+
+
+SEAM_CASES = [(g, o, dt) for g in ("e0", "seam_inside") for o in (1, 3) for dt in KR.TIMESTEPS]
+
+
+@pytest.mark.parametrize("grid,order,dt", SEAM_CASES)
+def test_added_grids_put_the_wrap_inside_the_field(grid, order, dt):
+    """Oracle-only conditions of the added longitude grids (K = 4): parcels cross +-180 in numbers, the float64 oracle is
+    well conditioned there, few seeds come near the seam, the float32 oracle stays close to the float64 one."""
+    from oracle import lcs_oracle as O
+    from tests import _seam as S
+    K = 4
+    u, v, lat, lon, slat, slon = S.inputs("float64", grid)
+    assert lon[0] == -180.0 + KR.GRIDS[grid] and lon[0] < 180.0 < lon[-1]
+    kw = dict(timestep=dt, SETTLS_order=K, interp_order=order, cyclic_xboundary=True, return_traj=True, t0=KR.T0, nsteps=KR.NSTEPS)
+    x64, y64 = O.parcel_propagation(u, v, lat, lon, seed_lat=slat, seed_lon=slon, **kw)
+    # the restatement the near-seam distances come from IS the oracle
+    tx, ty, seam = S.restated("float64", order, K, dt, KR.T0, grid)
+    assert np.array_equal(tx, x64) and np.array_equal(ty, y64)
+    n = x64[0].size
+    share = S.crossed(x64).sum() / n
+    assert share >= 0.20, f"{share:.1%} of the seeds cross +-180"
+    # conditioning: the seeds shifted by 1e-12 degrees
+    xs, ys = O.parcel_propagation(u, v, lat, lon, seed_lat=slat + 1e-12, seed_lon=slon + 1e-12, **kw)
+    moved = max(np.minimum(np.abs(xs[-1] - x64[-1]), np.abs(np.abs(xs[-1] - x64[-1]) - 360.0)).max(), np.abs(ys[-1] - y64[-1]).max())
+    assert moved <= 1e-11, f"the float64 oracle moves by {moved:.2e} degrees"
+    # the near-seam seeds a float32 comparison leaves out (float32 inputs, float64 arithmetic): at most 1 %
+    for k in (0, K):
+        left_out = int(S.near_seam("float32", order, k, dt, KR.T0, grid).sum())
+        assert left_out <= n // 100, f"K={k}: {left_out} seeds within {S.NEAR_SEAM} degrees of +-180"
+    # the float32 oracle against the float64 answer on the float32 inputs
+    a32 = S.inputs("float32", grid)
+    a64 = tuple(q.astype(np.float64) for q in a32)
+    r32 = O.parcel_propagation(*a32[:4], seed_lat=a32[4], seed_lon=a32[5], **kw)
+    r64 = O.parcel_propagation(*a64[:4], seed_lat=a64[4], seed_lon=a64[5], **kw)
+    dx = np.abs(r32[0][-1].astype(np.float64) - r64[0][-1])
+    err = np.maximum(np.minimum(dx, np.abs(dx - 360.0)), np.abs(r32[1][-1].astype(np.float64) - r64[1][-1]))
+    assert (err > 0.1).sum() <= 1 and (err > 0.5).sum() == 0, (int((err > 0.1).sum()), float(err.max()))
+
+
+@pytest.mark.parametrize("order", (1, 3))
+@pytest.mark.parametrize("K", (1, 4))
+def test_the_added_grids_can_tell_a_deferred_wrap(order, K):
+    """The mutant (tests/_seam.py: the in-level wrap left to the next sample's window test) equals the oracle bit for bit
+    on the flow's own longitudes and differs by more than 1e-3 degrees on at least 20 % of the seeds of either added grid:
+    the existing assertions separate the two once the inputs do."""
+    from tests import _seam as S
+    from tests._fullsize import lon_err
+    for dt in KR.TIMESTEPS:
+        tx, ty, _ = S.restated("float64", order, K, dt, KR.T0, "m180")
+        mx, my, _ = S.restated("float64", order, K, dt, KR.T0, "m180", defer=True)
+        assert np.array_equal(tx, mx) and np.array_equal(ty, my), (order, K, dt)
+        for grid in ("e0", "seam_inside"):
+            tx, ty, _ = S.restated("float64", order, K, dt, KR.T0, grid)
+            mx, my, _ = S.restated("float64", order, K, dt, KR.T0, grid, defer=True)
+            off = np.maximum(lon_err(mx[-1], tx[-1]), np.abs(my[-1] - ty[-1])) > 1e-3
+            assert off.mean() >= 0.20, f"{grid} order {order} K={K} dt={dt:+.0f}: the mutant differs on {off.mean():.1%} of the seeds"

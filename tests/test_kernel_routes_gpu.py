@@ -4,15 +4,20 @@ float64 CPU oracle (oracle/lcs_oracle.py) and, where the table names one, with i
 Inputs (kernel_routes.FLOW ...): a smooth global flow (flows.era5_like at 5 degrees), a 45 x 76 seed grid (ragged
 against every tile shape, global first and last rows included), 10 steps in level chunks of 4, both signs of the
 time step; parcels cross +-180 (cyclic) or leave the box (pointwise / outer clamp).  On this flow the oracle itself
-moves by <= 6e-12 degrees when the seeds shift by 1e-12 degrees, so the float64 bounds below measure the kernels."""
+moves by <= 6e-12 degrees when the seeds shift by 1e-12 degrees, so the float64 bounds below measure the kernels.
+
+Every route runs on the three longitude grids of kernel_routes.GRIDS: the flow's own (-180 ... 175, test ids as before the
+grids were added) and two with the +-180 meridian inside the field (``name@e0``, ``name@seam_inside``), where the reference's
+hard-coded wrap (Q7) happens in the field's interior.  There the float32 band leaves out the seeds whose float64 oracle
+position comes within 1e-2 degrees of +-180 at any update (tests/_seam.py; at most 1 % of them)."""
 import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
-from lagrangiancoherence_amd import flows
 from oracle import lcs_oracle as O
+from tests import _seam as S
 from tests import kernel_routes as KR
 from tests._fullsize import band, lon_err, positions_check
 
@@ -65,30 +70,14 @@ def _np(t):
     return t.detach().cpu().numpy()
 
 
-@functools.lru_cache(maxsize=None)
-def _flow64():
-    f = KR.FLOW
-    u, v, lat, lon = flows.era5_like(nt=f["nt"], ny=f["ny"], nx=f["nx"], dtype=np.float64, dt_seconds=f["dt_seconds"])
-    return u * f["scale"], v * f["scale"], lat, lon
+_flow64 = S.flow64
+_inputs = S.inputs           # (kind, grid="m180")
 
 
 @functools.lru_cache(maxsize=None)
-def _inputs(kind):
-    """(u, v, lat, lon, seed_lat, seed_lon) as the engine gets them, and as the oracle gets them for the float64 answer."""
-    u, v, lat, lon = _flow64()
-    f32 = np.float32
-    if kind == "float32":
-        u, v, lat, lon = (a.astype(f32) for a in (u, v, lat, lon))
-    elif kind == "f64_wind_f32":
-        u, v = u.astype(f32), v.astype(f32)
-    slat, slon = flows.seed_grid(*KR.SEEDS, lat, lon)
-    return u, v, lat, lon, slat, slon
-
-
-@functools.lru_cache(maxsize=None)
-def _oracle(kind, order, K, dt, xmode, t0, arith):
+def _oracle(kind, order, K, dt, xmode, t0, arith, grid="m180"):
     """Oracle trajectories (nsteps + 1, ny, nx) on the route's inputs in `arith` arithmetic."""
-    u, v, lat, lon, slat, slon = _inputs(kind)
+    u, v, lat, lon, slat, slon = _inputs(kind, grid)
     if arith == "float64" and kind == "float32":
         u, v, lat, lon, slat, slon = (a.astype(np.float64) for a in (u, v, lat, lon, slat, slon))
     kw = dict(timestep=dt, SETTLS_order=K, interp_order=order, cyclic_xboundary=xmode == "cyclic", return_traj=True,
@@ -99,10 +88,10 @@ def _oracle(kind, order, K, dt, xmode, t0, arith):
 _FIELDS = {}
 
 
-def _field(eng, r):
-    key = (id(eng), r["dtype"], r["order"], tuple(sorted(r["prepare"].items())))
+def _field(eng, r, grid="m180"):
+    key = (id(eng), r["dtype"], r["order"], tuple(sorted(r["prepare"].items())), grid)
     if key not in _FIELDS:
-        u, v, lat, lon, _, _ = _inputs(r["dtype"])
+        u, v, lat, lon, _, _ = _inputs(r["dtype"], grid)
         _FIELDS[key] = eng.prepare_field(u, v, lat, lon, r["order"], **r["prepare"])
     return _FIELDS[key]
 
@@ -111,9 +100,9 @@ def _xkw(xmode):
     return dict(cyclic_xboundary=xmode == "cyclic", noncyclic_clamp=None if xmode == "cyclic" else xmode)
 
 
-def _run(eng, r, field, K, dt):
+def _run(eng, r, field, K, dt, grid="m180"):
     """The route's call.  Returns (name, [(t0, x, y, traj_x or None, traj_y or None) per member])."""
-    _, _, _, _, slat, slon = _inputs(r["dtype"])
+    _, _, _, _, slat, slon = _inputs(r["dtype"], grid)
     order, call, M = r["order"], r["call"], r["members"]
     if call == "advect":
         res = eng.advect(field, slat, slon, dt, K, order, t0=KR.T0, nsteps=KR.NSTEPS, return_traj=r["traj"], **_xkw(r["xmode"]))
@@ -141,10 +130,10 @@ def _run(eng, r, field, K, dt):
     return eng.last_advect_kernel(), out
 
 
-def _compare(eng, r, field, K, dt, t0, x, y, tx, ty, label):
+def _compare(eng, r, field, K, dt, t0, x, y, tx, ty, label, grid="m180"):
     kind, order, xmode = r["dtype"], r["order"], r["xmode"]
     xg, yg = _np(x).astype(np.float64), _np(y).astype(np.float64)
-    o64 = _oracle(kind, order, K, dt, xmode, t0, "float64")
+    o64 = _oracle(kind, order, K, dt, xmode, t0, "float64", grid)
     if r["tol"] in ("exact64", "fast64"):
         tol = KR.TOL[r["tol"]]
         ex, ey = lon_err(xg, o64[0][-1]).max(), np.abs(yg - o64[1][-1]).max()
@@ -153,12 +142,18 @@ def _compare(eng, r, field, K, dt, t0, x, y, tx, ty, label):
             et = max(lon_err(_np(tx), o64[0]).max(), np.abs(_np(ty) - o64[1]).max())
             assert et <= tol, f"{label}: trajectories off by {et:.2e} degrees"
         return
-    o32 = _oracle(kind, order, K, dt, xmode, t0, "float32")
-    _, _, _, _, slat, slon = _inputs(kind)
+    o32 = _oracle(kind, order, K, dt, xmode, t0, "float32", grid)
+    _, _, _, _, slat, slon = _inputs(kind, grid)
     ny, nx = KR.SEEDS
+    leave_out = None
+    if grid != "m180" and xmode == "cyclic":
+        # float32 and float64 can wrap a parcel that comes this close to +-180 on different iterations, and then sample two
+        # cells apart: left out of the statistics, at most 1 % of the seeds
+        leave_out = S.near_seam(kind, order, K, dt, t0, grid)
+        assert leave_out.sum() <= leave_out.size // 100, f"{label}: {leave_out.sum()} seeds near +-180"
     keep = positions_check(eng, field, slat, slon, np.arange(ny), np.arange(nx), xg, yg, (o32[0][-1], o32[1][-1]),
-                           (o64[0][-1], o64[1][-1]), label, FLOORS32, interp_order=order, K=K, timestep=dt, t0=t0,
-                           nsteps=KR.NSTEPS)
+                           (o64[0][-1], o64[1][-1]), label, FLOORS32, interp_order=order, leave_out=leave_out, K=K,
+                           timestep=dt, t0=t0, nsteps=KR.NSTEPS)
     if tx is not None:
         txg, tyg = _np(tx).astype(np.float64), _np(ty).astype(np.float64)
         eg = np.maximum(lon_err(txg, o64[0]), np.abs(tyg - o64[1]))[:, keep]
@@ -177,27 +172,34 @@ def eng_equal(p, q):
     return torch.equal(p, q)
 
 
-@pytest.mark.parametrize("name", [n for n in ADVECT if KR.ROUTES[n]["call"] != "tracer"])
-def test_advect_route_vs_oracle(monkeypatch, name):
+def _cases(names):
+    """(route, grid) per test case: the ``m180`` cases first under the route's bare name, then ``name@grid``."""
+    return [pytest.param((n, g), id=n if g == "m180" else f"{n}@{g}") for g in KR.GRIDS for n in names]
+
+
+@pytest.mark.parametrize("case", _cases([n for n in ADVECT if KR.ROUTES[n]["call"] != "tracer"]))
+def test_advect_route_vs_oracle(monkeypatch, case):
+    name, grid = case
     r = KR.ROUTES[name]
+    want = KR.name_on(r, grid)
     eng = _engine(monkeypatch, r["env"])
-    field = _field(eng, r)
-    for K in r["Ks"]:
+    field = _field(eng, r, grid)
+    for K in KR.grid_ks(r, grid):
         for dt in KR.TIMESTEPS:
-            label = f"{name} K={K} dt={dt:+.0f}"
+            label = f"{name} K={K} dt={dt:+.0f}" + ("" if grid == "m180" else f" {grid}")
             with _Setters(eng, dict(r["setters"], set_level_chunk=KR.LEVEL_CHUNK)):
-                got, out = _run(eng, r, field, K, dt)
+                got, out = _run(eng, r, field, K, dt, grid)
                 if "set_verify" in r["setters"]:
                     audit = eng.read_verify()
                     assert audit["tile_changed"] == 0 and audit["entries_changed"] == 0, (label, audit)
-            assert got == name, f"{label}: dispatched {got}"
+            assert got == want, f"{label}: dispatched {got}"
             if r["call"] == "advect" and r["xmode"] != "reference_outer":
                 assert eng.last_advect_launches() >= 3, f"{label}: {eng.last_advect_launches()} launches, not level chunks"
             for m, (t0, x, y, tx, ty) in enumerate(out):
-                _compare(eng, r, field, K, dt, t0, x, y, tx, ty, f"{label} member {m}" if len(out) > 1 else label)
+                _compare(eng, r, field, K, dt, t0, x, y, tx, ty, f"{label} member {m}" if len(out) > 1 else label, grid)
             if r["sibling"]:
                 with _Setters(eng, dict(r["setters"], set_lds_tiles=0, set_level_chunk=KR.LEVEL_CHUNK)):
-                    sib, out2 = _run(eng, r, field, K, dt)
+                    sib, out2 = _run(eng, r, field, K, dt, grid)
                 assert sib == r["sibling"], f"{label}: sibling dispatched {sib}"
                 for (_, *a), (_, *b) in zip(out, out2):
                     assert _same_bits(a, b), f"{label}: differs from {sib} bit for bit"
@@ -219,26 +221,27 @@ def _oracle_levels(c, lat, lon, tx, ty, t0, order):
     return np.stack([O.xr_map_coordinates(c[t0 + i], lat, lon, tx[i], ty[i], order=order) for i in range(tx.shape[0])])
 
 
-@pytest.mark.parametrize("name", [n for n in ADVECT if KR.ROUTES[n]["call"] == "tracer"])
-def test_tracer_route_vs_oracle(monkeypatch, name):
+@pytest.mark.parametrize("case", _cases([n for n in ADVECT if KR.ROUTES[n]["call"] == "tracer"]))
+def test_tracer_route_vs_oracle(monkeypatch, case):
+    name, grid = case
     r = KR.ROUTES[name]
     eng = _engine(monkeypatch, r["env"])
     kind, order = r["dtype"], r["order"]
-    u, v, lat, lon, slat, slon = _inputs(kind)
+    u, v, lat, lon, slat, slon = _inputs(kind, grid)
     c64 = np.hypot(_flow64()[0], _flow64()[1]) + 20.0 * np.cos(np.deg2rad(_flow64()[2]))[None, :, None]
-    field = _field(eng, r)
+    field = _field(eng, r, grid)
     tr = eng.prepare_tracer(c64.astype(field.dtype), None, lat, lon, order, dtype=field.dtype)
     crange = float(c64.max() - c64.min())
-    for K in r["Ks"]:
+    for K in KR.grid_ks(r, grid):
         for dt in KR.TIMESTEPS:
-            label = f"{name} K={K} dt={dt:+.0f}"
+            label = f"{name} K={K} dt={dt:+.0f}" + ("" if grid == "m180" else f" {grid}")
             with _Setters(eng, {"set_level_chunk": KR.LEVEL_CHUNK}):
                 res = eng.advect_tracer(field, tr, slat, slon, dt, K, order, True, t0=KR.T0, nsteps=KR.NSTEPS,
                                         return_traj=True, tracer_traj=True)
             assert eng.last_tracer_kernel() == name, f"{label}: {eng.last_tracer_kernel()}"
             cg, mean = _np(res["c"]).astype(np.float64), _np(res["mean"]).astype(np.float64)
             if kind == "float64":
-                tx, ty = _oracle(kind, order, K, dt, "cyclic", KR.T0, "float64")
+                tx, ty = _oracle(kind, order, K, dt, "cyclic", KR.T0, "float64", grid)
                 want = _oracle_levels(c64, lat, lon, tx, ty, KR.T0, order)
                 tol = 1e-10 * crange
                 assert np.abs(cg - want).max() <= tol, (label, np.abs(cg - want).max())
