@@ -1878,6 +1878,9 @@ __device__ unsigned long long g_stamps[8];
 __device__ unsigned long long g_cause[4];  // seed-samples outside the tile in x, in y, of those below (x < lo), (y < lo)
 __device__ unsigned long long g_redo[3][3][3];  // [latitude band 0-30 / 30-60 / 60-90][third of the levels][samples, with redo, seeds redone]
 __device__ unsigned long long g_hist[2][5];     // wave-levels by the number of their K = 4 iterations with a redo: [0] all, [1] those whose PREVIOUS level had >= 3
+// redo iterations by where their out-of-tile seeds sit: [0] the lanes' first seeds only, [1] second seeds only, [2] both, in
+// disjoint lanes, [3] both, some lane with both; [4] out-of-tile seed-samples, [5] of those, the ones whose common-path tap serves
+__device__ unsigned long long g_class[6];
 #define LCS_STAMP(i)                                           \
     {                                                          \
         const long long _t = __builtin_amdgcn_s_memtime();     \
@@ -1941,6 +1944,17 @@ constexpr int SLAB_PITCH = 36;  // floats per slab row (32 + 4: rows stay 16-byt
 #ifndef LCS_LDS2_DIRECT_LEVELS
 #define LCS_LDS2_DIRECT_LEVELS 0
 #endif
+// THE OUT-OF-TILE PATH of an iteration (tall patches and PATCH_LINES; DEFER_X).  A sample whose window leaves the wave's tile is
+// almost always still inside the grid, and the exact sequence then recomputes what the common path has: with the common-path
+// window origin in [1, n - 2] on both axes the position is strictly inside both clamps (they are identities), index_coords()
+// does not wrap, and its coordinate is to_index()'s bit for bit -- the very conditions under which the common path serves a
+// sample from the tile.  LCS_LDS2_REUSE_TAP: such a sample keeps the common path's tap and goes straight to the gather (12 of
+// the sequence's 27 instructions less); origin 0 (Q7's x > -180, Q8's NaN) and everything outside take the whole sequence.
+// C3: 90.8 % of the out-of-tile seed-samples; advect 5.67-5.69 -> 5.57-5.60 ms (profiles/out_of_tile/).  0: the whole sequence
+// for every out-of-tile sample.
+#ifndef LCS_LDS2_REUSE_TAP
+#define LCS_LDS2_REUSE_TAP 1
+#endif
 template <int KFIX, bool CYCLIC, int MODE>
 __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgpu_num_sgpr(LCS_LDS2_NUM_SGPR)))
     advect_lds2_kernel(const AdvectArgs<float> A0) {
@@ -1951,6 +1965,7 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
     constexpr int ORDER = 1;
     constexpr bool DEFER_X = LCS_LDS2_DEFER_X != 0;
     constexpr int DIRECT_LEVELS = DEFER_X ? LCS_LDS2_DIRECT_LEVELS : 0;
+    constexpr bool REUSE_TAP = LCS_LDS2_REUSE_TAP != 0 && DEFER_X && (MODE == PATCH_TALL || LINES);  // (see THE OUT-OF-TILE PATH)
     // (a DPP row is 16 lanes: the neighbouring lane holds the next nodes of the same tile row only when tile rows do not straddle DPP rows)
     constexpr bool DPP_NEXT = LCS_LDS2_DPP_NEXT != 0 && 16 % Lds2Geom::LANES_PER_ROW == 0;
     const int K = KFIX >= 0 ? KFIX : A.K;
@@ -2080,6 +2095,9 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
     auto to_index = [&](f2 v) { return (v - pmin) * sc; };  // subtract first: exact 0 at the grid origin
     const float xlo = A.x_min, xhi = A.x_max;
     auto x_needs_care = [&](float x) { return CYCLIC ? !(fabsf(x) < 180.0f) : !((x > xlo) & (x < xhi)); };
+    // a window origin in [1, n - 2] on both axes: one unsigned compare each (a field these kernels take has more than two nodes
+    // on either axis: order1_two_seed_applies)
+    auto origin_inside = [&](const TapL &t) { return ((unsigned)(t.x0 - 1) < (unsigned)(A.nx_f - 2)) & ((unsigned)(t.y0 - 1) < (unsigned)(A.ny_f - 2)); };
     const float *lvl = A.img + (size_t)t0 * A.level_elems;
     const float *elv = A.ext + (size_t)t0 * A.level_elems;
     const int pad_cols = A.pitch, pad_rows = A.ny_f + LC_PAD;
@@ -2253,10 +2271,12 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             anybad = false;
+            TapL tq[NS];  // the common path's taps (REUSE_TAP: the out-of-tile path reads them)
 #pragma unroll
             for (int q = 0; q < NS; ++q) {
                 typedef __attribute__((address_space(3))) const f4 lds_f4;
                 const TapL t = tap_of(to_index(p[q]));
+                tq[q] = t;
                 const int rx = t.x0 - lo_x, ry = t.y0 - lo_y;
                 bad[q] = ((unsigned)rx > (unsigned)lim_x) | ((unsigned)ry > (unsigned)lim_y);
 #ifdef LCS_STAMPS
@@ -2294,24 +2314,34 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
                     atomicAdd(&g_redo[band][third][0], 1ull);
                     atomicAdd(&g_redo[band][third][1], (m0 | m1) ? 1ull : 0ull);
                     atomicAdd(&g_redo[band][third][2], (unsigned long long)(__popcll(m0) + __popcll(m1)));
+                    if (m0 | m1) atomicAdd(&g_class[m0 == 0 ? 1 : m1 == 0 ? 0 : (m0 & m1) ? 3 : 2], 1ull);
+                }
+                const unsigned long long h0 = __ballot(bad[0] && origin_inside(tq[0])), h1 = __ballot(bad[1] && origin_inside(tq[1]));
+                if (lane == 0 && (m0 | m1)) {
+                    atomicAdd(&g_class[4], (unsigned long long)(__popcll(m0) + __popcll(m1)));
+                    atomicAdd(&g_class[5], (unsigned long long)(__popcll(h0) + __popcll(h1)));
                 }
             }
 #endif
             if (DIRECT_LEVELS > 0) redos += __ballot(anybad) != 0ull;
+            // the out-of-tile sample of one seed: the exact sequence and a global gather -- or, for a window origin inside the
+            // grid, the gather alone at the common path's tap (see THE OUT-OF-TILE PATH)
+            auto exact_sample = [&](f2 pc, TapL t, f2 eq, f2 hq) {
+                if (!REUSE_TAP || !origin_inside(t)) {
+                    if (DEFER_X)
+                        clamp_position_c<CYCLIC>(A, pc, ymax_v);  // the deferred clamps of the previous update (Q7 / Q8 / Q9)
+                    else
+                        pc.y = __builtin_amdgcn_fmed3f(pc.y, A.y_min, ymax_v);  // the deferred clamp (Q8)
+                    t = tap_of(index_coords(A, pc));
+                }
+                f2 r = hq * window_global<ORDER>(elv, A, t, eq) + pc;
+                if (!DEFER_X) clamp_position_p(A, r, ymax_v);
+                return r;
+            };
             if (anybad) {
 #pragma unroll
-                for (int q = 0; q < NS; ++q) {
-                    if (bad[q]) {  // exact sequence, global gather
-                        f2 pc = p[q];
-                        if (DEFER_X)
-                            clamp_position_c<CYCLIC>(A, pc, ymax_v);  // the deferred clamps of the previous update (Q7 / Q8 / Q9)
-                        else
-                            pc.y = __builtin_amdgcn_fmed3f(pc.y, A.y_min, ymax_v);  // the deferred clamp (Q8)
-                        const TapL t = tap_of(index_coords(A, pc));
-                        pn[q] = hd[q] * window_global<ORDER>(elv, A, t, e[q]) + pc;
-                        if (!DEFER_X) clamp_position_p(A, pn[q], ymax_v);
-                    }
-                }
+                for (int q = 0; q < NS; ++q)
+                    if (bad[q]) pn[q] = exact_sample(p[q], tq[q], e[q], hd[q]);
             }
 #pragma unroll
             for (int q = 0; q < NS; ++q) p[q] = pn[q];
@@ -4854,6 +4884,14 @@ extern "C" int lc_debug_read_hist(unsigned long long *out10, int reset) {
     if (reset) {
         unsigned long long z[10] = {};
         if (hipMemcpyToSymbol(HIP_SYMBOL(g_hist), z, sizeof(z)) != hipSuccess) return -1;
+    }
+    return 0;
+}
+extern "C" int lc_debug_read_class(unsigned long long *out6, int reset) {
+    if (hipMemcpyFromSymbol(out6, HIP_SYMBOL(g_class), sizeof(g_class)) != hipSuccess) return -1;
+    if (reset) {
+        unsigned long long z[6] = {};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_class), z, sizeof(z)) != hipSuccess) return -1;
     }
     return 0;
 }

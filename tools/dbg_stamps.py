@@ -43,3 +43,10 @@ if hasattr(lib, "lc_debug_read_hist") and lib.lc_debug_read_hist(hist, 1) == 0:
     h = np.array(list(hist), dtype=np.float64).reshape(2, 5)
     print("wave-levels by the number of their 4 iterations with a redo (0..4):", np.round(100 * h[0] / max(h[0].sum(), 1), 1), "%")
     print("... of the wave-levels whose previous level had >= 3 (%.1f %% of all):" % (100 * h[1].sum() / max(h[0].sum(), 1)), np.round(100 * h[1] / max(h[1].sum(), 1), 1), "%")
+
+cls = (C.c_ulonglong * 6)()
+if hasattr(lib, "lc_debug_read_class") and lib.lc_debug_read_class(cls, 1) == 0:
+    c = np.array(list(cls), dtype=np.float64)
+    print("redo iterations by where their out-of-tile seeds sit (first seeds only / second seeds only / both, disjoint lanes / both, "
+          "some lane with both):", np.round(100 * c[:4] / max(c[:4].sum(), 1), 1), "%")
+    print(f"out-of-tile seed-samples served at the common path's tap (window origin in [1, n - 2] on both axes): {100 * c[5] / max(c[4], 1):.2f} %")
