@@ -602,6 +602,50 @@ int lc_ridge_classify(lc_ctx *ctx, const void *hxx, const void *hxy, const void 
                       const void *gx, const void *gy, size_t n, double tolerance,
                       void *mask_out, void *eigmin_out, void *dt_out, void *eigvec_out);
 
+/* ---- ridges of a stack of planes (find_ridges_spherical_hessian on a series) -----------
+ * tools.find_ridges_spherical_hessian (LCS/tools.py:52-155) from the smoothing on, for n_members independent planes
+ * [n_members][ny*nx] of float64 (latitude and longitude ascending, tools.py:70-71) in two kernels instead of about thirty
+ * launches per plane.  Both entry points and the getter were added at LC_VERSION 104 without a bump: nothing that existed
+ * changed.  A plane never reads another plane; plane m of every output equals what lc_gaussian_filter,
+ * lc_fourth_order_derivative and lc_ridge_classify give for plane m alone, bit for bit.
+ *   tools.py:74-75    sigma > 0: scipy.ndimage.gaussian_filter per plane (truncate 4, reflect; never across planes: the
+ *                     reference's call on a 3-D array would smooth across time and then fail at its reshape, :87-90).
+ *                     sigma <= 0 or NaN: no smoothing, work_dev is not read.  A radius int(4 sigma + 0.5) above 256 is
+ *                     refused with LC_EUNSUPPORTED, as lc_gaussian_filter refuses it.
+ *   tools.py:77-78    ddadx, ddady = derivative_spherical_coords(da, 1 / 0): the float32 cast (:258), the 5-point index stencil
+ *                     (:202-244: one-sided / 2 on the two first and last rows; in longitude cyclic when isglobal != 0, else
+ *                     one-sided / 2 on the two first and last columns), widened to float64 and divided by dx_dev[row]
+ *                     (:255, :264) or multiplied by 1 / dy rounded once (:256, :262: what the per-plane route's division by
+ *                     the scalar dy does on the device).  grad_out [n_members][2][ny*nx]: these two, float64.
+ *   tools.py:79-81    d2dadx2, d2dady2, d2dadxdy the same way from the float32 casts of ddadx, ddady.
+ *   tools.py:87-93    the Hessian per point, inf / NaN entries zeroed.
+ *   tools.py:99-118   numpy.linalg.eig of it, the row-indexed eigenvector (:107), its product with the gradient (:115) and
+ *                     the eigenvalue of largest magnitude (:118), as lc_ridge_classify: dt_out [n_members][ny*nx] the raw
+ *                     product, eigmin_out that eigenvalue, eigvec_out [n_members][2][ny*nx] the vector, unmasked.
+ *   tools.py:123-133  the angle and the eigmin < 0 masking of the vector are left to the caller (two element-wise expressions).
+ *   tools.py:136-138  mask_out: 1 where |product| <= tolerance (or the product is NaN) and that eigenvalue is negative, else 0.
+ * Every output may be NULL.  work_dev: float64 [lc_ridges_work_elems(ny, nx, n_members)] scratch (0 elements for bad sizes).
+ * A null context, a wrong struct_size, ny < 5 or nx < 5 (lc_fourth_order_derivative's limit), a plane of 2^31 points or
+ * more, a radius above 256, and any overlap between f / dx_dev, work_dev and the outputs are refused before any HIP call.
+ * lc_ctx_last_ridges_kernel: what the context's last lc_ridges_batch launched, "gauss_planes_kernel+hessian_ridge_kernel"
+ * or "hessian_ridge_kernel" ("" before the first).  No kernel of this call waits for another workgroup. */
+size_t lc_ridges_work_elems(int ny, int nx, int n_members);
+typedef struct lc_ridges_args {
+    size_t struct_size; /* sizeof(lc_ridges_args): checked before any other field */
+    const void *f;      /* float64 [n_members][ny*nx] */
+    int ny, nx, n_members;
+    const void *dx_dev; /* float64 [ny]: metres per longitude step of every row (tools.py:255) */
+    double dy;          /* metres per latitude step (tools.py:256) */
+    double sigma;       /* <= 0 or NaN: no smoothing */
+    double tolerance;
+    int isglobal;
+    void *work_dev;
+    void *mask_out, *eigmin_out, *dt_out; /* float64 [n_members][ny*nx], or NULL */
+    void *eigvec_out, *grad_out;          /* float64 [n_members][2][ny*nx], or NULL */
+} lc_ridges_args;
+int lc_ridges_batch(lc_ctx *ctx, const lc_ridges_args *args);
+const char *lc_ctx_last_ridges_kernel(const lc_ctx *ctx);
+
 /* ---- connected components of a ridge mask (filter_ridges) ----------------------------
  * What the driver does with the raw mask before it uses it (LCS/area_of_influence.py:210-242): label its connected
  * components, measure each, keep those that pass a threshold.  The function the driver imports for it comes from a package

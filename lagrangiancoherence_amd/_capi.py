@@ -184,6 +184,25 @@ class MorphArgs(C.Structure):
 PROTOTYPES["lc_morph_work_elems"] = (_sz, [_i, _i, _i])
 PROTOTYPES["lc_mask_morphology"] = (_i, [_vp, C.POINTER(MorphArgs)])
 
+
+
+class RidgesArgs(C.Structure):
+    """``lc_ridges_args`` of include/lcs_hip.h, field for field."""
+    _fields_ = [("struct_size", _sz),
+                ("f", _vp),
+                ("ny", _i), ("nx", _i), ("n_members", _i),
+                ("dx_dev", _vp),
+                ("dy", _d), ("sigma", _d), ("tolerance", _d),
+                ("isglobal", _i),
+                ("work_dev", _vp),
+                ("mask_out", _vp), ("eigmin_out", _vp), ("dt_out", _vp),
+                ("eigvec_out", _vp), ("grad_out", _vp)]
+
+
+PROTOTYPES["lc_ridges_work_elems"] = (_sz, [_i, _i, _i])
+PROTOTYPES["lc_ridges_batch"] = (_i, [_vp, C.POINTER(RidgesArgs)])
+PROTOTYPES["lc_ctx_last_ridges_kernel"] = (C.c_char_p, [_vp])
+
 _lib = None
 
 

@@ -6,6 +6,7 @@
 #include <cstring>
 #include <vector>
 
+#include "gauss_taps.h"
 #include "hostxfer.h"
 #include "lcs_common.h"
 
@@ -92,6 +93,7 @@ extern "C" int lc_ctx_create(int device, lc_ctx **out) {
     c->last_pack_kernel = "";
     c->last_tracer_kernel = "";
     c->last_strain_kernel = "";
+    c->last_ridges_kernel = "";
     c->verify_dev = nullptr;
     c->trunc = nullptr;
     c->xfer = nullptr;
@@ -362,39 +364,15 @@ extern "C" int lc_field_extrapolate(lc_ctx *ctx, const void *packed_dev, int dty
 namespace {
 
 constexpr int GAUSS_MAX_RADIUS = 256;
+static_assert(GAUSS_MAX_RADIUS == GAUSS_W_CAPACITY, "a GaussW holds every radius lc_gaussian_filter accepts");
 
-struct GaussW {
-    double w[GAUSS_MAX_RADIUS + 1];  // w[0] centre ... w[radius]
-    int radius;
-};
-
-__device__ __forceinline__ int reflect_index(int i, int n) {
-    // scipy 'reflect' (d c b a | a b c d | d c b a), any distance
-    if (n == 1) return 0;
-    const int period = 2 * n;
-    i %= period;
-    if (i < 0) i += period;
-    return i < n ? i : period - 1 - i;
-}
-
+// GaussW, reflect_index and the tap loop: gauss_taps.h (shared with ridges_batch.hip's gauss_planes_kernel)
 template <typename T, int AXIS>
 __global__ void gauss_kernel(const T *__restrict__ in, T *__restrict__ out, int ny, int nx, const GaussW G) {
     const size_t total = (size_t)ny * nx;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int y = (int)(i / nx), x = (int)(i - (size_t)y * nx);
-        double acc = (double)in[i] * G.w[0];
-        for (int j = G.radius; j >= 1; --j) {  // outermost pair first, as correlate1d does
-            double lo, hi;
-            if (AXIS == 0) {
-                lo = (double)in[(size_t)reflect_index(y - j, ny) * nx + x];
-                hi = (double)in[(size_t)reflect_index(y + j, ny) * nx + x];
-            } else {
-                lo = (double)in[(size_t)y * nx + reflect_index(x - j, nx)];
-                hi = (double)in[(size_t)y * nx + reflect_index(x + j, nx)];
-            }
-            acc += (lo + hi) * G.w[j];
-        }
-        out[i] = (T)acc;
+        out[i] = (T)gauss_taps<T, AXIS>(in, y, x, ny, nx, G);
     }
 }
 
@@ -423,12 +401,7 @@ extern "C" int lc_gaussian_filter(lc_ctx *ctx, const void *in_dev, int dtype, in
         lc_set_error("lc_gaussian_filter: sigma %g needs radius %d > %d", sigma, G.radius, GAUSS_MAX_RADIUS);
         return LC_EUNSUPPORTED;
     }
-    // scipy _gaussian_kernel1d: phi = exp(-0.5/sigma^2 * x^2); phi /= phi.sum()
-    double sum = 0.0;
-    std::vector<double> phi(2 * G.radius + 1);
-    for (int k = -G.radius; k <= G.radius; ++k) phi[k + G.radius] = std::exp(-0.5 / (sigma * sigma) * (double)k * k);
-    for (double p : phi) sum += p;
-    for (int k = 0; k <= G.radius; ++k) G.w[k] = phi[k + G.radius] / sum;
+    gauss_fill_weights(G, sigma);  // scipy _gaussian_kernel1d (gauss_taps.h)
     LC_HIP_CHECK(hipSetDevice(ctx->device));
     if (dtype == LC_F32) return gauss_impl<float>(ctx, (const float *)in_dev, ny, nx, G, (float *)tmp_dev, (float *)out_dev);
     return gauss_impl<double>(ctx, (const double *)in_dev, ny, nx, G, (double *)tmp_dev, (double *)out_dev);

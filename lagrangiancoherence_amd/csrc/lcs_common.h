@@ -50,6 +50,7 @@ struct lc_ctx {
     // (0: the by-size chunk), dispatch positions at a launch's end that are cut short, levels the last one loses (-1: the
     // built-in defaults; depth 0: off).  Only with level_chunk = -1: an explicit level chunk is uniform chunks.
     int grade_chunk, grade_zone, grade_depth;
+    const char *last_ridges_kernel;  // what the last lc_ridges_batch launched (lc_ctx_last_ridges_kernel)
 #ifdef LCS_TIMELINE  // diagnostic build only: start / end stamps of the two-seed order-1 kernel's workgroups (lc_debug_read_timeline)
     unsigned long long *timeline_dev;
     size_t timeline_cap;  // records allocated

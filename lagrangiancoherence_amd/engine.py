@@ -918,8 +918,69 @@ class Engine:
                                                self._ptr(vec) if return_eigvec else None), self.lib)
         return (mask, eigmin, dt, vec) if return_eigvec else (mask, eigmin, dt)
 
+    _RIDGE_PLANES = ("mask", "eigmin", "dt", "eigvec", "grad")
+
+    @staticmethod
+    def ridge_metric(lat, lon):
+        """``(dx, dy)`` of tools.derivative_spherical_coords (LCS/tools.py:254-256) for ascending coordinates in degrees: metres
+        per longitude step of every row (an array, in the coordinates' dtype as numpy evaluates it) and per latitude step."""
+        y = lat * np.pi / 180                                                   # tools.py:254
+        dx = (np.pi / 180) * (lon[1] - lon[0]) * 6371000 * np.cos(y)            # tools.py:255
+        dy = (np.pi / 180) * (lat[1] - lat[0]) * 6371000                        # tools.py:256
+        return dx, float(dy)
+
+    def last_ridges_kernel(self) -> str:
+        """Names of the kernels the last :meth:`ridges_batch` call launched (``lc_ctx_last_ridges_kernel``), joined by ``+``."""
+        return self.lib.lc_ctx_last_ridges_kernel(self.ctx).decode()
+
+    def ridges_batch(self, f, lat, lon, sigma=.5, tolerance=0.0005e-3, isglobal=True, want=("mask", "eigmin")) -> dict:
+        """tools.find_ridges_spherical_hessian (LCS/tools.py:52-155) for a stack of planes in one call (``lc_ridges_batch``:
+        two Gaussian launches and one fused Hessian / classification launch for all of them).  ``f``: ``(ny, nx)`` or
+        ``(n, ny, nx)``, an array or a device tensor (used where it lies: nothing goes to the host), ``lat`` / ``lon`` its
+        ascending coordinates in degrees (tools.py:70-71 sorts before it gets here).  ``sigma``: the Gaussian's width in grid
+        steps, applied to every plane on its own; ``None`` or ``<= 0``: no smoothing.  ``isglobal``: cyclic longitude stencil.
+
+        Returns a dict of float64 device tensors for the names in ``want``: ``mask`` (1 on a ridge, else 0), ``eigmin`` (the
+        Hessian eigenvalue of largest magnitude) and ``dt`` (the raw eigenvector / gradient product) shaped like ``f``;
+        ``eigvec`` (the row-indexed eigenvector, unmasked) and ``grad`` (``ddadx, ddady``) with a dimension of 2 in front of
+        ``(ny, nx)``.  Plane ``m`` of each equals the per-plane chain (:meth:`gaussian_filter`, :meth:`index_derivative`,
+        :meth:`ridge_classify`) on plane ``m`` bit for bit."""
+        want = tuple(want)
+        bad = [w for w in want if w not in self._RIDGE_PLANES]
+        if bad or not want:
+            raise ValueError(f"want {want!r}: a non-empty subset of {self._RIDGE_PLANES}")
+        torch = self.torch
+        fd = self.to_device(f, np.float64)
+        if fd.dim() not in (2, 3) or fd.numel() == 0:
+            raise ValueError("f: a plane (ny, nx) or a stack of planes (n, ny, nx), none of them empty")
+        shape = tuple(int(s) for s in fd.shape)
+        ny, nx = shape[-2:]
+        n = shape[0] if len(shape) == 3 else 1
+        lat, lon = np.asarray(lat), np.asarray(lon)
+        if lat.shape != (ny,) or lon.shape != (nx,):
+            raise ValueError("lat / lon: one latitude per row and one longitude per column of f")
+        dx, dy = self.ridge_metric(lat, lon)
+        dx = self.to_device(dx, np.float64)
+        smooth = sigma is not None and float(sigma) > 0
+        out = {}
+        for k in want:
+            out[k] = self._empty((*shape[:-2], 2, ny, nx) if k in ("eigvec", "grad") else shape, np.float64)
+        a = _capi.RidgesArgs(struct_size=C.sizeof(_capi.RidgesArgs))
+        a.f, a.ny, a.nx, a.n_members = fd.data_ptr(), ny, nx, n
+        a.dx_dev, a.dy, a.sigma, a.tolerance = dx.data_ptr(), dy, float(sigma) if smooth else 0.0, float(tolerance)
+        a.isglobal = int(bool(isglobal))
+        work = None
+        if smooth:
+            work = torch.empty((max(1, int(self.lib.lc_ridges_work_elems(ny, nx, n))),), dtype=torch.float64, device=self.device)
+            a.work_dev = work.data_ptr()
+        for k in self._RIDGE_PLANES:
+            setattr(a, k + "_out", out[k].data_ptr() if k in out else None)
+        self._use_current_stream()
+        _capi.check(self.lib.lc_ridges_batch(self.ctx, C.byref(a)), self.lib)
+        return out
+
     # ------------------------------------------------------------------ connected components of a mask (filter_ridges)
-    COMPONENT_PROPS = ("area", "mean_intensity", "max_intensity", "min_intensity", "major_axis_length", "minor_axis_length")
+    COMPONENT_PROPS =("area", "mean_intensity", "max_intensity", "min_intensity", "major_axis_length", "minor_axis_length")
 
     def _planes(self, a, dtype=None):
         """``a`` (2-D, or 3-D with a leading member dimension) on the device as ``(n_members, ny, nx)``; ``dtype`` None: its own

@@ -73,6 +73,33 @@ def derivative_spherical_coords(da, dim=0, isglobal=True):
     return _make(da, deriv, ("latitude", "longitude"), {"latitude": lat, "longitude": lon}, getattr(da, "name", None))
 
 
+def _hessian_ridges_plane(eng, a, lat, lon, sigma, tolerance_threshold, isglobal):
+    """The device side of the 2-D ``find_ridges_spherical_hessian``: ``a`` a float64 ``(latitude, longitude)`` device tensor,
+    ``lat`` / ``lon`` ascending.  Returns the device tensors ``(mask, eigmin, dt, vec, ddadx, ddady)``."""
+    torch = eng.torch
+    if isinstance(sigma, (float, int)) and sigma > 1e-15:                              # tools.py:74-75
+        a = eng.gaussian_filter(a, sigma)
+    y = lat * np.pi / 180
+    dx = eng.to_device((np.pi / 180) * (lon[1] - lon[0]) * 6371000 * np.cos(y), np.float64)[:, None]   # tools.py:255
+    dy = (np.pi / 180) * (lat[1] - lat[0]) * 6371000                                   # tools.py:256
+
+    def D(f, dim):   # derivative_spherical_coords: float32 cast, index stencil, metric (tools.py:258-264)
+        d = eng.index_derivative(f.to(torch.float32), dim, isglobal).to(torch.float64)   # isglobal: tools.py:77-81
+        return d / dy if dim == 0 else d / dx
+    ddadx, ddady = D(a, 1), D(a, 0)                                                    # tools.py:77-78
+    d2x2, d2y2, dxdy = D(ddadx, 1), D(ddady, 0), D(ddadx, 0)                           # tools.py:79-81
+    mask, eigmin, dt, vec = eng.ridge_classify(d2x2, dxdy, d2y2, ddadx, ddady, tolerance_threshold,
+                                               return_eigvec=True)
+    return mask, eigmin, dt, vec, ddadx, ddady
+
+
+def _angle_and_masked(torch, vec, eigmin):
+    """``angle`` (tools.py:125, of the unmasked vector) and the vector zeroed where ``eigmin >= 0`` (tools.py:133); the
+    component axis of ``vec`` is the third from the end, in front of ``(latitude, longitude)``."""
+    angle = (180 / np.pi) * torch.atan(vec.select(-3, 0) / vec.select(-3, 1))
+    return angle, torch.where((eigmin < 0).unsqueeze(-3), vec, torch.zeros_like(vec))
+
+
 def find_ridges_spherical_hessian(da, sigma=.5, scheme='first_order', tolerance_threshold=0.0005e-3,
                                   return_eigvectors=False, isglobal=True):
     """Hessian ridge filter in spherical coordinates.  Signature of LCS/tools.py:52-54.
@@ -90,44 +117,54 @@ def find_ridges_spherical_hessian(da, sigma=.5, scheme='first_order', tolerance_
     Hessian planes, tools.py:123-124) and is zeroed where ``eigmin >= 0`` (tools.py:133); ``gradient`` has a
     leading ``elements`` dimension ``['ddadx', 'ddady']``; ``angle`` is ``180/pi * arctan(e0/e1)`` of the
     unmasked vector (tools.py:125).
+
+    An input with more dimensions than ``latitude`` and ``longitude`` (the ``(time, latitude, longitude)`` record of
+    ``LCS.series``, ``LCS.bidirectional`` or ``LCS.strain``) is a stack of independent planes: every plane is smoothed and
+    differenced on its own -- never across time -- and equals the 2-D call on that plane bit for bit, all of them in the same
+    three kernel launches (``Engine.ridges_batch``).  That is this function's definition, not the reference's: its
+    ``gaussian_filter(da)`` would smooth a 3-D array across time and then fail at its reshape (tools.py:87-90).  The results
+    have the input's dimension order and coordinates, the ``eigvectors`` / ``elements`` dimension leading as above.
     """
     dims = tuple(da.dims)
+    lead = tuple(d for d in dims if d not in ("latitude", "longitude"))
     lat, lon = _coord(da, "latitude"), _coord(da, "longitude")
     ilat, ilon = np.argsort(lat, kind="stable"), np.argsort(lon, kind="stable")       # tools.py:70-71
-    vals = np.asarray(da.transpose("latitude", "longitude").values, dtype=np.float64)[ilat][:, ilon]
-    lat, lon = lat[ilat], lon[ilon]
     eng = get_engine()
     torch = eng.torch
-    a = eng.to_device(vals, np.float64)
-    if isinstance(sigma, (float, int)) and sigma > 1e-15:                              # tools.py:74-75
-        a = eng.gaussian_filter(a, sigma)
-    y = lat * np.pi / 180
-    dx = eng.to_device((np.pi / 180) * (lon[1] - lon[0]) * 6371000 * np.cos(y), np.float64)[:, None]   # tools.py:255
-    dy = (np.pi / 180) * (lat[1] - lat[0]) * 6371000                                   # tools.py:256
+    name = getattr(da, "name", None)
+    if not lead:
+        vals = np.asarray(da.transpose("latitude", "longitude").values, dtype=np.float64)[ilat][:, ilon]
+        lat, lon = lat[ilat], lon[ilon]
+        mask, eigmin, dt, vec, ddadx, ddady = _hessian_ridges_plane(eng, eng.to_device(vals, np.float64), lat, lon, sigma,
+                                                                    tolerance_threshold, isglobal)
+        grad = torch.stack([ddadx, ddady]) if return_eigvectors else None
+        order, coords = ("latitude", "longitude"), {"latitude": lat, "longitude": lon}
+        plain = lambda t: t
+        labelled = lambda t: t
+    else:
+        order = (*lead, "latitude", "longitude")
+        vals = np.asarray(da.transpose(*order).values, dtype=np.float64)[..., ilat, :][..., ilon]
+        lat, lon = lat[ilat], lon[ilon]
+        lead_shape, (ny, nx) = vals.shape[:-2], vals.shape[-2:]
+        smooth = isinstance(sigma, (float, int)) and sigma > 1e-15                     # tools.py:74-75
+        want = ("mask", "eigmin", "dt", "eigvec", "grad") if return_eigvectors else ("mask", "eigmin")
+        res = eng.ridges_batch(np.ascontiguousarray(vals.reshape((-1, ny, nx))), lat, lon, sigma=sigma if smooth else None,
+                               tolerance=tolerance_threshold, isglobal=isglobal, want=want)
+        mask, eigmin, dt, vec, grad = (res.get(k) for k in ("mask", "eigmin", "dt", "eigvec", "grad"))
+        coords = {"latitude": lat, "longitude": lon, **{d: _coord(da, d) for d in lead}}
+        plain = lambda t: t.reshape(*lead_shape, ny, nx)                               # (n, ny, nx) -> the lead dimensions
+        labelled = lambda t: t.movedim(-3, 0).reshape(2, *lead_shape, ny, nx)          # (n, 2, ny, nx) -> 2 in front
 
-    def D(f, dim):   # derivative_spherical_coords: float32 cast, index stencil, metric (tools.py:258-264)
-        d = eng.index_derivative(f.to(torch.float32), dim, isglobal).to(torch.float64)   # isglobal: tools.py:77-81
-        return d / dy if dim == 0 else d / dx
-    ddadx, ddady = D(a, 1), D(a, 0)                                                    # tools.py:77-78
-    d2x2, d2y2, dxdy = D(ddadx, 1), D(ddady, 0), D(ddadx, 0)                           # tools.py:79-81
-    mask, eigmin, dt, vec = eng.ridge_classify(d2x2, dxdy, d2y2, ddadx, ddady, tolerance_threshold,
-                                               return_eigvec=True)
-
-    def out(t, lead=None, labels=None):
-        arr = _to_np(t)
-        coords = {"latitude": lat, "longitude": lon}
-        if lead is None:
-            o = _make(da, arr, ("latitude", "longitude"), coords, getattr(da, "name", None))
-            return o.transpose(*dims)                                                  # tools.py:150
-        coords[lead] = np.asarray(labels)
-        o = _make(da, arr, (lead, "latitude", "longitude"), coords, getattr(da, "name", None))
-        return o.transpose(lead, *dims)                                                # tools.py:141-147
+    def out(t, first=None, labels=None):
+        if first is None:
+            return _make(da, _to_np(plain(t)), order, dict(coords), name).transpose(*dims)       # tools.py:150
+        o = _make(da, _to_np(labelled(t)), (first, *order), {**coords, first: np.asarray(labels)}, name)
+        return o.transpose(first, *dims)                                               # tools.py:141-147
     if not return_eigvectors:
         return out(mask), out(eigmin)
-    angle = (180 / np.pi) * torch.atan(vec[0] / vec[1])                                # tools.py:125
-    vec_masked = torch.where((eigmin < 0)[None], vec, torch.zeros_like(vec))           # tools.py:133
+    angle, vec_masked = _angle_and_masked(torch, vec, eigmin)
     return (out(mask), out(eigmin), out(dt), out(vec_masked, "eigvectors", ["d2dadxdy", "d2dadydx"]),
-            out(torch.stack([ddadx, ddady]), "elements", ["ddadx", "ddady"]), out(angle))
+            out(grad, "elements", ["ddadx", "ddady"]), out(angle))
 
 
 def filter_ridges(ridges, ftle, criteria, thresholds, verbose=True, connectivity=2, cyclic=False, fill=0.0):
