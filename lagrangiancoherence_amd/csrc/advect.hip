@@ -915,13 +915,11 @@ __global__ void __launch_bounds__(BLOCK) advect_lds64w_kernel(const AdvectArgs<d
 // tiles (levels t and t + 1, one anchor on the middle of the level's travel) serve the Euler sample and both samples of every
 // iteration; scipy's weights (cubic_weights), tap order (tap_sum_order3) and numpy's index map (locate<double, 3>), so the
 // result is advect_seed<double, 3, true> with A.wind_f32 bit for bit.  A window outside the tiles reads global memory.
-#ifndef LCS_LDS64W_O3_MINWAVES
-#define LCS_LDS64W_O3_MINWAVES 2   // 200 vector registers, no spills (a 4 x 4 window of float64 nodes is 64 of them): config 2's shape 15.8 ms;
-                                   // 3 waves (168 registers, 34 spilled) 17.4; 4 waves (128, 138 spilled) not run
-#endif
+constexpr int LDS64W_O3_MINWAVES = 2;  // 200 vector registers, no spills (a 4 x 4 window of float64 nodes is 64 of them): config 2's shape 15.8 ms;
+                                       // 3 waves (168 registers, 34 spilled) 17.4; 4 waves (128, 138 spilled) not run
 constexpr int TW3 = 16, TW3_PITCH = 20;
 template <int KFIX, bool CYCLIC>
-__global__ void __launch_bounds__(BLOCK, LCS_LDS64W_O3_MINWAVES) advect_lds64w_o3_kernel(const AdvectArgs<double> A0) {
+__global__ void __launch_bounds__(BLOCK, LDS64W_O3_MINWAVES) advect_lds64w_o3_kernel(const AdvectArgs<double> A0) {
 #pragma clang fp contract(off)
     typedef double T;
     const AdvectArgs<double> A = for_member(A0);
@@ -1247,20 +1245,13 @@ __device__ void advect_seed_f32(const AdvectArgs<float> &A, int iy, int ix) {
 // ======================================================================================
 // Tile geometry per interpolation order (nodes).  Measured on C3 with 8x8-seed waves (ms):
 //   order 1: 16x4 11.9, 16x8 10.2, 16x16 10.2, 32x8 10.6     order 3: 16x8 22.7, 16x16 21.2, 32x8 24.3, 32x16 20.4
+constexpr int O3_COLS = 32, O3_ROWS = 16;
+constexpr int O3_PITCH = O3_COLS + 4;  // 36 nodes: the 4 x 4 window reads of neighbouring rows fall into different banks (two-seed kernel on C3: 15.45 against 15.6-15.9 ms with 34)
 template <int ORDER>
 struct TileGeom {
-#ifndef LCS_O3_COLS
-#define LCS_O3_COLS 32
-#endif
-#ifndef LCS_O3_ROWS
-#define LCS_O3_ROWS 16
-#endif
-    static constexpr int COLS = ORDER == 3 ? LCS_O3_COLS : 16;   // one row = COLS/2 lanes x 16 B
-    static constexpr int ROWS = ORDER == 3 ? LCS_O3_ROWS : 8;
-#ifndef LCS_O3_PITCH
-#define LCS_O3_PITCH (LCS_O3_COLS + 4)  // 36 nodes: the 4 x 4 window reads of neighbouring rows fall into different banks (two-seed kernel on C3: 15.45 against 15.6-15.9 ms with 34)
-#endif
-    static constexpr int PITCH = ORDER == 3 ? LCS_O3_PITCH : COLS + 2;  // rows stay 16-byte aligned
+    static constexpr int COLS = ORDER == 3 ? O3_COLS : 16;   // one row = COLS/2 lanes x 16 B
+    static constexpr int ROWS = ORDER == 3 ? O3_ROWS : 8;
+    static constexpr int PITCH = ORDER == 3 ? O3_PITCH : COLS + 2;  // rows stay 16-byte aligned
     static constexpr int LANES_PER_ROW = COLS / 2;
     static constexpr int ROWS_PER_PASS = 64 / LANES_PER_ROW;
 };
@@ -1269,16 +1260,11 @@ struct TileGeom {
 // (~27 vector-L1 tag lookups each: 13 of the kernel's 20 ms of TCP time on C3, next to 13.5 ms of VALU work),
 // while a small tile of img[t] around the patch's CURRENT position is one coalesced 16-byte load per lane.
 // (Order 1 gathers 2 x 16 B per lane; there the tile was measured slower, 8.2 vs 7.6 ms.)
-#ifndef LCS_E_ROWS
-#define LCS_E_ROWS 8
-#endif
-#ifndef LCS_E_PITCH
-#define LCS_E_PITCH 18
-#endif
+constexpr int E_ROWS = 8, E_PITCH = 18;
 template <int ORDER>
 struct EulerGeom {
     static constexpr bool ON = ORDER == 3;
-    static constexpr int COLS = 16, ROWS = LCS_E_ROWS, PITCH = LCS_E_PITCH;
+    static constexpr int COLS = 16, ROWS = E_ROWS, PITCH = E_PITCH;
     static constexpr int LANES_PER_ROW = COLS / 2, ROWS_PER_PASS = 64 / LANES_PER_ROW, NPASS = ROWS / ROWS_PER_PASS;
     static constexpr int ELEMS = ON ? ROWS * PITCH : 0;
 };
@@ -1459,24 +1445,8 @@ __device__ __forceinline__ f2 euler_global(const float *__restrict__ lvl, const 
 
 // trajectory.py:89-94 on a packed position: latitude clamp in one v_med3_f32 (a NaN input makes med3
 // return min3 = y_min, which is Q8's rule; ``ymax_v`` lives in a VGPR because a VOP3 takes one SGPR);
-// the cyclic wrap is the exact reference sequence in a rare branch.
-__device__ __forceinline__ void clamp_position_p(const AdvectArgs<float> &A, f2 &p, float ymax_v) {
-    p.y = __builtin_amdgcn_fmed3f(p.y, A.y_min, ymax_v);
-    if (A.cyclic) {
-        if (!(fabsf(p.x) < 180.0f)) {  // rare (Q7)
-            float x = p.x;
-            if (!(x > -180.0f)) x = pymod180<float>(x);
-            if (!(x < 180.0f)) x = -180.0f + pymod180<float>(x);
-            p.x = x;
-        }
-    } else if (p.x < A.x_min || p.x > A.x_max) {  // NaN stays NaN, as in the reference
-        if (A.clamp_flag) *A.clamp_flag = 1u;
-        p.x = p.x < A.x_min ? A.x_min : A.x_max;
-    }
-}
-
-// ... with the boundary kind known at compile time (the kernels are instantiated per kind: no uniform branch on A.cyclic,
-// one v_cmp + one exec-masked rare block per call)
+// the cyclic wrap is the exact reference sequence in a rare branch.  The boundary kind is known at compile time (the
+// kernels are instantiated per kind: no uniform branch on A.cyclic, one v_cmp + one exec-masked rare block per call).
 template <bool CYCLIC>
 __device__ __forceinline__ void clamp_position_c(const AdvectArgs<float> &A, f2 &p, float ymax_v) {
     p.y = __builtin_amdgcn_fmed3f(p.y, A.y_min, ymax_v);
@@ -1498,12 +1468,10 @@ __device__ __forceinline__ void clamp_position_c(const AdvectArgs<float> &A, f2 
 // to an index outside [0, n-1), which the NEXT sample's window test flags by itself, and the exact-redo path starts by
 // applying both clamps to the position it was handed; the level ends with one clamp of each kind (stores, next Euler
 // sample).  Same values as clamping after every update (the clamps are pure functions of the position), one v_cmp + one
-// s_or fewer per sample: 10 VALU and 10 SALU of the 260 / 134 per wave-level.  -DLCS_LDS2_DEFER_X=0 is the round-5 form.
+// s_or fewer per sample: 10 VALU and 10 SALU of the 260 / 134 per wave-level.  The only form: the round-5 one (a wrap / clamp
+// after every update) is in tools/experiments/advect_r06_compile_time_forks.patch.
 // Cyclic: "outside [0, n-1)" holds for x <= -180 and x >= 180 only on longitudes that start at -180 and span at most a full
 // circle; the launcher checks that per call and sends every other cyclic call to the direct-gather kernels (lds_tiles_for).
-#ifndef LCS_LDS2_DEFER_X
-#define LCS_LDS2_DEFER_X 1
-#endif
 // Control flow: rocprof shows the VALU (~80 % of issue slots) and the CU's scalar pipe (SALU + branches,
 // ~75 %) saturating together, so the loop is written with ONE rare branch per sample instead of one per
 // special case.  Every lane first runs the common case unconditionally -- coordinate already in
@@ -1513,31 +1481,12 @@ __device__ __forceinline__ void clamp_position_c(const AdvectArgs<float> &A, f2 
 // case never faults on garbage: LDS reads cannot fault (out-of-range DS reads return 0) and the global
 // gather clamps its indices.  Lanes without a seed (grid edge, pole rows) shadow a neighbouring seed so
 // that they follow the same path; only their stores are masked.
-#ifndef LCS_O3_MINWAVES
-#define LCS_O3_MINWAVES 1
-#endif
-#ifndef LCS_LDS_NUM_SGPR
-#define LCS_LDS_NUM_SGPR 0
-#endif
+constexpr int O3_MINWAVES = 1;
 enum Patch { PATCH_TALL = 0, PATCH_WIDE = 1, PATCH_LINES = 2, PATCH_PAIR = 3 };
 // The whole-line trajectory store.  Measured on C3 with return_traj (advect ms, profiles/r03): plain 9.24-9.35, nontemporal
 // (`nt`: the written lines do not push the wind tiles out of the XCD's L2) 8.27-8.29, write-through sc1 9.16-9.29,
-// sc0 sc1 9.25-9.36.  -DLCS_TRAJ_STORE_KIND=0 plain, 1 nt (default), 2 sc1, 3 sc0 sc1.
-#ifndef LCS_TRAJ_STORE_KIND
-#define LCS_TRAJ_STORE_KIND 1
-#endif
-__device__ __forceinline__ void traj_store_line(float *dst, f4 v) {
-#if LCS_TRAJ_STORE_KIND == 1
-    __builtin_nontemporal_store(v, (f4 *)dst);
-#elif LCS_TRAJ_STORE_KIND == 2
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(dst), "v"(v) : "memory");  // (s_nop: the >8-byte store-data hazard the compiler cannot see inside asm)
-#elif LCS_TRAJ_STORE_KIND == 3
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" : : "v"(dst), "v"(v) : "memory");
-#else
-    *(f4 *)dst = v;
-#endif
-}
-#define LCS_TRAJ_STORE(dst, v) traj_store_line(dst, v)
+// sc0 sc1 9.25-9.36.  The nontemporal one is kept; the other three are in tools/experiments/advect_r06_compile_time_forks.patch.
+__device__ __forceinline__ void traj_store_line(float *dst, f4 v) { __builtin_nontemporal_store(v, (f4 *)dst); }
 
 // LINES (with return_traj on grids whose rows are 16-byte aligned): the four waves of a workgroup sit side by side in
 // longitude (32 x 8 seeds) instead of stacked (8 x 32), put their positions into an LDS slab after each time level, meet at
@@ -1552,18 +1501,13 @@ __device__ __forceinline__ void traj_store_line(float *dst, f4 v) {
 // [4..11] first event: block, tile, wave, level, HW_ID before / after, lane mask lo / hi, [12] first-event latch, [15] 0xBAD: inject one (test hook)
 static_assert(LC_VERIFY_WORDS >= 16, "lc_ctx_read_verify's counter block");
 template <int ORDER, int KFIX, bool CYCLIC, bool LINES, bool VERIFY = false>
-__global__ void __launch_bounds__(BLOCK, ORDER == 3 ? LCS_O3_MINWAVES : 1)
-#if LCS_LDS_NUM_SGPR > 0
-    __attribute__((amdgpu_num_sgpr(LCS_LDS_NUM_SGPR)))
-#endif
+__global__ void __launch_bounds__(BLOCK, ORDER == 3 ? O3_MINWAVES : 1)
     advect_lds_kernel(const AdvectArgs<float> A0) {
 #pragma clang fp contract(fast)
     const AdvectArgs<float> A = for_member(A0);
     constexpr int SLAB1_PITCH = 36;  // floats per slab row (32 + 4)
     __shared__ __attribute__((aligned(16))) float s_slab1[2][2][LINES ? 8 * SLAB1_PITCH : 4];
     const int K = KFIX >= 0 ? KFIX : A.K;  // KFIX: SETTLS_order known at compile time (the iteration loop unrolls)
-    // the longitude wrap / clamp deferred like the latitude clamp (the two-seed kernel's DEFER_X, see there)
-    constexpr bool DEFER_X = LCS_LDS2_DEFER_X != 0;
     typedef TileGeom<ORDER> G;
     constexpr int LT_COLS = G::COLS, LT_ROWS = G::ROWS, LT_PITCH = G::PITCH;
     constexpr int WIN = ORDER + 1;  // window edge in nodes
@@ -1613,7 +1557,7 @@ __global__ void __launch_bounds__(BLOCK, ORDER == 3 ? LCS_O3_MINWAVES : 1)
         A.traj_y[idx] = p.y;
     }
     float ymax_v = A.y_max;
-    asm volatile("" : "+v"(ymax_v));  // keep it in a VGPR (a VOP3 takes one SGPR; see clamp_position_p)
+    asm volatile("" : "+v"(ymax_v));  // keep it in a VGPR (a VOP3 takes one SGPR; see clamp_position_c)
     const unsigned tile_addr = lds_address(tile);
     unsigned pitch_bytes = (unsigned)LT_PITCH * 8u;
     asm volatile("" : "+s"(pitch_bytes));  // one SGPR for the whole kernel (a VOP3 literal is not encodable)
@@ -1628,10 +1572,6 @@ __global__ void __launch_bounds__(BLOCK, ORDER == 3 ? LCS_O3_MINWAVES : 1)
     // one wraps to the far end of the periodic axis (measured 2 % faster, rejected).  Same expression as
     // index_coords(), so the exact-redo path sees the same coordinate as the common path.
     auto to_index = [&](f2 q) { return (q - pmin) * sc; };
-    // the common case needs the new longitude strictly inside these bounds (Q7 wrap / Q9 clamp otherwise)
-    // (cyclic: |x| < 180 is one compare with a source modifier; hence the template parameter)
-    const float xlo = A.x_min, xhi = A.x_max;
-    auto x_needs_care = [&](float x) { return CYCLIC ? !(fabsf(x) < 180.0f) : !((x > xlo) & (x < xhi)); };
     const float *lvl = A.img + (size_t)A.t0 * A.level_elems;
     const float *elv = A.ext + (size_t)A.t0 * A.level_elems;
     const int pad_cols = A.pitch, pad_rows = A.ny_f + LC_PAD;  // >= LT_COLS, LT_ROWS (checked by the launcher)
@@ -1709,13 +1649,11 @@ __global__ void __launch_bounds__(BLOCK, ORDER == 3 ? LCS_O3_MINWAVES : 1)
                 e = euler_global<ORDER>(lvl, A, t);
             }
             f2 pn = dd * e + p;
-            if (!DEFER_X) bad |= x_needs_care(pn.x);
             if (bad) {  // exact sequence
                 c0 = index_coords(A, p);
                 t = tap_of(c0);
                 e = euler_global<ORDER>(lvl, A, t);
                 pn = dd * e + p;
-                if (!DEFER_X) clamp_position_p(A, pn, ymax_v);
             }
             dprev = (pn - p) * sc;  // Euler displacement in index space
             p = pn;
@@ -1737,7 +1675,7 @@ __global__ void __launch_bounds__(BLOCK, ORDER == 3 ? LCS_O3_MINWAVES : 1)
             // window origins floor(c) the common case accepts: inside the tile AND in [0, n-2] (no wrap)
             const int sox = ox - WOFF, soy = oy - WOFF;
             const int hx = min(sox + LT_COLS - WIN, A.nx_f - 2), hy = min(soy + LT_ROWS - WIN, A.ny_f - 2);
-            const int lx = max(sox, DEFER_X ? 1 : 0), ly = max(soy, DEFER_X ? 1 : 0);  // (DEFER_X: origin 0 to the exact path, as in the two-seed kernel)
+            const int lx = max(sox, 1), ly = max(soy, 1);  // (the deferred wrap: origin 0 to the exact path, as in the two-seed kernel)
             if (hx >= lx && hy >= ly) {
                 lo_x = lx;
                 lo_y = ly;
@@ -1747,10 +1685,10 @@ __global__ void __launch_bounds__(BLOCK, ORDER == 3 ? LCS_O3_MINWAVES : 1)
             }
         }
         // ---- 4. K iterations out of LDS ----------------------------------------------------------
-        // The latitude clamp (trajectory.py:89-90) is DEFERRED: a latitude outside [y_min, y_max] maps to an index
-        // outside [0, n-1), which the next sample's window test flags, and every exact-redo path starts by
-        // clamping the position it was handed -- the same values as clamping after each update, one v_med3
-        // per level instead of one per sample.
+        // The latitude clamp (trajectory.py:89-90) and the longitude wrap / clamp are DEFERRED: a position they would
+        // touch maps to an index outside [0, n-1), which the next sample's window test flags, and every exact-redo
+        // path starts by clamping the position it was handed -- the same values as clamping after each update, one
+        // clamp of each kind per level instead of one per sample.
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             // absolute index coordinate: its rounding must not depend on where the tile sits (row-sharded runs
@@ -1760,23 +1698,15 @@ __global__ void __launch_bounds__(BLOCK, ORDER == 3 ? LCS_O3_MINWAVES : 1)
             bool bad = ((unsigned)rx > (unsigned)lim_x) | ((unsigned)ry > (unsigned)lim_y);
             const f2 ew = window_lds<ORDER, LT_PITCH, VERIFY>(base_addr, pitch_bytes, rx, ry, t, e);  // e + sample of ext[t]
             f2 pn = hd * ew + p;
-            if (!DEFER_X) bad |= x_needs_care(pn.x);
             if (bad) {  // exact sequence, global gather
                 f2 pc = p;
-                if (DEFER_X)
-                    clamp_position_c<CYCLIC>(A, pc, ymax_v);  // the deferred clamps of the previous update (Q7 / Q8 / Q9)
-                else
-                    pc.y = __builtin_amdgcn_fmed3f(pc.y, A.y_min, ymax_v);  // the deferred clamp (Q8)
+                clamp_position_c<CYCLIC>(A, pc, ymax_v);  // the deferred clamps of the previous update (Q7 / Q8 / Q9)
                 t = tap_of(index_coords(A, pc));
                 pn = hd * window_global<ORDER>(elv, A, t, e) + pc;
-                if (!DEFER_X) clamp_position_p(A, pn, ymax_v);
             }
             p = pn;
         }
-        if (DEFER_X)
-            clamp_position_c<CYCLIC>(A, p, ymax_v);  // the level's one clamp of either kind (stores, next Euler sample)
-        else
-            p.y = __builtin_amdgcn_fmed3f(p.y, A.y_min, ymax_v);  // the level's one latitude clamp (stores, next Euler sample)
+        clamp_position_c<CYCLIC>(A, p, ymax_v);  // the level's one clamp of either kind (stores, next Euler sample)
         if constexpr (VERIFY) {
             if (A.verify && K > 0) {
                 // the audit: every lane reads back the 16 bytes it staged for this level, after the last window read
@@ -1821,7 +1751,7 @@ __global__ void __launch_bounds__(BLOCK, ORDER == 3 ? LCS_O3_MINWAVES : 1)
             sy[o] = p.y;
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // one barrier per level: two slabs alternate
             const f4 line = *(const f4 *)(s_slab1[s & 1][wave & 1] + (lane >> 3) * SLAB1_PITCH + (lane & 7) * 4);
-            if (sl_ok) LCS_TRAJ_STORE((wave ? A.traj_y : A.traj_x) + (size_t)(s + 1) * plane + sl_idx, line);
+            if (sl_ok) traj_store_line((wave ? A.traj_y : A.traj_x) + (size_t)(s + 1) * plane + sl_idx, line);
         } else if (live && A.traj_x) {
             A.traj_x[(size_t)(s + 1) * plane + idx] = p.x;
             A.traj_y[(size_t)(s + 1) * plane + idx] = p.y;
@@ -1857,20 +1787,12 @@ constexpr int SPL = 2;  // seeds per lane
 // tile brings y down to 1.5 % and the wave-samples with a redo from 19 % to 11 %, but its second staging pass
 // costs what the redos saved (7.19 against 7.04 ms).  C5 (seeds half as dense, 200 steps) is slower per particle
 // whatever the tile: its patches are pulled apart by the flow over the longer integration, not merely too wide.
-#ifndef LCS_LDS2_ROWS
-#define LCS_LDS2_ROWS 8
-#endif
-#ifndef LCS_LDS2_COLS
-#define LCS_LDS2_COLS 16
-#endif
-#ifndef LCS_LDS2_PITCH
-#define LCS_LDS2_PITCH (LCS_LDS2_COLS + 4)
-#endif
+constexpr int LDS2_ROWS = 8, LDS2_COLS = 16, LDS2_PITCH = LDS2_COLS + 4;
 struct Lds2Geom {  // staging: a tile row = COLS/2 lanes x 16 bytes
-    static constexpr int COLS = LCS_LDS2_COLS, LANES_PER_ROW = COLS / 2, ROWS_PER_PASS = 64 / LANES_PER_ROW;
+    static constexpr int COLS = LDS2_COLS, LANES_PER_ROW = COLS / 2, ROWS_PER_PASS = 64 / LANES_PER_ROW;
     // one pass of 64 lanes covers the tile, or the tile is a whole number of full passes (a row count that 64 lanes do not
     // divide -- 12 x 10 nodes: 6 lanes per row, 10 rows, lanes 60..63 over -- has the spare lanes repeat the last row)
-    static_assert(LCS_LDS2_ROWS % ROWS_PER_PASS == 0 || LCS_LDS2_ROWS < ROWS_PER_PASS + 1, "tile rows per staging pass");
+    static_assert(LDS2_ROWS % ROWS_PER_PASS == 0 || LDS2_ROWS < ROWS_PER_PASS + 1, "tile rows per staging pass");
 };
 
 #ifdef LCS_STAMPS  // diagnostic build only: where a wave's cycles go (s_memtime), summed over waves and levels
@@ -1893,9 +1815,7 @@ __device__ unsigned long long g_class[6];
 
 // 98 SGPRs as compiled admit 6 workgroups per CU (MI355X_MICROARCH.md: 97-112 -> 6); capped at 96 -> 7
 // (7.55 -> 7.31 ms on C3; 80 -> 8 workgroups measures the same as 96).
-#ifndef LCS_LDS2_NUM_SGPR
-#define LCS_LDS2_NUM_SGPR 96
-#endif
+constexpr int LDS2_NUM_SGPR = 96;
 // Which seeds a wave holds, and how return_traj's positions reach memory (template parameter MODE).  Per-seed arithmetic
 // does not depend on it: results are bit-identical in every mode.
 //   PATCH_TALL   lane = column + 8 * row, the lane's second seed 8 rows further down: 8 x 16 seeds per wave, the four waves
@@ -1919,64 +1839,40 @@ __device__ unsigned long long g_class[6];
 // (enum Patch: declared above the one-seed kernel, which shares PATCH_LINES' store form)
 constexpr int SLAB_PITCH = 36;  // floats per slab row (32 + 4: rows stay 16-byte aligned)
 
-// (65 VGPRs = 7 waves per SIMD.  Asked for 8 -- -DLCS_LDS2_MINWAVES=8 -DLCS_LDS2_NUM_SGPR=80: 57 VGPRs, 78 SGPRs, no
+// (65 VGPRs = 7 waves per SIMD.  Asked for 8 -- LDS2_MINWAVES = 8, LDS2_NUM_SGPR = 80: 57 VGPRs, 78 SGPRs, no
 // spills -- C3 measures 6.58-6.73 ms against 6.48-6.52 and config 5 302 against 299 ms: occupancy is not what either lacks.)
-#ifndef LCS_LDS2_MINWAVES
-#define LCS_LDS2_MINWAVES 1
-#endif
-// DIRECT LEVELS (round 6).  Which waves leave their tiles is not spread thin: on C3, 77 % of the wave-levels have no redo in
-// any of their four iterations and 17 % have one in ALL four (2.5 / 1.7 / 1.3 % in one / two / three), and a wave that had
-// three or more is at four again in the next level 92 times in 100 (-DLCS_STAMPS, g_hist: patches the flow has stretched
-// beyond the tile, polar rows whose zonal travel is longer than the tile -- they stay that way).  Such a wave pays for the
-// tile (staging, 2 x 17 instructions of window arithmetic per iteration) and then for the exact sequence on top (2 x 27) in
-// every iteration.  So a wave whose level had >= 3 iterations with a redo takes the next LCS_LDS2_DIRECT_LEVELS levels
-// DIRECT: no tile, every lane through the exact sequence (the redo block, unmasked); then one level with a tile again, which
-// decides anew.  Same functions, same values (a seed's bits do not depend on which path served it).  0 = never.
-// MEASURED AND NOT ADOPTED (profiles/r06/direct_levels_ab.txt): C3 advect 5.99-6.03 ms without, 6.13-6.15 / 6.15-6.20 /
-// 6.23-6.25 ms with 3 / 7 / 15 direct levels -- the instructions saved (~12 % of the VALU stream) are vector-L1 lookups
-// spent: a direct level gathers 2 x 16 bytes per sample for ALL 64 lanes of the wave where the redo path gathers for the
-// ~29 % that left the tile, and the vector L1 already answers 0.73 lookups per CU-cycle.  (A launch made of polar rows alone
-// does gain: rank 7 of 8 of C4, 14.2 -> 13.0 ms.)  Kept as a compile-time option, off.
-#ifndef LCS_LDS2_DPP_NEXT
-#define LCS_LDS2_DPP_NEXT 1   // node c+2 of the staging from the neighbouring lane (two DPP moves) instead of an 8-byte load: C3 5.98 -> 5.91 ms
-                             // (one vector-memory instruction of eight per wave-level less; profiles/r06/headline_kernel_ab.txt section 9).  0: the load
-#endif
-#ifndef LCS_LDS2_DIRECT_LEVELS
-#define LCS_LDS2_DIRECT_LEVELS 0
-#endif
-// THE OUT-OF-TILE PATH of an iteration (tall patches and PATCH_LINES; DEFER_X).  A sample whose window leaves the wave's tile is
+constexpr int LDS2_MINWAVES = 1;
+// Node c+2 of the staging comes from the neighbouring lane (two DPP moves) instead of an 8-byte load: C3 5.98 -> 5.91 ms (one
+// vector-memory instruction of eight per wave-level less; profiles/r06/headline_kernel_ab.txt section 9).  The load, and the
+// direct levels of sections 3 to 5 of that file (measured and not adopted), are in
+// tools/experiments/advect_r06_compile_time_forks.patch.
+// THE OUT-OF-TILE PATH of an iteration (tall patches and PATCH_LINES).  A sample whose window leaves the wave's tile is
 // almost always still inside the grid, and the exact sequence then recomputes what the common path has: with the common-path
 // window origin in [1, n - 2] on both axes the position is strictly inside both clamps (they are identities), index_coords()
 // does not wrap, and its coordinate is to_index()'s bit for bit -- the very conditions under which the common path serves a
-// sample from the tile.  LCS_LDS2_REUSE_TAP: such a sample keeps the common path's tap and goes straight to the gather (12 of
+// sample from the tile.  REUSE_TAP: such a sample keeps the common path's tap and goes straight to the gather (12 of
 // the sequence's 27 instructions less); origin 0 (Q7's x > -180, Q8's NaN) and everything outside take the whole sequence.
-// C3: 90.8 % of the out-of-tile seed-samples; advect 5.67-5.69 -> 5.57-5.60 ms (profiles/out_of_tile/).  0: the whole sequence
-// for every out-of-tile sample.
-#ifndef LCS_LDS2_REUSE_TAP
-#define LCS_LDS2_REUSE_TAP 1
-#endif
+// C3: 90.8 % of the out-of-tile seed-samples; advect 5.67-5.69 -> 5.57-5.60 ms (profiles/out_of_tile/).
 template <int KFIX, bool CYCLIC, int MODE>
-__global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgpu_num_sgpr(LCS_LDS2_NUM_SGPR)))
+__global__ void __launch_bounds__(BLOCK, LDS2_MINWAVES) __attribute__((amdgpu_num_sgpr(LDS2_NUM_SGPR)))
     advect_lds2_kernel(const AdvectArgs<float> A0) {
 #pragma clang fp contract(fast)
     const AdvectArgs<float> A = for_member(A0);
     constexpr bool WIDE = MODE == PATCH_WIDE, LINES = MODE == PATCH_LINES, GROUP = MODE == PATCH_PAIR;
     constexpr int NS = SPL;  // seeds per lane (member groups: members per lane)
     constexpr int ORDER = 1;
-    constexpr bool DEFER_X = LCS_LDS2_DEFER_X != 0;
-    constexpr int DIRECT_LEVELS = DEFER_X ? LCS_LDS2_DIRECT_LEVELS : 0;
-    constexpr bool REUSE_TAP = LCS_LDS2_REUSE_TAP != 0 && DEFER_X && (MODE == PATCH_TALL || LINES);  // (see THE OUT-OF-TILE PATH)
+    constexpr bool REUSE_TAP = MODE == PATCH_TALL || LINES;  // (see THE OUT-OF-TILE PATH)
     // (a DPP row is 16 lanes: the neighbouring lane holds the next nodes of the same tile row only when tile rows do not straddle DPP rows)
-    constexpr bool DPP_NEXT = LCS_LDS2_DPP_NEXT != 0 && 16 % Lds2Geom::LANES_PER_ROW == 0;
+    static_assert(16 % Lds2Geom::LANES_PER_ROW == 0, "node c+2 of the staging comes from the neighbouring lane of the DPP row");
     const int K = KFIX >= 0 ? KFIX : A.K;
     typedef Lds2Geom G;
-    constexpr int LT_COLS = G::COLS, LT_ROWS = LCS_LDS2_ROWS;
+    constexpr int LT_COLS = G::COLS, LT_ROWS = LDS2_ROWS;
     // LDS tile of 16-byte entries {u, v, u[x+1] - u, v[x+1] - v}: the x-differences of the two lerps are formed
-    // ONCE per node when the tile is staged (2 packed subtractions + one more 8-byte load per lane and level) instead of
+    // ONCE per node when the tile is staged (2 packed subtractions + two cross-lane moves per lane and level) instead of
     // once per sample (2 per sample and seed), and a window is two 16-byte reads instead of four 8-byte ones.
     // Same values as n00 + tx * (n01 - n00): results stay bit-identical to the other float kernels.
     // Pitch 20 entries: rows shift 16 banks, no conflicts between neighbouring rows for ds_read_b128.
-    constexpr int LT_PITCH = LCS_LDS2_PITCH;
+    constexpr int LT_PITCH = LDS2_PITCH;
     constexpr int WIN = 2, WOFF = LC_PAD_LO;
     __shared__ __attribute__((aligned(16))) f4 s_tiles[BLOCK / 64][LT_ROWS * LT_PITCH];
     // PATCH_LINES: two slabs (alternating by level) of the workgroup's 16 x 32 longitudes and latitudes
@@ -2093,8 +1989,6 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
     asm volatile("" : "+s"(pitch_bytes));
     const f2 pmin = {A.lon_min, A.lat_min}, sc = {A.sx, A.sy};
     auto to_index = [&](f2 v) { return (v - pmin) * sc; };  // subtract first: exact 0 at the grid origin
-    const float xlo = A.x_min, xhi = A.x_max;
-    auto x_needs_care = [&](float x) { return CYCLIC ? !(fabsf(x) < 180.0f) : !((x > xlo) & (x < xhi)); };
     // a window origin in [1, n - 2] on both axes: one unsigned compare each (a field these kernels take has more than two nodes
     // on either axis: order1_two_seed_applies)
     auto origin_inside = [&](const TapL &t) { return ((unsigned)(t.x0 - 1) < (unsigned)(A.nx_f - 2)) & ((unsigned)(t.y0 - 1) < (unsigned)(A.ny_f - 2)); };
@@ -2105,9 +1999,6 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
     const int st_row = min(lane / G::LANES_PER_ROW, LT_ROWS - 1), st_col = (lane % G::LANES_PER_ROW) * 2;
     const unsigned st_off = ((unsigned)st_row * (unsigned)pad_cols + (unsigned)st_col) * 8u;
     constexpr int NPASS = (LT_ROWS + G::ROWS_PER_PASS - 1) / G::ROWS_PER_PASS;
-    // node c+2 of the lane's tile row (the x-difference of node c+1 needs it): loaded with the tile, 8 more bytes
-    // per lane; the last lane of a row re-reads its own node instead (its entry c+1 is never a window origin)
-    const unsigned st_next = st_off + (st_col + 2 < LT_COLS ? 16u : 0u);
     // seed 0 of the lane in the patch's middle: row 8 of 16 (tall patches), row 4 of 8 and column 8 of 16 (PATCH_WIDE)
     constexpr int CENTRE = (WIDE || GROUP) ? TILE_W / 2 + TILE_W * 4 : TILE_W / 2 + TILE_W * 7;
     f2 dprev = {0.0f, 0.0f};
@@ -2118,10 +2009,7 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
     unsigned long long acc_n[3] = {0, 0, 0};
     int prev_redos = 0;
 #endif
-    int direct_left = 0;  // wave-uniform: levels this wave still takes without a tile
     for (int s = 0; s < nlev; ++s) {
-        const bool direct = DIRECT_LEVELS > 0 && direct_left > 0;
-        if (direct) --direct_left;
 #ifdef LCS_STAMPS
         int level_redos = 0;
 #endif
@@ -2155,8 +2043,7 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
         // ---- 1. anchor the tile on the centre lane's predicted travel and issue its loads ------------
         int ox = 0, oy = 0;
         f4 stage[NPASS];
-        f2 stage_next[NPASS];
-        if (K > 0 && !direct) {
+        if (K > 0) {
             // (anchoring a pair's tile half way between its two members instead: 276.4 against 276.4 ms on config 5)
             const f2 ca = dprev * (1.0f + kpred) + of_anchor(c0);
             const int rxm = __builtin_amdgcn_readlane((int)floor_to_uint(ca.x), CENTRE);
@@ -2167,10 +2054,8 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
             oy = min(max(rym + WOFF - (LT_ROWS - WIN) / 2, 0), pad_rows - LT_ROWS);
             const char *src = (const char *)elv + ((size_t)__umul24((unsigned)oy, (unsigned)pad_cols) + (unsigned)ox) * 8;
 #pragma unroll
-            for (int r = 0; r < NPASS; ++r) {
+            for (int r = 0; r < NPASS; ++r)
                 __builtin_memcpy(&stage[r], src + (size_t)(r * G::ROWS_PER_PASS) * pad_cols * 8 + st_off, 16);
-                if (!DPP_NEXT) __builtin_memcpy(&stage_next[r], src + (size_t)(r * G::ROWS_PER_PASS) * pad_cols * 8 + st_next, 8);
-            }
         }
         LCS_STAMP(0)  // anchor + tile load issue
         // ---- 2. Euler samples (global gathers) ----------------------------------------------------
@@ -2182,7 +2067,6 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
             bad[q] = ((unsigned)t.x0 > (unsigned)(A.nx_f - 2)) | ((unsigned)t.y0 > (unsigned)(A.ny_f - 2));
             e[q] = euler_global<ORDER>(lvl, A, t);
             pn[q] = dd[q] * e[q] + p[q];
-            if (!DEFER_X) bad[q] |= x_needs_care(pn[q].x);
             anybad |= bad[q];
         }
         if (anybad) {  // exact sequence for the lanes / seeds that need it
@@ -2192,7 +2076,6 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
                     const TapL t = tap_of(index_coords(A, p[q]));
                     e[q] = euler_global<ORDER>(lvl, A, t);
                     pn[q] = dd[q] * e[q] + p[q];
-                    if (!DEFER_X) clamp_position_p(A, pn[q], ymax_v);
                 }
             }
         }
@@ -2206,7 +2089,7 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
         // ---- 3. tile into LDS ------------------------------------------------------------------------
         int lo_x = 0x40000000, lo_y = 0x40000000, lim_x = 0, lim_y = 0;  // no tile: nothing is "inside"
         unsigned base_addr = tile_addr;
-        if (K > 0 && !direct) {
+        if (K > 0) {
             __builtin_amdgcn_wave_barrier();  // the previous level's reads are done (LDS ops of a wave are in order)
 #pragma unroll
             for (int r = 0; r < NPASS; ++r) {
@@ -2217,17 +2100,12 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
                 // TILE row receives the next tile row's first node or zero, and its entry c+1 is never a window origin.  (s_nop 4:
                 // the five wait states a DPP instruction needs after a VALU write of EXEC, two after one of its source, whatever
                 // precedes the statement: tools/asm_hazards.py audits the sites.)
-                f2 nxt;
-                if constexpr (DPP_NEXT) {
-                    float nx0, nx1;
-                    const float s0 = stage[r].x, s1 = stage[r].y;
-                    asm volatile("s_nop 4\n\tv_mov_b32_dpp %0, %2 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-                                 "v_mov_b32_dpp %1, %3 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0"
-                                 : "=&v"(nx0), "=&v"(nx1) : "v"(s0), "v"(s1));
-                    nxt = (f2){nx0, nx1};
-                } else {
-                    nxt = stage_next[r];
-                }
+                float nx0, nx1;
+                const float s0 = stage[r].x, s1 = stage[r].y;
+                asm volatile("s_nop 4\n\tv_mov_b32_dpp %0, %2 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                             "v_mov_b32_dpp %1, %3 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0"
+                             : "=&v"(nx0), "=&v"(nx1) : "v"(s0), "v"(s1));
+                const f2 nxt = {nx0, nx1};
                 f4 *dst = tile + (r * G::ROWS_PER_PASS + st_row) * LT_PITCH + st_col;
                 const f2 n0 = stage[r].xy, n1 = stage[r].zw, d0 = n1 - n0, d1 = nxt - n1;
                 dst[0] = (f4){n0.x, n0.y, d0.x, d0.y};
@@ -2236,12 +2114,12 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
             __builtin_amdgcn_wave_barrier();
             const int sox = ox - WOFF, soy = oy - WOFF;
             const int hx = min(sox + LT_COLS - WIN, A.nx_f - 2), hy = min(soy + LT_ROWS - WIN, A.ny_f - 2);
-            // DEFER_X: column 0 and row 0 are left to the exact path.  A parcel sitting EXACTLY on lon_min = -180 has index
+            // The deferred wrap: column 0 and row 0 are left to the exact path.  A parcel sitting EXACTLY on lon_min = -180 has index
             // 0.0 and must still meet Q7's `x > -180` test (every other longitude the reference would wrap or clamp maps
             // to an index outside [0, n-1) and fails the window test by itself); and a NaN coordinate converts to index 0,
             // so with origin 0 excluded it fails the window test on either axis and is clamped first (Q8: a NaN latitude
-            // becomes y_min while the longitude lives on) -- the round-5 form caught it through x_needs_care(NaN).
-            const int lx = max(sox, DEFER_X ? 1 : 0), ly = max(soy, DEFER_X ? 1 : 0);
+            // becomes y_min while the longitude lives on).
+            const int lx = max(sox, 1), ly = max(soy, 1);
             if (hx >= lx && hy >= ly) {
                 lo_x = lx;
                 lo_y = ly;
@@ -2254,20 +2132,7 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 #endif
         LCS_STAMP(2)  // wait for the tile + LDS write
-        // ---- 4. K iterations out of LDS (latitude clamp deferred to the redo path / the level's end) -----
-        int redos = 0;  // iterations of this level in which some lane needed the exact sequence (wave-uniform)
-        if (direct) {   // (see LCS_LDS2_DIRECT_LEVELS) the exact sequence for every lane, no tile
-#pragma unroll 1
-            for (int k = 0; k < K; ++k) {
-#pragma unroll
-                for (int q = 0; q < NS; ++q) {
-                    f2 pc = p[q];
-                    clamp_position_c<CYCLIC>(A, pc, ymax_v);
-                    const TapL t = tap_of(index_coords(A, pc));
-                    p[q] = hd[q] * window_global<ORDER>(elv, A, t, e[q]) + pc;
-                }
-            }
-        } else
+        // ---- 4. K iterations out of LDS (both clamps deferred to the redo path / the level's end) -----
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             anybad = false;
@@ -2299,7 +2164,6 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
                 const f2 r1 = c1.xy + t.tx * c1.zw;   // n10 + tx (n11 - n10)
                 const f2 ew = e[q] + (r0 + t.ty * (r1 - r0));  // e + sample of ext[t]
                 pn[q] = hd[q] * ew + p[q];
-                if (!DEFER_X) bad[q] |= x_needs_care(pn[q].x);
                 anybad |= bad[q];
             }
 #ifdef LCS_STAMPS
@@ -2323,20 +2187,14 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
                 }
             }
 #endif
-            if (DIRECT_LEVELS > 0) redos += __ballot(anybad) != 0ull;
             // the out-of-tile sample of one seed: the exact sequence and a global gather -- or, for a window origin inside the
             // grid, the gather alone at the common path's tap (see THE OUT-OF-TILE PATH)
             auto exact_sample = [&](f2 pc, TapL t, f2 eq, f2 hq) {
                 if (!REUSE_TAP || !origin_inside(t)) {
-                    if (DEFER_X)
-                        clamp_position_c<CYCLIC>(A, pc, ymax_v);  // the deferred clamps of the previous update (Q7 / Q8 / Q9)
-                    else
-                        pc.y = __builtin_amdgcn_fmed3f(pc.y, A.y_min, ymax_v);  // the deferred clamp (Q8)
+                    clamp_position_c<CYCLIC>(A, pc, ymax_v);  // the deferred clamps of the previous update (Q7 / Q8 / Q9)
                     t = tap_of(index_coords(A, pc));
                 }
-                f2 r = hq * window_global<ORDER>(elv, A, t, eq) + pc;
-                if (!DEFER_X) clamp_position_p(A, r, ymax_v);
-                return r;
+                return hq * window_global<ORDER>(elv, A, t, eq) + pc;
             };
             if (anybad) {
 #pragma unroll
@@ -2346,14 +2204,8 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
 #pragma unroll
             for (int q = 0; q < NS; ++q) p[q] = pn[q];
         }
-        if (DIRECT_LEVELS > 0 && redos >= 3) direct_left = DIRECT_LEVELS;
 #pragma unroll
-        for (int q = 0; q < NS; ++q) {  // the level's one latitude clamp -- and, with DEFER_X, its one longitude test
-            if (DEFER_X)
-                clamp_position_c<CYCLIC>(A, p[q], ymax_v);
-            else
-                p[q].y = __builtin_amdgcn_fmed3f(p[q].y, A.y_min, ymax_v);
-        }
+        for (int q = 0; q < NS; ++q) clamp_position_c<CYCLIC>(A, p[q], ymax_v);  // the level's one latitude clamp and its one longitude test
         if (GROUP) {  // a member outside its own steps keeps its position, bit for bit
 #pragma unroll
             for (int q = 0; q < NS; ++q)
@@ -2374,7 +2226,7 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_MINWAVES) __attribute__((amdgp
             const f4 line = *(const f4 *)(s_slab[s & 1][wave >> 1] + sl_row * SLAB_PITCH + sl_col);
             if (sl_ok) {
                 float *dst = ((wave >> 1) ? A.traj_y : A.traj_x) + (size_t)(s + 1) * plane + sl_idx;
-                LCS_TRAJ_STORE(dst, line);
+                traj_store_line(dst, line);
             }
         } else if (A.traj_x) {
             store_pair(A.traj_x, A.traj_y, (size_t)(s + 1) * plane);
@@ -2502,7 +2354,7 @@ struct PatchLanes {  // the lane's SPL seeds: where they are in the grid, their 
             }
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // (one barrier per level: see advect_lds2_kernel)
             const f4 line = *(const f4 *)(((wave >> 1) ? sy : sx) + sl_row * SLAB_PITCH + sl_col);
-            if (sl_ok) LCS_TRAJ_STORE(((wave >> 1) ? A.traj_y : A.traj_x) + (size_t)(s + 1) * plane + sl_idx, line);
+            if (sl_ok) traj_store_line(((wave >> 1) ? A.traj_y : A.traj_x) + (size_t)(s + 1) * plane + sl_idx, line);
         } else if (A.traj_x) {
             store_lanes(A.traj_x, A.traj_y, (size_t)(s + 1) * plane);
         }
@@ -2524,16 +2376,13 @@ struct PatchLanes {  // the lane's SPL seeds: where they are in the grid, their 
 
 // 97 VGPRs as compiled = 4 waves per SIMD; asked for 5 (96 VGPRs) it measures 16.05-16.1 ms on C3 against 16.6-16.7, asked
 // for 6 (spills) 17.4; the one-seed kernel 17.2 on the same box (profiles/r03).
-#ifndef LCS_LDS2_O3_MINWAVES
-#define LCS_LDS2_O3_MINWAVES 5
-#endif
+constexpr int LDS2_O3_MINWAVES = 5;
 template <int KFIX, bool CYCLIC, int MODE>
-__global__ void __launch_bounds__(BLOCK, LCS_LDS2_O3_MINWAVES) advect_lds2_o3_kernel(const AdvectArgs<float> A0) {
+__global__ void __launch_bounds__(BLOCK, LDS2_O3_MINWAVES) advect_lds2_o3_kernel(const AdvectArgs<float> A0) {
 #pragma clang fp contract(fast)
     const AdvectArgs<float> A = for_member(A0);
     constexpr int ORDER = 3;
     constexpr bool WIDE = MODE == PATCH_WIDE, LINES = MODE == PATCH_LINES;
-    constexpr bool DEFER_X = LCS_LDS2_DEFER_X != 0;  // the longitude wrap / clamp deferred like the latitude clamp (see the order-1 kernel)
     const int K = KFIX >= 0 ? KFIX : A.K;
     typedef TileGeom<ORDER> G;
     typedef EulerGeom<ORDER> E;
@@ -2560,8 +2409,6 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_O3_MINWAVES) advect_lds2_o3_ke
     asm volatile("" : "+s"(epitch_bytes));
     const f2 pmin = {A.lon_min, A.lat_min}, sc = {A.sx, A.sy};
     auto to_index = [&](f2 v) { return (v - pmin) * sc; };  // subtract first: exact 0 at the grid origin
-    const float xlo = A.x_min, xhi = A.x_max;
-    auto x_needs_care = [&](float x) { return CYCLIC ? !(fabsf(x) < 180.0f) : !((x > xlo) & (x < xhi)); };
     const float *lvl = A.img + (size_t)A.t0 * A.level_elems;
     const float *elv = A.ext + (size_t)A.t0 * A.level_elems;
     const int pad_cols = A.pitch, pad_rows = A.ny_f + LC_PAD;
@@ -2609,7 +2456,6 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_O3_MINWAVES) advect_lds2_o3_ke
                 bad[q] |= ((unsigned)rx > (unsigned)(hx - lx)) | ((unsigned)ry > (unsigned)(hy - ly)) | (hx < lx) | (hy < ly);
                 e[q] = window_lds<ORDER, E::PITCH>(ebase, epitch_bytes, rx, ry, t0[q], zero);
                 pn[q] = L.dd[q] * e[q] + p[q];
-                if (!DEFER_X) bad[q] |= x_needs_care(pn[q].x);
                 anybad |= bad[q];
             }
         }
@@ -2620,7 +2466,6 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_O3_MINWAVES) advect_lds2_o3_ke
                     const TapL t = tap_of(index_coords(A, p[q]));
                     e[q] = euler_global<ORDER>(lvl, A, t);
                     pn[q] = L.dd[q] * e[q] + p[q];
-                    if (!DEFER_X) clamp_position_p(A, pn[q], ymax_v);
                 }
             }
         }
@@ -2647,7 +2492,7 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_O3_MINWAVES) advect_lds2_o3_ke
             __builtin_amdgcn_wave_barrier();
             const int sox = ox - WOFF, soy = oy - WOFF;
             const int hx = min(sox + LT_COLS - WIN, A.nx_f - 2), hy = min(soy + LT_ROWS - WIN, A.ny_f - 2);
-            const int lx = max(sox, DEFER_X ? 1 : 0), ly = max(soy, DEFER_X ? 1 : 0);  // (DEFER_X: origin 0 to the exact path, as at order 1)
+            const int lx = max(sox, 1), ly = max(soy, 1);  // (the deferred wrap: origin 0 to the exact path, as at order 1)
             if (hx >= lx && hy >= ly) {
                 lo_x = lx;
                 lo_y = ly;
@@ -2656,7 +2501,7 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_O3_MINWAVES) advect_lds2_o3_ke
                 base_addr = tile_addr + (unsigned)(lx - sox) * 8u + (unsigned)(ly - soy) * ((unsigned)LT_PITCH * 8u);
             }
         }
-        // ---- 3. K iterations out of LDS (latitude clamp deferred to the redo path / the level's end) ---------------
+        // ---- 3. K iterations out of LDS (both clamps deferred to the redo path / the level's end, see the order-1 kernel) ----
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             anybad = false;
@@ -2667,7 +2512,6 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_O3_MINWAVES) advect_lds2_o3_ke
                 bad[q] = ((unsigned)rx > (unsigned)lim_x) | ((unsigned)ry > (unsigned)lim_y);
                 const f2 ew = window_lds<ORDER, LT_PITCH>(base_addr, pitch_bytes, rx, ry, t, e[q]);  // e + sample of ext[t]
                 pn[q] = L.hd[q] * ew + p[q];
-                if (!DEFER_X) bad[q] |= x_needs_care(pn[q].x);
                 anybad |= bad[q];
             }
             if (anybad) {
@@ -2675,13 +2519,9 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_O3_MINWAVES) advect_lds2_o3_ke
                 for (int q = 0; q < SPL; ++q) {
                     if (bad[q]) {  // exact sequence, global gather
                         f2 pc = p[q];
-                        if (DEFER_X)
-                            clamp_position_c<CYCLIC>(A, pc, ymax_v);  // the deferred clamps of the previous update (Q7 / Q8 / Q9)
-                        else
-                            pc.y = __builtin_amdgcn_fmed3f(pc.y, A.y_min, ymax_v);  // the deferred clamp (Q8)
+                        clamp_position_c<CYCLIC>(A, pc, ymax_v);  // the deferred clamps of the previous update (Q7 / Q8 / Q9)
                         const TapL t = tap_of(index_coords(A, pc));
                         pn[q] = L.hd[q] * window_global<ORDER>(elv, A, t, e[q]) + pc;
-                        if (!DEFER_X) clamp_position_p(A, pn[q], ymax_v);
                     }
                 }
             }
@@ -2689,12 +2529,7 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS2_O3_MINWAVES) advect_lds2_o3_ke
             for (int q = 0; q < SPL; ++q) p[q] = pn[q];
         }
 #pragma unroll
-        for (int q = 0; q < SPL; ++q) {  // the level's one clamp of either kind
-            if (DEFER_X)
-                clamp_position_c<CYCLIC>(A, p[q], ymax_v);
-            else
-                p[q].y = __builtin_amdgcn_fmed3f(p[q].y, A.y_min, ymax_v);
-        }
+        for (int q = 0; q < SPL; ++q) clamp_position_c<CYCLIC>(A, p[q], ymax_v);  // the level's one clamp of either kind
         L.store_level(A, &s_slab[0][0][0], s);
         lvl += A.level_elems;
         elv += A.level_elems;
@@ -3132,28 +2967,14 @@ __device__ void advect_seed_fast64(const AdvectArgs<double> &A, int iy, int ix) 
 // is another image) and a lane whose window left the tile re-samples from global memory.  8 x 8 seeds per wave, four
 // waves stacked per workgroup, no workgroup barrier.
 // ======================================================================================
-#ifndef LCS_T64_ROWS
-#define LCS_T64_ROWS 12
-#endif
-#ifndef LCS_LDS64_MINWAVES
-#define LCS_LDS64_MINWAVES 1
-#endif
-#ifndef LCS_LDS64_NUM_SGPR
-#define LCS_LDS64_NUM_SGPR 0
-#endif
-#ifndef LCS_T64_PITCH
-#define LCS_T64_PITCH 17
-#endif
-constexpr int T64_COLS = 16, T64_ROWS = LCS_T64_ROWS, T64_PITCH = LCS_T64_PITCH;  // nodes
+constexpr int T64_COLS = 16, T64_ROWS = 12, T64_PITCH = 17;  // nodes
+constexpr int LDS64_MINWAVES = 1;
 // RAW: the Euler sample (and the pole rows) from the raw planes of the level instead of the lin image (lc_advect_ex) -- a
 // compile-time variant: as a run-time choice the extra uniform state cost the kernel 9 vector registers and a wave per SIMD.
 // SRC = SRC_RAW_ALL: the tile of ext[t] itself is formed while it is staged -- each lane loads its nodes of levels t and
 // t + 1 from the raw planes (mirrored where the image has pads) and stores 2 F[t] - F[t+1]: no packed image exists at all.
 template <int KFIX, bool CYCLIC, int SRC>
-__global__ void __launch_bounds__(BLOCK, LCS_LDS64_MINWAVES)
-#if LCS_LDS64_NUM_SGPR > 0
-    __attribute__((amdgpu_num_sgpr(LCS_LDS64_NUM_SGPR)))
-#endif
+__global__ void __launch_bounds__(BLOCK, LDS64_MINWAVES)
     advect_lds64_kernel(const AdvectArgs<double> A0) {
 #pragma clang fp contract(off)
     constexpr bool RAW = SRC != SRC_IMAGES, EXTRAW = SRC == SRC_RAW_ALL;
@@ -3339,26 +3160,13 @@ __global__ void __launch_bounds__(BLOCK, LCS_LDS64_MINWAVES)
 // that follow move the parcel by about K Euler displacements: trajectory.py:100-120 accumulates) -- so the anchor costs no
 // second barrier.  Same locate / lerp / clamp functions, same fallback for a window outside the tile: bit-identical to
 // advect_lds64_kernel and to the direct kernel whatever the tile holds.
-#ifndef LCS_W64_COLS
-#define LCS_W64_COLS 24
-#endif
-#ifndef LCS_W64_ROWS
-#define LCS_W64_ROWS 20
-#endif
-#ifndef LCS_W64_PITCH
-#define LCS_W64_PITCH (LCS_W64_COLS + 1)
-#endif
-#ifndef LCS_W64_NEXT
-#define LCS_W64_NEXT 1   // raw planes only: keep the level-(t + 1) nodes of the staging as the next level's Euler tile
-#endif
-#ifndef LCS_W64_MINWAVES
-#define LCS_W64_MINWAVES 1
-#endif
-constexpr int W64_COLS = LCS_W64_COLS, W64_ROWS = LCS_W64_ROWS, W64_PITCH = LCS_W64_PITCH, W64_SIDE = 16;  // nodes; seeds per side
+constexpr int W64_COLS = 24, W64_ROWS = 20, W64_PITCH = W64_COLS + 1, W64_SIDE = 16;  // nodes; seeds per side
+constexpr int W64_MINWAVES = 1;
 template <int KFIX, bool CYCLIC, int SRC>
-__global__ void __launch_bounds__(BLOCK, LCS_W64_MINWAVES) advect_wg64_kernel(const AdvectArgs<double> A0) {
+__global__ void __launch_bounds__(BLOCK, W64_MINWAVES) advect_wg64_kernel(const AdvectArgs<double> A0) {
 #pragma clang fp contract(off)
-    constexpr bool RAW = SRC != SRC_IMAGES, EXTRAW = SRC == SRC_RAW_ALL, NEXT = EXTRAW && LCS_W64_NEXT != 0;
+    // NEXT (raw planes only): keep the level-(t + 1) nodes of the staging as the next level's Euler tile
+    constexpr bool RAW = SRC != SRC_IMAGES, EXTRAW = SRC == SRC_RAW_ALL, NEXT = EXTRAW;
     constexpr int NODES = W64_COLS * W64_ROWS;
     const AdvectArgs<double> A = for_member(A0);
     const int K = KFIX >= 0 ? KFIX : A.K;
@@ -3618,26 +3426,16 @@ __global__ void __launch_bounds__(BLOCK, LCS_W64_MINWAVES) advect_wg64_kernel(co
 // per workgroup = four workgroups per CU.  Measured on config 2 at order 3 (profiles/r04/c2_o3_lds_pitch_ab.txt): pitch 20
 // for both 16-row tiles 6.39 ms, this 6.24-6.33; pitch 24 for both 16-row tiles (48 KB, three workgroups per CU) 6.79
 // although each wave runs 18 % shorter; round 2-3: pitch 17 8.46, 20 7.90, 24 (48 KB) 8.25.
-#ifndef LCS_T64O3_PITCH
-#define LCS_T64O3_PITCH 24
-#endif
-#ifndef LCS_T64O3_EROWS
-#define LCS_T64O3_EROWS 12   // rows of the Euler tile (img[t]: the patch where it is, 8 rows + the window = 11 at least)
-#endif
-#ifndef LCS_T64O3_EPITCH
-#define LCS_T64O3_EPITCH 20
-#endif
-constexpr int T64O3 = 16, T64O3_PITCH = LCS_T64O3_PITCH, T64O3_EROWS = LCS_T64O3_EROWS, T64O3_EPITCH = LCS_T64O3_EPITCH;
+constexpr int T64O3 = 16, T64O3_PITCH = 24, T64O3_EPITCH = 20;
+constexpr int T64O3_EROWS = 12;  // rows of the Euler tile (img[t]: the patch where it is, 8 rows + the window = 11 at least)
 static_assert(T64O3_EROWS % 4 == 0 && T64O3_EROWS >= 12 && T64O3_EROWS <= T64O3, "Euler tile rows");
-#ifndef LCS_LDS64_O3_MINWAVES
-#define LCS_LDS64_O3_MINWAVES 4   // 128 vector registers: the kernel compiles to 126-129 depending on the tile shapes, and 129 is a wave per SIMD less
-#endif
+constexpr int LDS64_O3_MINWAVES = 4;  // 128 vector registers: the kernel compiles to 126-129 depending on the tile shapes, and 129 is a wave per SIMD less
 // EXTCUB: no ext image -- the iteration tile is staged from the coefficient images of levels t and t + 1 as
 // 2 img[t] - img[t+1] node by node (the pack's own expression: bit-identical), and a window that left the tile takes its
 // taps from both levels.  The pack then neither reads the coefficients back nor writes a second image (float64 config 2:
 // 8.5 GB of 22 per step), and the advect kernel streams ONE image series from HBM instead of two.
 template <int KFIX, bool CYCLIC, bool EXTCUB = false>
-__global__ void __launch_bounds__(BLOCK, LCS_LDS64_O3_MINWAVES) advect_lds64_o3_kernel(const AdvectArgs<double> A0) {
+__global__ void __launch_bounds__(BLOCK, LDS64_O3_MINWAVES) advect_lds64_o3_kernel(const AdvectArgs<double> A0) {
 #pragma clang fp contract(off)
     const AdvectArgs<double> A = for_member(A0);
     const int K = KFIX >= 0 ? KFIX : A.K;

@@ -851,22 +851,15 @@ __global__ void __launch_bounds__(64) prefilter_rows_stream_kernel(double *__res
 // integer division anywhere -- the first form, one flat index per node decomposed with two 64-bit divisions, was bound
 // by that arithmetic, not by memory (C3: 0.60 ms for 3.4 GB; config 2 in float64 with both images: 2.5 ms for 10 GB).
 // Non-temporal stores of the images (nothing reads them again before the advect kernel streams them): config 2's float64
-// pack 2.07 -> 1.95 ms, C3's 0.54 -> 0.50 (profiles/r03).  -DLCS_PACK_PLAIN: plain stores (A/B).
-#ifdef LCS_PACK_PLAIN
-#define LCS_PACK_STORE(ptr, val) (*(ptr) = (val))
-#else
+// pack 2.07 -> 1.95 ms, C3's 0.54 -> 0.50 (profiles/r03; the plain stores of that A/B: tools/experiments/advect_r06_compile_time_forks.patch).
 #define LCS_PACK_STORE(ptr, val) __builtin_nontemporal_store(val, ptr)
-#endif
 // A thread walks PACK_LV consecutive time levels of its node and carries level t+1 forward, so every raw level is read
 // ONCE (plus one level in PACK_LV at the chunk's end) instead of twice -- as F[t] for lin[t] / ext[t] and again as F[t+1]
 // for ext[t-1]: float64 config 2 moved 13.9 GB for 10.1 GB compulsory that way (profiles/r03/c2_pmc_traffic.json).  The
 // loads of a chunk are issued together (static trip count), then the stores.
 // lin == NULL: the fused-level image alone (lc_field_pack(order 1, packed_dev = NULL): the caller samples order 1 from
 // the raw planes, lc_advect_ex).
-#ifndef LCS_PACK_LV
-#define LCS_PACK_LV 2
-#endif
-constexpr int PACK_LV = LCS_PACK_LV;
+constexpr int PACK_LV = 2;
 template <typename T>
 __global__ void __launch_bounds__(256) pack_fused_kernel(const T *__restrict__ u, const T *__restrict__ v, T *__restrict__ lin,
                                                          T *__restrict__ ext, int nt, int ny, int nx) {

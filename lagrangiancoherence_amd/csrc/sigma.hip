@@ -128,13 +128,8 @@ __global__ void __launch_bounds__(SBLOCK) sigma_batch_kernel_f32(const SigmaArgs
 // strip are loaded as halo: the sincos work per output cell is 1.03 x (1 + 4/MROWS) instead of the LDS tile's 1.33.
 // Five rows of loads are in flight per wave (a register ring indexed like the window).  Same arithmetic as sigma_kernel_f32, bit for bit.
 // ======================================================================================
-#ifndef LCS_SIGMA_MROWS
-#define LCS_SIGMA_MROWS 20
-#endif
-#ifndef LCS_SIGMA_MBLOCK
-#define LCS_SIGMA_MBLOCK 256
-#endif
-constexpr int MBLOCK = LCS_SIGMA_MBLOCK;  // threads per workgroup of the marching kernel (waves are independent)
+constexpr int MARCH_ROWS = 20;  // output rows a wave walks down (the kernels' MROWS)
+constexpr int MBLOCK = 256;      // threads per workgroup of the marching kernel (waves are independent)
 constexpr int MCOLS = 2;                 // columns per lane
 constexpr int MSPAN_OUT = 62 * MCOLS;    // columns written per wave
 
@@ -287,7 +282,7 @@ int sigma_impl(lc_ctx *ctx, const void *x_dep, const void *y_dep, int in_row0, i
     const SigmaRoute route = sigma_route(ctx, A);
     if constexpr (sizeof(T) == 4) {
         if (route == SIGMA_MARCH) {
-            constexpr int MROWS = LCS_SIGMA_MROWS;
+            constexpr int MROWS = MARCH_ROWS;
             const int nspans = (nx + MSPAN_OUT - 1) / MSPAN_OUT, nstrips = (n_out_rows + MROWS - 1) / MROWS;
             const int blocks = (nspans * nstrips + MBLOCK / 64 - 1) / (MBLOCK / 64);
             if (layout == LC_LAYOUT_REFERENCE)

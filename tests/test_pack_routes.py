@@ -130,7 +130,7 @@ def test_the_dispatcher_restated_sends_every_shape_to_its_route():
     assert int(consts["FHALO"]) + 2 == PR.FIR_MIN and int(consts["FT"]) == PR.FIR_TILE
     assert int(consts["PR_CHUNK"]) == PR.STREAM_MIN == 2 * int(consts["RS_C"]) and int(consts["PR_ROWS"]) == int(consts["RS_ROWS"]) == PR.FIR_TILE
     assert "ny >= FHALO + 2 && nx >= FHALO + 2" in code and "cols_stream = stream && ny >= 64" in code and "nx >= PR_CHUNK" in code
-    assert re.search(r"#define LCS_PACK_LV 2\b", code)
+    assert re.search(r"\bconstexpr int PACK_LV = 2;", code)
 
 
 def test_route_inputs_meet_the_edges():
