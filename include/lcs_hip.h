@@ -474,7 +474,15 @@ int lc_advect_series_dirs(lc_ctx *ctx, const lc_advect_args *args, int n_dirs);
 /* One interpolation pass on its own: tools.xr_map_coordinates (LCS/tools.py:11-41) for the
  * u and v fields of time level `level` at the given positions (degrees), same index
  * scale, row classes and boundary modes as inside lc_advect.  pos_x/pos_y/out_u/out_v
- * are [ny*nx] dtype elements on the device. */
+ * are [ny*nx] dtype elements on the device.
+ * Positions that are not finite (every interp_order, both dtypes; the finite positions of the same call are not affected):
+ *   - on a 'wrap' row (interior seed rows) a NaN or infinite coordinate gives NaN: scipy's wrap of an infinite
+ *     coordinate is inf - inf;
+ *   - on a 'constant' row (the first / last interp_order global seed rows) an infinite coordinate is outside the field:
+ *     the sample is exactly 0, as for any coordinate outside [0, n-1], whatever the other coordinate is; a NaN
+ *     coordinate gives NaN unless the other coordinate is outside.
+ * This departs from scipy on purpose: scipy.ndimage.map_coordinates casts such a coordinate to an integer, which is
+ * undefined (scipy 1.15 on x86-64 answers 0 for a NaN or -inf coordinate on a 'wrap' row). */
 int lc_sample(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, int dtype,
               int nt, int ny_f, int nx_f,
               double lat_min, double lat_max, double lon_min, double lon_max, int level,
@@ -507,7 +515,8 @@ int lc_sample_raw(lc_ctx *ctx, const void *packed_lin, const void *packed_cub, c
  *   mean1_out, mean2_out   NULL or [ny*nx] dtype: (dtype)(sum / mean_count) after this range, sum including what sum1 /
  *                sum2 held on entry -- the reference driver's cs.mean('time') over entries 0..nsteps is mean_count =
  *                nsteps + 1 (equal up to summation order).
- * NaN in the tracer is not specified: the sampled value is whatever the interpolation makes of it. */
+ * NaN in the tracer is not specified: the sampled value is whatever the interpolation makes of it.  A NaN or infinite
+ * POSITION is specified: lc_sample's rule for positions that are not finite, entry by entry (a NaN value enters the sums). */
 typedef struct lc_tracer_args {
     size_t struct_size;                                       /* sizeof(lc_tracer_args) as the caller compiled it */
     const void *tracer_lin, *tracer_cub, *c1_raw, *c2_raw;

@@ -283,6 +283,7 @@ struct Tap {
     T wy[6], wx[6];   // scipy's per-axis weights (order+1 of them)
     T ty, tx;         // fractional parts (float order-1 lerp form)
     bool zero;        // 'constant' mode, coordinate outside [0, n-1]: the sample is exactly 0
+    bool nan;         // orders 2, 4, 5: a NaN coordinate (an infinite one is NaN after the wrap): the sample is NaN
 };
 
 template <typename T>
@@ -359,6 +360,7 @@ __device__ __forceinline__ Pair<T> fetch_general(const T *__restrict__ lvl, cons
     Pair<T> r;
     r.u = (T)su;
     r.v = (T)sv;
+    if (t.nan) r.u = r.v = T(NAN);  // the window is node (0, 0)'s, for addressing only: orders 1 and 3 get NaN from their weights
     return r;
 }
 
@@ -377,6 +379,7 @@ __device__ __forceinline__ Tap<T> locate(const AdvectArgs<T> &A, T x, T y) {
     }
     Tap<T> t;
     t.zero = false;
+    t.nan = false;
     if (WRAP) {
         cy = wrap_coord<T>(cy, T(A.ny_f - 1));
         cx = wrap_coord<T>(cx, T(A.nx_f - 1));
@@ -386,7 +389,10 @@ __device__ __forceinline__ Tap<T> locate(const AdvectArgs<T> &A, T x, T y) {
     if (ORDER != 1 && ORDER != 3) {
         t.ty = t.tx = T(0);
         t.off = 0;
-        if (!(cy >= T(0) && cy <= T(A.ny_f - 1) && cx >= T(0) && cx <= T(A.nx_f - 1))) cy = cx = T(0);  // NaN / inf: memory safety
+        if (!(cy >= T(0) && cy <= T(A.ny_f - 1) && cx >= T(0) && cx <= T(A.nx_f - 1))) {
+            t.nan = cy != cy || cx != cx;  // NaN, or +-inf through wrap_coord (inf - inf); 'constant' +-inf: t.zero
+            cy = cx = T(0);                // memory safety
+        }
         locate_general<T, ORDER>(t, cy, cx);
         return t;
     }

@@ -701,7 +701,13 @@ class Engine:
                                                field.ny_f, field.nx_f, 1, self._ptr(field.lin), None), self.lib)
 
     def sample(self, field: PackedField, pos_x, pos_y, level=0, interp_order=1, row0=0, ny_global=None):
-        """tools.xr_map_coordinates for (u, v) of one time level at positions (ny, nx) in degrees."""
+        """tools.xr_map_coordinates for (u, v) of one time level at positions (ny, nx) in degrees.
+
+        Positions that are not finite (``lc_sample`` in include/lcs_hip.h; every order, both dtypes): on an interior
+        ('wrap') row a NaN or infinite coordinate gives NaN; on one of the first / last ``interp_order`` global rows
+        ('constant') an infinite coordinate is outside the field and gives exactly 0, a NaN coordinate gives NaN unless the
+        other coordinate is outside.  The finite positions of the same call are not affected.  scipy itself answers 0 for a
+        NaN coordinate (an undefined float-to-integer cast); this departs from it on purpose."""
         _check_order(field, interp_order)
         self._check_planes(field)
         self._planes64(field)
