@@ -1,4 +1,4 @@
 """``from LagrangianCoherence.LCS.tools import ...`` -- the hot-path helpers, HIP-backed."""
-from lagrangiancoherence_amd.tools import (derivative_spherical_coords, dilate_ridges, distance_to_ridges, filter_ridges,  # noqa: F401
-                                           find_ridges_spherical_hessian, fourth_order_derivative, skeletonize_ridges,
-                                           xr_map_coordinates)
+from lagrangiancoherence_amd.tools import (above_local_threshold, derivative_spherical_coords, dilate_ridges,  # noqa: F401
+                                           distance_to_ridges, filter_ridges, find_ridges_spherical_hessian,
+                                           fourth_order_derivative, skeletonize_ridges, threshold_local, xr_map_coordinates)

@@ -782,6 +782,47 @@ typedef struct lc_morph_args {
 } lc_morph_args;
 int lc_mask_morphology(lc_ctx *ctx, const lc_morph_args *args);
 
+/* ---- adaptive local threshold (threshold_local, above_local_threshold) ------------------
+ * The other half of the driver's result, its "local strain" area (LCS/area_of_influence.py:194-199):
+ *   local_thresh = threshold_local(ftle_local.values, block_size=301, offset=-.8);  binary_local = ftle_local > local_thresh
+ * skimage.filters.threshold_local with its defaults is scipy.ndimage.gaussian_filter(f, sigma, mode='reflect') - offset with
+ * sigma = (block_size - 1) / 6 and scipy's radius int(4 sigma + 0.5): block 301 is sigma 50, radius 200.  Both entry points
+ * were added at LC_VERSION 104 without a bump: nothing that existed changed.  n_members independent planes [n_members][ny*nx]
+ * per call, every launch for all of them; a plane is smoothed on its own.
+ *
+ *   f              `dtype` elements, LC_F32 or LC_F64; float32 is widened to float64 where it is read: the results are those of
+ *                  the widened field bit for bit
+ *   sigma_y, sigma_x  the Gaussian's width along latitude / longitude in grid steps.  An axis with sigma <= 1e-15 is not
+ *                  filtered, as scipy skips it (both: threshold = f - offset).  Weights, radius, accumulation in double and
+ *                  the summation order are lc_gaussian_filter's (centre first, then the pairs from the outermost inwards):
+ *                  with offset 0, equal sigmas and float64 the threshold equals its result bit for bit.
+ *   cyclic         != 0: longitude is periodic (scipy mode 'wrap' on that axis) instead of reflected; latitude is always
+ *                  reflected.  Either rule holds at any distance: a radius many times the plane is legal.
+ *   threshold_out  float64 [n_members][ny*nx] or NULL: smooth - offset, one rounding
+ *   mask_out       uint8 [n_members][ny*nx] or NULL: 1 where f > threshold, else 0; a NaN on either side gives 0.  With only
+ *                  the mask wanted no threshold plane is written.
+ *   work           float64 [lc_local_threshold_work_elems(ny, nx, n_members)] scratch (0 elements for bad sizes): the planes
+ *                  between the two passes; may be NULL when at most one axis is filtered
+ * Refused with LC_EINVAL before any HIP call: a null context or argument structure, a wrong struct_size, a bad dtype or size, a
+ * plane of 2^31 points or more, a NaN sigma, an offset that is not finite, both outputs NULL, any overlap among f, work and the
+ * outputs; with LC_EUNSUPPORTED, as lc_gaussian_filter: a radius above 256.
+ * lc_ctx_last_threshold_kernel: the kernels of the last call joined by '+' ("" before the first call or for a null context).
+ * No kernel of this call waits for another workgroup. */
+size_t lc_local_threshold_work_elems(int ny, int nx, int n_members);
+typedef struct lc_local_threshold_args {
+    size_t struct_size; /* sizeof(lc_local_threshold_args): checked before any other field */
+    const void *f;
+    int dtype, ny, nx, n_members;
+    double sigma_y, sigma_x;
+    double offset;      /* finite */
+    int cyclic;
+    void *work;          /* float64 */
+    void *threshold_out; /* float64, or NULL */
+    void *mask_out;      /* uint8, or NULL */
+} lc_local_threshold_args;
+int lc_local_threshold(lc_ctx *ctx, const lc_local_threshold_args *args);
+const char *lc_ctx_last_threshold_kernel(const lc_ctx *ctx);
+
 /* ---- multi-GPU: halo exchange on RCCL ----------------------------------------
  * New (the reference is single-process).  One process per GPU,
  * seed rows block-partitioned, wind replicated; lc_advect needs no communication

@@ -185,6 +185,22 @@ PROTOTYPES["lc_morph_work_elems"] = (_sz, [_i, _i, _i])
 PROTOTYPES["lc_mask_morphology"] = (_i, [_vp, C.POINTER(MorphArgs)])
 
 
+class LocalThresholdArgs(C.Structure):
+    """``lc_local_threshold_args`` of include/lcs_hip.h, field for field."""
+    _fields_ = [("struct_size", _sz),
+                ("f", _vp),
+                ("dtype", _i), ("ny", _i), ("nx", _i), ("n_members", _i),
+                ("sigma_y", _d), ("sigma_x", _d),
+                ("offset", _d),
+                ("cyclic", _i),
+                ("work", _vp), ("threshold_out", _vp), ("mask_out", _vp)]
+
+
+PROTOTYPES["lc_local_threshold_work_elems"] = (_sz, [_i, _i, _i])
+PROTOTYPES["lc_local_threshold"] = (_i, [_vp, C.POINTER(LocalThresholdArgs)])
+PROTOTYPES["lc_ctx_last_threshold_kernel"] = (C.c_char_p, [_vp])
+
+
 
 class RidgesArgs(C.Structure):
     """``lc_ridges_args`` of include/lcs_hip.h, field for field."""

@@ -1,7 +1,8 @@
 // The separable Gaussian of scipy.ndimage.gaussian_filter (truncate=4.0, mode='reflect', accumulation in double, the
-// symmetric-kernel summation order of ni_filters.c), shared by api.hip (gauss_kernel: one plane, float32 / float64) and
-// ridges_batch.hip (gauss_planes_kernel: a stack of float64 planes): the weights, the reflection and the tap loop are
-// written once, here, so a plane smoothed by either kernel has the same bits.
+// symmetric-kernel summation order of ni_filters.c), shared by api.hip (gauss_kernel: one plane, float32 / float64),
+// ridges_batch.hip (gauss_planes_kernel: a stack of float64 planes) and threshold.hip (gauss_line_kernel: radii in the
+// hundreds, the lines staged in LDS): the weights, the reflection and the tap loop -- out of global memory and out of LDS --
+// are written once, here, so a plane smoothed by any of the kernels has the same bits.
 #pragma once
 #include <cmath>
 #include <vector>
@@ -54,6 +55,22 @@ __device__ __forceinline__ double gauss_taps(const T *__restrict__ in, int y, in
         acc += (lo + hi) * G.w[j];
     }
     return acc;
+}
+
+// The same sum for N output nodes of lines staged in LDS (threshold.hip: gauss_line_kernel): `centre` is the first node's own
+// sample, its neighbours along the axis lie STEP words apart (the boundary rule was resolved when the line was staged), node n
+// is NEXT words further on.  Centre first, then the pairs from the outermost inwards: node for node the arithmetic of
+// gauss_taps above, so a plane smoothed through LDS has gauss_kernel's bits.  No division, no modulo, no global load.
+template <int N, int STEP, int NEXT>
+__device__ __forceinline__ void gauss_taps_lds(const double *centre, const GaussW &G, double (&acc)[N]) {
+#pragma unroll
+    for (int n = 0; n < N; ++n) acc[n] = centre[n * NEXT] * G.w[0];
+    for (int j = G.radius; j >= 1; --j) {
+        const double w = G.w[j];
+        const double *lo = centre - j * STEP, *hi = centre + j * STEP;
+#pragma unroll
+        for (int n = 0; n < N; ++n) acc[n] += (lo[n * NEXT] + hi[n * NEXT]) * w;
+    }
 }
 
 }  // namespace

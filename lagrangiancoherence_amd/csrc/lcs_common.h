@@ -51,6 +51,7 @@ struct lc_ctx {
     // built-in defaults; depth 0: off).  Only with level_chunk = -1: an explicit level chunk is uniform chunks.
     int grade_chunk, grade_zone, grade_depth;
     const char *last_ridges_kernel;  // what the last lc_ridges_batch launched (lc_ctx_last_ridges_kernel)
+    const char *last_threshold_kernel;  // what the last lc_local_threshold launched (lc_ctx_last_threshold_kernel)
 #ifdef LCS_TIMELINE  // diagnostic build only: start / end stamps of the two-seed order-1 kernel's workgroups (lc_debug_read_timeline)
     unsigned long long *timeline_dev;
     size_t timeline_cap;  // records allocated

@@ -1159,6 +1159,56 @@ class Engine:
             dist, nearest = dist[0], nearest[0] if return_nearest else None
         return (dist, nearest) if return_nearest else dist
 
+    # ------------------------------------------------------------------ adaptive local threshold
+    _THRESHOLD_PLANES = ("threshold", "mask")
+
+    @property
+    def last_threshold_kernel(self) -> str:
+        """Names of the kernels the last :meth:`local_threshold` call launched (``lc_ctx_last_threshold_kernel``), joined by
+        ``+``."""
+        return self.lib.lc_ctx_last_threshold_kernel(self.ctx).decode()
+
+    def local_threshold(self, f, sigma, offset=0.0, cyclic=False, want=("threshold",)) -> dict:
+        """The Gaussian local threshold of ``skimage.filters.threshold_local`` and its comparison in one call
+        (``lc_local_threshold``; LCS/area_of_influence.py:194-199): ``threshold = scipy.ndimage.gaussian_filter(f, sigma,
+        mode='reflect') - offset`` and ``mask = f > threshold``.
+
+        ``f``: ``(ny, nx)`` or ``(n_members, ny, nx)``, an array or a device tensor (float32 / float64 kept, anything else
+        converted to float64; float32 is widened on the device), every plane smoothed on its own in the same launches.
+        ``sigma``: the Gaussian's width in grid steps, a scalar or ``(latitude, longitude)``; an axis with ``sigma <= 1e-15``
+        is not filtered; a radius ``int(4 sigma + 0.5)`` above 256 is refused.  ``cyclic``: longitude is periodic instead of
+        reflected.  Returns a dict of device tensors shaped like ``f`` for the names in ``want``: ``threshold`` (float64) and /
+        or ``mask`` (uint8: 1 where ``f > threshold``, 0 elsewhere and wherever either side is NaN).  With only the mask
+        wanted no threshold plane is written."""
+        want = tuple(want)
+        if not want or any(w not in self._THRESHOLD_PLANES for w in want):
+            raise ValueError(f"want {want!r}: a non-empty subset of {self._THRESHOLD_PLANES}")
+        sigma = np.asarray(sigma, dtype=np.float64)
+        if sigma.shape not in ((), (2,)):
+            raise ValueError("sigma: a scalar or (latitude, longitude)")
+        sy, sx = (float(s) for s in np.broadcast_to(sigma, (2,)))
+        m = self._planes(f)
+        n, ny, nx = (int(s) for s in m.shape)
+        torch = self.torch
+        out = {}
+        if "threshold" in want:
+            out["threshold"] = self._empty((n, ny, nx), np.float64)
+        if "mask" in want:
+            out["mask"] = torch.empty((n, ny, nx), dtype=torch.uint8, device=self.device)
+        a = _capi.LocalThresholdArgs(struct_size=C.sizeof(_capi.LocalThresholdArgs))
+        a.f, a.dtype = m.data_ptr(), _NP2LC[np.dtype(str(m.dtype).replace("torch.", ""))]
+        a.ny, a.nx, a.n_members = ny, nx, n
+        a.sigma_y, a.sigma_x, a.offset, a.cyclic = sy, sx, float(offset), int(bool(cyclic))
+        work = None
+        if sy > 1e-15 and sx > 1e-15:     # the planes between the two passes
+            work = self._empty((max(1, int(self.lib.lc_local_threshold_work_elems(ny, nx, n))),), np.float64)
+            a.work = work.data_ptr()
+        a.threshold_out = out["threshold"].data_ptr() if "threshold" in out else None
+        a.mask_out = out["mask"].data_ptr() if "mask" in out else None
+        self._use_current_stream()
+        _capi.check(self.lib.lc_local_threshold(self.ctx, C.byref(a)), self.lib)
+        return out if len(f.shape) == 3 else {k: v[0] for k, v in out.items()}
+
     # ------------------------------------------------------------------ thinning and dilating a mask
     THINNING_METHODS = ("guohall", "zhang")
     STRUCTURES = {1: 2 + 8 + 32 + 128, 2: 255}   # connectivity -> the neighbours of lc_morph_args.structure (N, E, S, W; all eight)

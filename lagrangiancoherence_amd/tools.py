@@ -12,6 +12,9 @@
 * ``skeletonize_ridges``            LCS/area_of_influence.py:207: ``skeletonize(ridges.values)``, the thinning between the Hessian
                                     mask and the filter (scikit-image there: the rule is defined here, see its docstring)
 * ``dilate_ridges``                 LCS/area_of_influence.py:233: ``binary_dilation(ridges.values)``
+* ``threshold_local``               LCS/area_of_influence.py:194-199: ``threshold_local(ftle_local.values, block_size=301,
+                                    offset=-.8)`` (scikit-image there: the Gaussian rule it documents is restated here), and
+                                    ``above_local_threshold``, that threshold and the driver's comparison with it in one call
 
 The remaining functions of that module (IDW regridding, harvesine, latlonsel) have no caller on the
 path.
@@ -24,7 +27,8 @@ from .dropin import _coord, _make, _to_np, get_engine
 from .engine import Engine, common_dtype
 
 __all__ = ["xr_map_coordinates", "fourth_order_derivative", "derivative_spherical_coords",
-           "find_ridges_spherical_hessian", "filter_ridges", "distance_to_ridges", "skeletonize_ridges", "dilate_ridges"]
+           "find_ridges_spherical_hessian", "filter_ridges", "distance_to_ridges", "skeletonize_ridges", "dilate_ridges",
+           "threshold_local", "above_local_threshold"]
 
 
 def xr_map_coordinates(da, new_x, new_y, isglobal=True, order=1):
@@ -331,3 +335,71 @@ def dilate_ridges(ridges, iterations=1, connectivity=1, cyclic=False, fill=0.0):
     was = (mask != 0) & ~torch.isnan(mask)
     added = torch.where(grown != 0, torch.ones_like(mask), torch.full_like(mask, float(fill)))
     return out(torch.where(was, mask, added))
+
+
+def _local_threshold(da, block_size, method, offset, mode, param, cyclic, want):
+    """What the two local-threshold functions share: skimage's argument rules, the field sorted as ``filter_ridges`` sorts it,
+    one ``Engine.local_threshold`` call, and the way back to the caller's class and dimension order."""
+    if isinstance(block_size, (int, np.integer)):
+        blocks = (int(block_size),) * 2
+    else:
+        blocks = tuple(block_size)
+        if len(blocks) != 2 or not all(isinstance(b, (int, np.integer)) for b in blocks):
+            raise ValueError(f"block_size {block_size!r}: an odd int or a (latitude, longitude) pair of odd ints")
+    if any(b % 2 == 0 for b in blocks):
+        raise ValueError(f"block_size {block_size!r}: must be odd (skimage.filters.threshold_local's rule)")
+    if any(b < 1 for b in blocks):
+        raise ValueError(f"block_size {block_size!r}: >= 1")
+    if method != 'gaussian':
+        raise NotImplementedError(f"method {method!r}: only 'gaussian' (skimage's default) runs on the device")
+    if mode != 'reflect':
+        raise NotImplementedError(f"mode {mode!r}: only 'reflect' (skimage's default); cyclic=True makes longitude periodic")
+    sigma = tuple((b - 1) / 6.0 for b in blocks) if param is None else param
+    dims = tuple(da.dims)
+    lead = [d for d in dims if d not in ("latitude", "longitude")]
+    if len(lead) > 1 or len(dims) - len(lead) != 2:
+        raise ValueError("da: dims (latitude, longitude) and at most one more")
+    order = (*lead, "latitude", "longitude")
+    lat, lon = _coord(da, "latitude"), _coord(da, "longitude")
+    ilat, ilon = np.argsort(lat, kind="stable"), np.argsort(lon, kind="stable")
+    v = np.asarray(da.transpose(*order).values)
+    v = v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)
+    v = np.ascontiguousarray(v[..., ilat, :][..., ilon])
+    coords = {"latitude": lat[ilat], "longitude": lon[ilon]}
+    if lead:
+        coords[lead[0]] = _coord(da, lead[0])
+    res = get_engine().local_threshold(v, sigma, offset=offset, cyclic=cyclic, want=(want,))[want]
+    res = _to_np(res)
+    res = res.astype(bool) if want == "mask" else res
+    return _make(da, res, order, coords, getattr(da, "name", None)).transpose(*dims)
+
+
+def threshold_local(da, block_size=3, method='gaussian', offset=0, mode='reflect', param=None, cval=0, cyclic=False):
+    """The adaptive threshold of ``skimage.filters.threshold_local`` on the device (``Engine.local_threshold``): the call
+    LCS/area_of_influence.py:194 makes, ``threshold_local(ftle_local.values, block_size=301, offset=-.8)``.  skimage's
+    signature plus ``cyclic``.
+
+    scikit-image is not a dependency of this project, so the rule is restated from its documented definition: with
+    ``method='gaussian'`` the threshold of a pixel is the Gaussian-weighted mean of its neighbourhood minus ``offset``, i.e.
+    ``scipy.ndimage.gaussian_filter(image, sigma, mode='reflect') - offset`` with ``sigma = (block_size - 1) / 6`` (or
+    ``param``, when given), truncated at 4 sigma as scipy truncates it.  ``block_size`` is an odd int or a ``(latitude,
+    longitude)`` pair of odd ints -- an even one raises ``ValueError`` as in skimage -- and a block of 1 leaves its axis
+    unfiltered.  The other methods (``'mean'``, ``'median'``, ``'generic'``) and boundary modes raise
+    ``NotImplementedError``; ``cval`` belongs to ``mode='constant'`` and is accepted for the signature.  The radius
+    ``int(4 sigma + 0.5)`` may be many times the plane but not above 256 (``block_size`` up to 385).
+
+    ``da`` is a labelled array over ``latitude`` and ``longitude`` (sorted ascending here, as ``filter_ridges`` sorts), 2-D,
+    or 3-D with one more dimension (time, member): every plane then gets its own threshold -- never smoothed across time --
+    all of them in the same kernel launches.  ``cyclic``: longitude is periodic (a global axis) instead of reflected.
+
+    Returns the float64 threshold in the caller's class and dimension order."""
+    return _local_threshold(da, block_size, method, offset, mode, param, cyclic, "threshold")
+
+
+def above_local_threshold(da, block_size, offset=0, param=None, cyclic=False):
+    """``da > threshold_local(da, block_size, offset=offset, param=param, cyclic=cyclic)`` in one call: the driver's
+    ``binary_local = ftle_local > local_thresh`` (LCS/area_of_influence.py:195), the comparison fused into the Gaussian's last
+    pass so that no threshold plane is written or read back.  A NaN in ``da`` or in its threshold gives ``False``.
+
+    Returns the boolean mask in the caller's class and dimension order."""
+    return _local_threshold(da, block_size, 'gaussian', offset, 'reflect', param, cyclic, "mask")
