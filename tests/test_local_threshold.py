@@ -195,7 +195,12 @@ def _call(g):
 
 
 def _id(change):
-    return "-".join(f"{k}={getattr(v, 'value', v)}" for k, v in change.items())
+    """A pointer into _BLOCK shows as its offset: the block's address differs from process to process, a test's name must not."""
+    def show(v):
+        v = getattr(v, "value", v)
+        inside = isinstance(v, int) and 0 <= v - C.addressof(_BLOCK) < C.sizeof(_BLOCK)
+        return f"block+{v - C.addressof(_BLOCK)}" if inside else v
+    return "-".join(f"{k}={show(v)}" for k, v in change.items())
 
 
 @pytest.mark.parametrize("change, status, message", REFUSALS, ids=[_id(c) for c, _, _ in REFUSALS])
