@@ -283,6 +283,33 @@ int lc_field_pack(lc_ctx *ctx, const void *u_dev, const void *v_dev, int dtype,
                   void *ext_dev /* NULL, or lc_packed_elems(nt-1,..): also build the
                                    lc_field_extrapolate image of this order in the same call */);
 
+/* Deferred pack (additive: LC_VERSION stays 104).  lc_field_pack(LC_F32, order 1) with both images, of which only the levels
+ * the first launch of a fused lc_advect call reads are packed now -- packed_dev[0 .. first_levels] and ext_dev[0 .. first_levels - 1];
+ * first_levels <= 0: the default level chunk, 32 -- while the rest stays PENDING in the context: an lc_advect_ex call on exactly
+ * these images that runs the tall-patch two-seed kernel in more than one launch (one member, settls_order > 0, no
+ * trajectories, no outer clamp, t0 + its first launch's levels below the packed ones) packs them inside its own launches, in
+ * extra workgroups placed among the advecting ones: the pack streams memory that the advect kernel leaves idle.  EVERY other
+ * entry point that takes image pointers or packs completes the pending pack first with the stand-alone kernel, as do a
+ * second deferred pack (one pending pack per context), a change of the context's stream, lc_sync, lc_free, lc_memcpy_d2h,
+ * lc_copy_to_host, lc_copy_to_device and
+ * lc_ctx_destroy: nothing called through this interface reads an incomplete image.  The images are the same bits as
+ * lc_field_pack's.  u_dev and v_dev must stay alive and unchanged until the pack is complete (lc_ctx_pack_pending() == 0).  A
+ * caller that reads the images by other means (its own kernels, copies not made through this library) calls
+ * lc_ctx_flush_pack first.  A series that the first levels cover anyway (nt - 1 <= first_levels), and every call while
+ * deferring is switched off (lc_ctx_set_deferred_pack(ctx, 0), or LCS_DEFER_PACK=0 in the environment when the context is
+ * created), is packed at once, exactly as lc_field_pack does.
+ * lc_ctx_pack_pending: the first level of packed_dev not packed yet, 0 when nothing is pending.
+ * lc_ctx_set_deferred_pack_mix: of every `period` consecutive workgroups of a launch that carries a pack (a power of two, 32
+ * to 16384; 0, the default: chosen per launch so that a pack workgroup has 7 items or a few more) the last pack_blocks (8, 16 or 24; default 8) are pack workgroups; item_levels (2, 4 or 8; default 8):
+ * the time levels per item of theirs.  Measurement knobs: results do not depend on them.  No environment variables.
+ * A change of the context's stream completes the pack on the stream it began on and makes the new stream wait for it. */
+int lc_field_pack_deferred(lc_ctx *ctx, const void *u_dev, const void *v_dev, int nt, int ny_f, int nx_f, int first_levels,
+                           void *packed_dev, void *ext_dev);
+int lc_ctx_flush_pack(lc_ctx *ctx);
+int lc_ctx_pack_pending(const lc_ctx *ctx);
+int lc_ctx_set_deferred_pack(lc_ctx *ctx, int on);
+int lc_ctx_set_deferred_pack_mix(lc_ctx *ctx, int pack_blocks, int period, int item_levels); /* UNSTABLE: for measurements only, may change or go without a version bump */
+
 /* Optional third image for the SETTLS iterations: ext[t] = 2*packed[t] - packed[t+1],
  * t = 0..nt-2 (same layout, nt-1 levels).  Interpolation is linear in the field, so
  * one sample of ext[t] equals 2*interp(F[t]) - interp(F[t+1]) of trajectory.py:110-112

@@ -61,6 +61,11 @@ PROTOTYPES = {
     "lc_memcpy_d2h": (_i, [_vp, _vp, _vp, _sz]),
     "lc_packed_elems": (_sz, [_i, _i, _i]),
     "lc_field_pack": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "lc_field_pack_deferred": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "lc_ctx_flush_pack": (_i, [_vp]),
+    "lc_ctx_pack_pending": (_i, [_vp]),
+    "lc_ctx_set_deferred_pack": (_i, [_vp, _i]),
+    "lc_ctx_set_deferred_pack_mix": (_i, [_vp, _i, _i, _i]),
     "lc_field_extrapolate": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "lc_regrid_common_grid": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "lc_spectral_truncate": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

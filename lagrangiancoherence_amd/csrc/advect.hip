@@ -26,6 +26,7 @@
 
 #include "lcs_common.h"
 #include "launch_plan.h"
+#include "pack_node.h"
 
 namespace {
 
@@ -37,6 +38,18 @@ namespace {
 constexpr int TILE_W = 8;
 constexpr int TILE_H = 32;
 constexpr int BLOCK = TILE_W * TILE_H;
+
+// The part of a deferred pack (lc_field_pack_deferred; float32, order 1) that a fused launch carries in pack workgroups placed
+// among its advect workgroups (lcplan::pack_mix): the levels [t_lo, nt) of the images -- lin[t] from level lin_from on, ext[t]
+// while t + 1 < nt -- ALL above what any advect workgroup of the same launch reads (lcplan::launch_reach; advect_impl): the launch
+// boundary alone orders the writes before the reads of the next launch.  na = 0: no pack workgroups, the launch is today's.
+struct PackJob {
+    const float *u, *v;
+    float *lin, *ext;
+    int t_lo, lin_from, nt;
+    int na, shift;                 // advect blocks in every 2^shift blocks after the pole blocks (lcplan::PackMix)
+    int pack_blocks, item_levels;  // pack workgroups of the launch; levels per item (2, 4 or 8)
+};
 
 template <typename T>
 struct AdvectArgs {
@@ -99,9 +112,11 @@ struct AdvectArgs {
     lcplan::Grading grade;
     int grade_launch, grade_t0;              // this launch's index, the call's first level
     const T *grade_x_start, *grade_y_start;  // the call's start positions (NULL: the seed grid): where a range that begins at level 0 starts
+    PackJob pack;                            // two-seed order-1 kernel, tall patches: the pack workgroups of this launch (na = 0: none)
 #ifdef LCS_TIMELINE  // diagnostic build only
     unsigned long long *timeline;  // NULL, or [launch][block][4]: first stamp, last stamp, dispatch position, levels (lc_debug_read_timeline)
     int timeline_launch;
+    int timeline_grid;             // blocks per launch of the record: the launch WITHOUT pack workgroups (they leave no record; an advect workgroup's is at its pole blocks + dispatch position)
 #endif
 };
 
@@ -1819,6 +1834,29 @@ __device__ unsigned long long g_class[6];
 #define LCS_STAMP(i)
 #endif
 
+// A pack workgroup of a launch that carries part of a deferred pack (PackJob): the items p, p + P, ... of lcplan::pack_items,
+// 256 nodes of one padded row x LV levels each, with pack_fused_kernel's own per-node expressions (pack_node.h).  The item
+// index is uniform over the workgroup: its decomposition is scalar arithmetic.
+template <int LV>
+__device__ __forceinline__ void pack_items_run(const PackJob &J, int ny_f, int nx_f, int p) {
+    const lcplan::PackItems it = lcplan::pack_items(ny_f, nx_f, LC_PAD, J.nt - J.t_lo, LV);
+    const int pitch = nx_f + LC_PAD;
+    const size_t plane = (size_t)ny_f * nx_f, level = (size_t)(ny_f + LC_PAD) * pitch;
+    for (int item = p; item < it.n; item += J.pack_blocks) {
+        const int rest = item / it.xchunks, xc = item - rest * it.xchunks, g = rest / it.rows, py = rest - g * it.rows;
+        const int px = xc * 256 + (int)threadIdx.x;
+        if (px >= pitch) continue;
+        const int sx = mirror_index(px - LC_PAD_LO, nx_f), sy = mirror_index(py - LC_PAD_LO, ny_f);
+        pack_node_levels<float, LV>(J.u, J.v, J.lin, J.ext, plane, level, (size_t)sy * nx_f + sx, (size_t)py * pitch + px, J.t_lo + g * LV, J.nt,
+                                    J.lin_from);
+    }
+}
+__device__ __forceinline__ void pack_workgroup(const PackJob &J, int ny_f, int nx_f, int p) {
+    if (J.item_levels == 8) pack_items_run<8>(J, ny_f, nx_f, p);
+    else if (J.item_levels == 4) pack_items_run<4>(J, ny_f, nx_f, p);
+    else pack_items_run<2>(J, ny_f, nx_f, p);
+}
+
 // 98 SGPRs as compiled admit 6 workgroups per CU (MI355X_MICROARCH.md: 97-112 -> 6); capped at 96 -> 7
 // (7.55 -> 7.31 ms on C3; 80 -> 8 workgroups measures the same as 96).
 constexpr int LDS2_NUM_SGPR = 96;
@@ -1883,6 +1921,13 @@ __global__ void __launch_bounds__(BLOCK, LDS2_MINWAVES) __attribute__((amdgpu_nu
     __shared__ __attribute__((aligned(16))) f4 s_tiles[BLOCK / 64][LT_ROWS * LT_PITCH];
     // PATCH_LINES: two slabs (alternating by level) of the workgroup's 16 x 32 longitudes and latitudes
     __shared__ __attribute__((aligned(16))) float s_slab[2][2][LINES ? 16 * SLAB_PITCH : 4];
+    if (MODE == PATCH_TALL && A0.pack.na > 0 && (int)blockIdx.x >= A0.pole_blocks) {   // a pack workgroup (PackJob) does its items and leaves
+        int p;
+        if (lcplan::pack_mix_block((int)blockIdx.x - A0.pole_blocks, A0.pack.na, A0.pack.shift, p)) {
+            pack_workgroup(A0.pack, A0.ny_f, A0.nx_f, p);
+            return;
+        }
+    }
     if (GROUP ? pole_block_group(A) : pole_block<float, POLE_LIN>(A)) return;
     // This workgroup's tile, levels [t0, t0 + nsteps) and start positions: the launch's -- or, with graded level counts (tall
     // patches without trajectories; launch_plan.h), those of its dispatch position: fewer levels towards the end of the
@@ -1890,8 +1935,11 @@ __global__ void __launch_bounds__(BLOCK, LDS2_MINWAVES) __attribute__((amdgpu_nu
     // first level.  An empty range stores nothing: its seeds' positions are where the previous launch (or the caller) left them.
     int tile_id, t0 = A.t0, nsteps = A.nsteps;
     const float *x_from = A.x_start, *y_from = A.y_start;
+    // d: the dispatch position.  In a launch that carries pack workgroups (tall patches; PackJob) it counts the advect
+    // workgroups only (the pack workgroups left at the kernel's top).
+    int d = (int)blockIdx.x - A.pole_blocks;
+    if (MODE == PATCH_TALL && A.pack.na > 0) lcplan::pack_mix_block(d, A.pack.na, A.pack.shift, d);
     if (MODE == PATCH_TALL && A.grade.n > 0) {
-        const int d = (int)blockIdx.x - A.pole_blocks;
         tile_id = lcplan::tile_of_block(lcplan::graded_slot(A.grade, A.grade_launch, d), A.ntiles, A.ntx, A.xcd_chunk, A.tile_order);
         if (tile_id >= A.ntiles) return;
         const lcplan::Range r = lcplan::graded_range(A.grade, A.grade_launch, d);
@@ -1901,16 +1949,17 @@ __global__ void __launch_bounds__(BLOCK, LDS2_MINWAVES) __attribute__((amdgpu_nu
         x_from = r.a == 0 ? A.grade_x_start : A.x_out;
         y_from = r.a == 0 ? A.grade_y_start : A.y_out;
     } else {
-        tile_id = xcd_tile_id(A);
+        tile_id = lcplan::tile_of_block(d, A.ntiles, A.ntx, A.xcd_chunk, A.tile_order);  // (xcd_tile_id of the dispatch position)
         if (tile_id >= A.ntiles) return;  // whole block
     }
     const int tyi = tile_id / A.ntx, txi = tile_id - tyi * A.ntx;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #ifdef LCS_TIMELINE
-    unsigned long long *const tl_rec = A.timeline ? A.timeline + ((size_t)A.timeline_launch * gridDim.x + blockIdx.x) * 4 : nullptr;
+    // (by dispatch position, not by blockIdx.x: a launch that carries pack workgroups has a larger grid than the record's)
+    unsigned long long *const tl_rec = A.timeline ? A.timeline + ((size_t)A.timeline_launch * A.timeline_grid + A.pole_blocks + d) * 4 : nullptr;
     if (tl_rec && threadIdx.x == 0) {
         tl_rec[0] = wall_clock64();
-        tl_rec[2] = blockIdx.x;
+        tl_rec[2] = (unsigned long long)(A.pole_blocks + d);
         tl_rec[3] = (unsigned long long)nsteps;
     }
 #endif
@@ -2602,6 +2651,7 @@ struct LdsLaunch<float, ORDER> {
             int g2;
             const int mode = two_seed_patch_grid(A, A.patch_mode < PATCH_PAIR, g2);  // (PATCH_PAIR is the ensemble's, above)
             A.tile_order = A.tile_order_two_seed;
+            if (A.pack.na > 0) g2 = A.pole_blocks + lcplan::pack_mix(g2 - A.pole_blocks, (1 << A.pack.shift) - A.pack.na, A.pack.shift).grid;  // (tall patches: advect_impl)
             if (mode == PATCH_LINES) return launch_by_k({LC_K4(LC_INSTANCE, advect_lds2_kernel, 2 /* PATCH_LINES */)}, g2, st, A);
             if (mode == PATCH_WIDE) return launch_by_k({LC_K4(LC_INSTANCE, advect_lds2_kernel, 1 /* PATCH_WIDE */)}, g2, st, A);
             return launch_by_k({   // PATCH_TALL = 0
@@ -4268,6 +4318,7 @@ int advect_impl(lc_ctx *ctx, const lc_advect_args &a, const AdvectCall &call) {
     const bool per_member = outer && call.series && n_members > 1;
     const int n_flags = per_member ? n_members : 1;
     if (outer) {
+        LC_FLUSH_PACK(ctx);   // (never carries a pending pack: completed before anything of this call is enqueued)
         // fused kernel first, with a flag that says whether the clamp ever moved a parcel; if not, per-point and
         // outer-product clamps coincide (both are no-ops) and the fused result IS the reference's
         LC_HIP_CHECK(hipMallocAsync((void **)&clamp_flag, n_flags * sizeof(unsigned), ctx->stream));
@@ -4376,12 +4427,14 @@ int advect_impl(lc_ctx *ctx, const lc_advect_args &a, const AdvectCall &call) {
     // groups, trajectories, the other patch modes, pole rows inside the tiles (their seeds go by the launch's uniform range,
     // so a workgroup may not leave early) -- keeps uniform chunks: GR.n = 0.
     lcplan::Grading GR{};
+    int tall_blocks = 0;   // advect workgroups of a launch of the tall-patch two-seed order-1 kernel on one member (0: another kernel)
     if constexpr (sizeof(T) == 4) {
         const bool tiles_have_poles = A.pole_blocks == 0 && (A.row0 < A.order || A.row0 + ny > A.ny_global - A.order);
         if (order == 1 && use_lds && n_members == 1 && order1_two_seed_applies(A, lds_mode)) {
             AdvectArgs<float> P = A;
             int g2 = 0;
             const int mode = two_seed_patch_grid(P, P.patch_mode < PATCH_PAIR, g2);
+            if (mode == PATCH_TALL) tall_blocks = g2 - A.pole_blocks;
             if (ctx->level_chunk < 0 && !outer && !a.traj_x && !tiles_have_poles && mode == PATCH_TALL) {
                 const int gchunk = ctx->grade_chunk > 0 ? ctx->grade_chunk : chunk;
                 const int zone = ctx->grade_zone >= 0 ? ctx->grade_zone : lcplan::GRADE_ZONE_PER_CU * ctx->n_cus;
@@ -4404,18 +4457,51 @@ int advect_impl(lc_ctx *ctx, const lc_advect_args &a, const AdvectCall &call) {
             if (ctx->timeline_dev) {
                 (void)hipMemsetAsync(ctx->timeline_dev, 0, recs * 4 * sizeof(unsigned long long), ctx->stream);
                 A.timeline = ctx->timeline_dev;
+                A.timeline_grid = g2;
                 ctx->timeline_launches = lcplan::n_chunks(total, chunk);
                 ctx->timeline_grid = g2;
             }
 #endif
         }
     }
-    for (int ci = 0, nci = lcplan::n_chunks(total, chunk); ci < nci; ++ci) {
+    // Deferred pack (lc_field_pack_deferred; pack.hip): a call of the tall-patch two-seed kernel on ONE member of the pending
+    // pack's own images, K > 0, no trajectories, no outer clamp, more than one launch, whose first launch stays below the first
+    // unpacked level, carries the rest of the pack in its launches -- launch i, before which lin[.. t0 + reach(i)] and
+    // ext[.. t0 + reach(i) - 1] are complete (lcplan::launch_reach), packs up to reach(i + 1) in pack workgroups among its
+    // advect workgroups (lcplan::pack_mix), all of it above what the launch itself reads.  Every other call completes the
+    // pack first and launches exactly what it launches without one.
+    const int nci = lcplan::n_chunks(total, chunk);
+    lcplan::PackMix mix{};
+    bool carries_pack = false;
+    if (ctx->pend.next > 0) {
+        const lc_pending_pack &pd = ctx->pend;
+        if constexpr (sizeof(T) == 4) {
+            mix = lcplan::pack_mix(tall_blocks, ctx->pack_share, lcplan::PACK_SHIFT_MIN);   // (any pack workgroups at all: the period is chosen per launch)
+            carries_pack = tall_blocks > 0 && mix.pack_blocks > 0 && K > 0 && !a.traj_x && !outer && nci > 1 && a.dtype == LC_F32 &&
+                           a.packed_lin == pd.lin && a.packed_ext == pd.ext && a.nt == pd.nt && a.ny_f == pd.ny_f && a.nx_f == pd.nx_f &&
+                           ctx->stream == pd.stream && a.t0 + lcplan::launch_reach(total, chunk, GR, 0) < pd.next;
+        }
+        if (!carries_pack) LC_FLUSH_PACK(ctx);
+    }
+    for (int ci = 0; ci < nci; ++ci) {
         const int s0 = lcplan::chunk_first(ci, chunk);
         AdvectArgs<T> C = A;
         C.t0 = a.t0 + s0;
         C.nsteps = lcplan::chunk_levels(ci, total, chunk);
         C.pair_l0 = s0;
+        if (carries_pack && ctx->pend.next > 0 && ci + 1 < nci) {
+            lc_pending_pack &pd = ctx->pend;
+            const int upto = lcplan::imin(pd.nt, a.t0 + lcplan::launch_reach(total, chunk, GR, ci + 1) + 1);  // first level of lin the NEXT launch does not need
+            if (upto > pd.next) {
+                // pack workgroups by the items of this launch's share (lcplan::pack_mix_for_items), or the period the context sets
+                const int items = lcplan::pack_items(pd.ny_f, pd.nx_f, LC_PAD, upto - (pd.next - 1), ctx->pack_item_levels).n;
+                mix = ctx->pack_period_shift > 0 ? lcplan::pack_mix(tall_blocks, ctx->pack_share, ctx->pack_period_shift)
+                                                 : lcplan::pack_mix_for_items(tall_blocks, ctx->pack_share, items);
+                if (mix.pack_blocks <= 0) mix = lcplan::pack_mix(tall_blocks, ctx->pack_share, lcplan::PACK_SHIFT_MIN);
+                C.pack = {pd.u, pd.v, pd.lin, pd.ext, pd.next - 1, pd.next, upto, mix.na, mix.shift, mix.pack_blocks, ctx->pack_item_levels};
+                pd.next = upto < pd.nt ? upto : 0;
+            }
+        }
         if (GR.n > 0) {
             C.grade = GR;
             C.grade_launch = ci;
@@ -4756,6 +4842,7 @@ extern "C" int lc_sample_raw(lc_ctx *ctx, const void *packed_lin, const void *pa
     LC_REQUIRE(row0 >= 0 && row0 + ny <= ny_global, "lc_sample: rows outside the global grid");
     LC_REQUIRE(lat_max > lat_min && lon_max > lon_min, "lc_sample: field coordinates must be ascending");
     LC_HIP_CHECK(hipSetDevice(ctx->device));
+    LC_FLUSH_PACK(ctx);
     const bool raw = raw_replaces_lin(u_raw, v_raw, dtype, interp_order);
     SampleCall c = {};
     c.src = {packed_lin, packed_cub, raw ? u_raw : nullptr, raw ? v_raw : nullptr};
@@ -4809,6 +4896,7 @@ extern "C" int lc_tracer_sample(lc_ctx *ctx, const lc_tracer_args *args) {
     LC_REQUIRE(a.lat_max > a.lat_min && a.lon_max > a.lon_min, "lc_tracer_sample: field coordinates must be ascending");
     LC_REQUIRE(!(a.mean1_out || a.mean2_out) || a.mean_count >= 1, "lc_tracer_sample: mean_count %d", a.mean_count);
     LC_HIP_CHECK(hipSetDevice(ctx->device));
+    LC_FLUSH_PACK(ctx);
     const bool raw = raw_replaces_lin(a.c1_raw, a.c2_raw, a.dtype, a.interp_order);
     const FieldSource src = {a.tracer_lin, a.tracer_cub, raw ? a.c1_raw : nullptr, raw ? a.c2_raw : nullptr};
     if (a.dtype == LC_F32) return tracer_impl<float>(ctx, a, src);

@@ -74,6 +74,12 @@ extern "C" int lc_ctx_create(int device, lc_ctx **out) {
     c->grade_chunk = 0;   // graded level counts: the by-size chunk, the built-in zone and depth (advect.hip; no environment variable)
     c->grade_zone = -1;
     c->grade_depth = -1;
+    c->pend = {};
+    c->defer_pack = 1;
+    if (const char *ev = getenv("LCS_DEFER_PACK")) c->defer_pack = ev[0] != '0';  // read once, here
+    c->pack_share = 8;   // (measured: profiles/deferred_pack/deferred_pack_ab.txt)
+    c->pack_period_shift = 0;   // by the pack's size (lcplan::pack_mix_for_items)
+    c->pack_item_levels = 8;
 #ifdef LCS_TIMELINE
     c->timeline_dev = nullptr;
     c->timeline_cap = 0;
@@ -251,6 +257,7 @@ static void host_ws_destroy(lc_ctx *ctx);  // (below, with the one-call host rou
 extern "C" int lc_ctx_destroy(lc_ctx *ctx) {
     if (!ctx) return LC_OK;
     (void)hipSetDevice(ctx->device);
+    (void)lc_pack_flush(ctx);
     (void)hipStreamSynchronize(ctx->stream);
     lc_trunc_cache_free(ctx->trunc);
     lc_host_xfer::release(ctx->xfer);
@@ -266,12 +273,20 @@ extern "C" int lc_ctx_destroy(lc_ctx *ctx) {
 
 extern "C" int lc_ctx_set_stream(lc_ctx *ctx, void *hip_stream) {
     LC_REQUIRE(ctx, "lc_ctx_set_stream: null context");
+    if (ctx->pend.next > 0 && (hipStream_t)hip_stream != ctx->pend.stream) {
+        const int rc = lc_pack_flush_before(ctx, (hipStream_t)hip_stream);
+        if (rc != LC_OK) return rc;
+    }
     ctx->stream = (hipStream_t)hip_stream;  // NULL is the legacy default stream, a valid stream
     return LC_OK;
 }
 
 extern "C" int lc_ctx_use_own_stream(lc_ctx *ctx) {
     LC_REQUIRE(ctx, "lc_ctx_use_own_stream: null context");
+    if (ctx->pend.next > 0 && ctx->own_stream != ctx->pend.stream) {
+        const int rc = lc_pack_flush_before(ctx, ctx->own_stream);
+        if (rc != LC_OK) return rc;
+    }
     ctx->stream = ctx->own_stream;
     return LC_OK;
 }
@@ -279,6 +294,7 @@ extern "C" int lc_ctx_use_own_stream(lc_ctx *ctx) {
 extern "C" int lc_sync(lc_ctx *ctx) {
     LC_REQUIRE(ctx, "lc_sync: null context");
     LC_HIP_CHECK(hipSetDevice(ctx->device));
+    LC_FLUSH_PACK(ctx);
     LC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return LC_OK;
 }
@@ -300,6 +316,7 @@ extern "C" int lc_free(lc_ctx *ctx, void *dev) {
     LC_REQUIRE(ctx, "lc_free: null context");
     if (!dev) return LC_OK;
     LC_HIP_CHECK(hipSetDevice(ctx->device));
+    LC_FLUSH_PACK(ctx);
     LC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     LC_HIP_CHECK(hipFree(dev));
     return LC_OK;
@@ -316,6 +333,7 @@ extern "C" int lc_memcpy_h2d(lc_ctx *ctx, void *dev_dst, const void *host_src, s
 extern "C" int lc_memcpy_d2h(lc_ctx *ctx, void *host_dst, const void *dev_src, size_t bytes) {
     LC_REQUIRE(ctx && (bytes == 0 || (host_dst && dev_src)), "lc_memcpy_d2h: null argument");
     LC_HIP_CHECK(hipSetDevice(ctx->device));
+    LC_FLUSH_PACK(ctx);
     LC_HIP_CHECK(hipMemcpyAsync(host_dst, dev_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
     LC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return LC_OK;
@@ -343,6 +361,7 @@ extern "C" int lc_field_pack(lc_ctx *ctx, const void *u_dev, const void *v_dev, 
         return LC_EUNSUPPORTED;
     }
     LC_HIP_CHECK(hipSetDevice(ctx->device));
+    LC_FLUSH_PACK(ctx);
     LC_REQUIRE(ext_dev != packed_dev, "lc_field_pack: ext_dev must not alias packed_dev");
     return lc_launch_pack(ctx, u_dev, v_dev, dtype, nt, ny_f, nx_f, interp_order, packed_dev, ext_dev);
 }
@@ -354,6 +373,7 @@ extern "C" int lc_field_extrapolate(lc_ctx *ctx, const void *packed_dev, int dty
     LC_REQUIRE(packed_dev && ext_dev && packed_dev != ext_dev, "lc_field_extrapolate: bad pointers");
     LC_REQUIRE(nt >= 2 && ny_f >= 4 && nx_f >= 4, "lc_field_extrapolate: field too small");
     LC_HIP_CHECK(hipSetDevice(ctx->device));
+    LC_FLUSH_PACK(ctx);
     return lc_launch_extrapolate(ctx, packed_dev, dtype, nt, ny_f, nx_f, ext_dev);
 }
 
@@ -513,6 +533,7 @@ static int staged_copy(lc_ctx *ctx, const char *who, void *dst, const void *src,
     LC_REQUIRE(ctx && (bytes == 0 || (dst && src)), "%s: null pointer", who);
     if (!bytes) return LC_OK;
     LC_HIP_CHECK(hipSetDevice(ctx->device));
+    LC_FLUSH_PACK(ctx);   // (to_host may read an image; to_device may overwrite the planes a pending pack still reads)
     lc_host_xfer *hx = host_xfer_of(ctx);
     if (!hx) {
         LC_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, ctx->stream));
@@ -742,6 +763,7 @@ extern "C" int lc_lcs_host(lc_ctx *ctx, const void *u_host, const void *v_host, 
         return LC_EUNSUPPORTED;
     }
     LC_HIP_CHECK(hipSetDevice(ctx->device));
+    LC_FLUSH_PACK(ctx);
     hipStream_t st = ctx->stream;
     const size_t es = dtype == LC_F32 ? 4 : 8;
     const size_t lvl_bytes = (size_t)ny_f * nx_f * es, sbytes = (size_t)ny * nx * es, tbytes = sbytes * (size_t)(nsteps + 1);
@@ -908,6 +930,7 @@ extern "C" int lc_lcs_global_host(lc_ctx *ctx, const void *u_host, const void *v
         return LC_EUNSUPPORTED;
     }
     LC_HIP_CHECK(hipSetDevice(ctx->device));
+    LC_FLUSH_PACK(ctx);
     hipStream_t st = ctx->stream;
     const size_t es_in = dtype == LC_F32 ? 4 : 8;
     const size_t nin = (size_t)nt * ny_f * nx_f;

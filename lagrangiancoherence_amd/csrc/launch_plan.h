@@ -244,6 +244,84 @@ LCP_HD Range graded_range(const Grading &g, int launch, int d) {
     return r;
 }
 
+// ---- how far a launch reaches (deferred pack) ---------------------------------------------------------------------------------
+// The highest level index, relative to the call's first level, that any workgroup of launch i may read: the end of the
+// longest range of the launch.  Uniform chunks: min(total, (i + 1) chunk).  Graded: the maximum of graded_bound(g, i + 1, slot)
+// over the slots -- the cuts only pull a boundary inwards, except at the LAST boundary (i + 1 = n - 1), which the slots that end
+// the last launch's dispatch order push outwards by up to `depth` (the slot at its very end by all of it, and a slot is in one
+// zone only: nothing is taken off again).  A level's step reads lin[t] and ext[t]; the pole rows' two-sample path
+// (advect_seed<float, 1, false> on A.lin, in the pole workgroups and in tiles that hold pole rows) reads lin[t + 1] as well: a
+// launch needs lin[0 .. reach] INCLUSIVE and ext[0 .. reach - 1] of the levels counted from the call's t0.
+// Checked against every slot's range, exhaustively over small cases: tests/c/launch_reach_test.cpp.
+LCP_HD int launch_reach(int total, int chunk, const Grading &g, int i) {
+    if (g.n <= 0 || g.zone <= 0) return imin(total, (i + 1) * chunk);
+    if (i + 1 >= g.n) return g.total;
+    return imin(g.total, (i + 1) * g.chunk + (i + 1 == g.n - 1 ? g.depth : 0));
+}
+
+// ---- pack workgroups among the advect workgroups of a launch (deferred pack) -------------------------------------------------
+// A launch that carries part of a deferred pack grows by pack workgroups placed AMONG the advect ones in dispatch order: of
+// every 2^shift consecutive blocks after the pole blocks (the period: 32 .. 16384) the first `na` advect, the last 2^shift - na
+// (8, 16 or 24) pack.  na is a multiple of 8, so the advect block at dispatch position d sits at a block index b with b % 8 == d % 8: it keeps its XCD, and
+// the rotation argument of the graded level counts (rot_i a multiple of 8) holds as it is.  d counts advect blocks only: it is
+// what tile_of_block and the grading see.  The period that the advect blocks do not fill ends with them (no pack blocks after
+// the last advect block: every block of the grid is one or the other, none is idle).
+constexpr int PACK_SHIFT_MIN = 5, PACK_SHIFT_MAX = 14;
+struct PackMix {
+    int shift;        // log2 of the period
+    int na;           // advect blocks per period
+    int pack_blocks;  // pack workgroups of the launch
+    int grid;         // blocks of the launch without the pole blocks
+};
+LCP_HD PackMix pack_mix(int adv_blocks, int pack_per_period, int shift) {
+    PackMix m;
+    m.shift = shift;
+    m.na = (1 << shift) - pack_per_period;
+    const int periods = adv_blocks / m.na;
+    m.pack_blocks = periods * pack_per_period;
+    m.grid = adv_blocks + m.pack_blocks;
+    return m;
+}
+// The period by the pack's size.  What a pack workgroup costs the launch is per WORKGROUP, not per byte (about as much as an
+// advect workgroup, whatever it moves: profiles/deferred_pack/deferred_pack_ab.txt), and one that is dispatched late with many
+// items outlives the launch: so the number of pack workgroups follows the ITEMS -- about PACK_ITEMS_PER_WG each -- and not
+// the advect grid: the shortest period that gives no more than items / PACK_ITEMS_PER_WG of them (at least one group of 8).
+constexpr int PACK_ITEMS_PER_WG = 7;   // (the headline call then takes the measured period of 64: 7.4 items each)
+LCP_HD PackMix pack_mix_for_items(int adv_blocks, int pack_per_period, int items) {
+    const int want = imax(items / PACK_ITEMS_PER_WG, pack_per_period);
+    PackMix m = pack_mix(adv_blocks, pack_per_period, PACK_SHIFT_MIN);
+    for (int s = PACK_SHIFT_MIN + 1; s <= PACK_SHIFT_MAX && m.pack_blocks > want; ++s) {
+        const PackMix next = pack_mix(adv_blocks, pack_per_period, s);
+        if (next.pack_blocks <= 0) break;
+        m = next;
+    }
+    return m;
+}
+// Block b (blockIdx.x minus the pole blocks) of such a launch: true = the idx-th pack workgroup, false = the advect workgroup
+// at dispatch position idx.
+LCP_HD bool pack_mix_block(int b, int na, int shift, int &idx) {
+    const int q = b >> shift, r = b & ((1 << shift) - 1);
+    if (r >= na) {
+        idx = q * ((1 << shift) - na) + (r - na);
+        return true;
+    }
+    idx = q * na + r;
+    return false;
+}
+// Items of the pack workgroups: 256 nodes of one padded row x item_levels levels, the x chunk running fastest, then the padded
+// row, then the level group.  Workgroup p of P takes the items p, p + P, p + 2 P, ...
+struct PackItems {
+    int xchunks, rows, groups, n;
+};
+LCP_HD PackItems pack_items(int ny_f, int nx_f, int pad, int levels, int item_levels) {
+    PackItems it;
+    it.xchunks = (nx_f + pad + 255) / 256;
+    it.rows = ny_f + pad;
+    it.groups = (levels + item_levels - 1) / item_levels;
+    it.n = it.xchunks * it.rows * it.groups;
+    return it;
+}
+
 // ---- member groups (lc_advect_batch, two members per lane) ---------------------------------------------------------------
 // Members 2p and 2p+1 share a lane.  A group's LEVEL window is [0, nsteps + (g - 1) d): member q of the group steps at the
 // window levels [q d, q d + nsteps) (d = t0_stride).  Grouping only pays (and is only correct as implemented) when the

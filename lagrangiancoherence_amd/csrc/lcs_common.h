@@ -10,6 +10,19 @@
 struct lc_trunc_cache;                       // preprocess.hip: spectral-truncation operators of the last (nlat, nlon, T)
 void lc_trunc_cache_free(lc_trunc_cache *c);
 
+// The rest of a deferred pack (lc_field_pack_deferred; float32, order 1, both images): lin[0, next) and ext[0, next - 1) are
+// complete, the levels from there to the series' end are packed by the eligible advect call's own launches or by lc_pack_flush.
+struct lc_pending_pack {
+    const float *u, *v;
+    float *lin, *ext;
+    int nt, ny_f, nx_f;
+    int next;            // first level of lin not packed yet; 0: nothing pending
+    hipStream_t stream;  // the stream the first levels were packed on: where a flush completes the rest
+};
+
+// EVERY entry point that takes image pointers, packs, copies device memory or changes the context's stream begins with
+// LC_FLUSH_PACK(ctx) (below) -- lc_advect_ex alone decides for itself (advect_impl) --: a pending pack (`pend`) is otherwise read
+// half written.  A new entry point of that kind must do the same.
 struct lc_ctx {
     int device;
     int n_cus;           // compute units of the device (the fused prefilter sizes its last round by it)
@@ -52,6 +65,9 @@ struct lc_ctx {
     int grade_chunk, grade_zone, grade_depth;
     const char *last_ridges_kernel;  // what the last lc_ridges_batch launched (lc_ctx_last_ridges_kernel)
     const char *last_threshold_kernel;  // what the last lc_local_threshold launched (lc_ctx_last_threshold_kernel)
+    lc_pending_pack pend;       // the context's one pending pack (pack.hip)
+    int defer_pack;             // lc_field_pack_deferred defers (1, default) or packs the whole series at once as lc_field_pack does (0; LCS_DEFER_PACK at creation / lc_ctx_set_deferred_pack)
+    int pack_share, pack_period_shift, pack_item_levels;  // a launch that carries a pack: pack workgroups (8 / 16 / 24) in every 2^shift blocks (32 .. 16384; shift 0, the default: by the pack's size), levels per item of theirs (2 / 4 / 8): lc_ctx_set_deferred_pack_mix
 #ifdef LCS_TIMELINE  // diagnostic build only: start / end stamps of the two-seed order-1 kernel's workgroups (lc_debug_read_timeline)
     unsigned long long *timeline_dev;
     size_t timeline_cap;  // records allocated
@@ -150,3 +166,12 @@ static inline lc_advect_args lc_whole_grid_args(const lc_dev_wind &w, const lc_d
 int lc_launch_pack(lc_ctx *ctx, const void *u, const void *v, int dtype, int nt, int ny_f, int nx_f,
                    int order, void *packed, void *ext);
 int lc_launch_extrapolate(lc_ctx *ctx, const void *img, int dtype, int nt, int ny_f, int nx_f, void *ext);
+int lc_pack_flush(lc_ctx *ctx);  // completes the context's pending pack, if any, with the stand-alone kernel on its stream
+// ... and makes `next`, the stream the context is about to work on, wait for it: the pack was begun on another stream, whose
+// order the caller's own waits (recorded before this moment) do not cover
+int lc_pack_flush_before(lc_ctx *ctx, hipStream_t next);
+#define LC_FLUSH_PACK(ctx)                  \
+    do {                                    \
+        const int _rc = lc_pack_flush(ctx); \
+        if (_rc != LC_OK) return _rc;       \
+    } while (0)

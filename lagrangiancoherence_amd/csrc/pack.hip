@@ -13,15 +13,9 @@
 
 #include "lcs_common.h"
 #include "launch_plan.h"
+#include "pack_node.h"
 
 namespace {
-
-__device__ __forceinline__ int mirror_index(int i, int n) {
-    // scipy ni_interpolation.c tap mirroring; here |i| never exceeds n+1
-    if (i < 0) i = -i;
-    if (i > n - 1) i = 2 * (n - 1) - i;
-    return i;
-}
 
 // interior nodes: packed[t][y+1][x+1] = {u[t][y][x], v[t][y][x]}
 // TIN: the element type of the raw planes (float for LC_F64_WIND_F32: a float32 wind whose spline coefficients scipy forms
@@ -850,15 +844,13 @@ __global__ void __launch_bounds__(64) prefilter_rows_stream_kernel(double *__res
 // A block takes 256 consecutive nodes of one padded row of one level (grid: x chunks, padded rows, levels): no
 // integer division anywhere -- the first form, one flat index per node decomposed with two 64-bit divisions, was bound
 // by that arithmetic, not by memory (C3: 0.60 ms for 3.4 GB; config 2 in float64 with both images: 2.5 ms for 10 GB).
-// Non-temporal stores of the images (nothing reads them again before the advect kernel streams them): config 2's float64
-// pack 2.07 -> 1.95 ms, C3's 0.54 -> 0.50 (profiles/r03; the plain stores of that A/B: tools/experiments/advect_r06_compile_time_forks.patch).
-#define LCS_PACK_STORE(ptr, val) __builtin_nontemporal_store(val, ptr)
 // A thread walks PACK_LV consecutive time levels of its node and carries level t+1 forward, so every raw level is read
 // ONCE (plus one level in PACK_LV at the chunk's end) instead of twice -- as F[t] for lin[t] / ext[t] and again as F[t+1]
 // for ext[t-1]: float64 config 2 moved 13.9 GB for 10.1 GB compulsory that way (profiles/r03/c2_pmc_traffic.json).  The
 // loads of a chunk are issued together (static trip count), then the stores.
 // lin == NULL: the fused-level image alone (lc_field_pack(order 1, packed_dev = NULL): the caller samples order 1 from
 // the raw planes, lc_advect_ex).
+// (the per-node expressions: pack_node.h, shared with the pack workgroups of a fused advect launch)
 constexpr int PACK_LV = 2;
 template <typename T>
 __global__ void __launch_bounds__(256) pack_fused_kernel(const T *__restrict__ u, const T *__restrict__ v, T *__restrict__ lin,
@@ -868,27 +860,11 @@ __global__ void __launch_bounds__(256) pack_fused_kernel(const T *__restrict__ u
     if (px >= pitch) return;
     const size_t plane = (size_t)ny * nx, level = (size_t)(ny + LC_PAD) * pitch;
     const int sx = mirror_index(px - LC_PAD_LO, nx);
-    typedef T T2 __attribute__((ext_vector_type(2)));
     for (int py = blockIdx.y; py < ny + LC_PAD; py += gridDim.y) {     // (the grid covers every row and level chunk unless
         const int sy = mirror_index(py - LC_PAD_LO, ny);               //  a dimension exceeds 65535 blocks)
         const size_t so = (size_t)sy * nx + sx, po = (size_t)py * pitch + px;
-        for (int t0 = blockIdx.z * PACK_LV; t0 < nt; t0 += gridDim.z * PACK_LV) {
-            T a[PACK_LV + 1], b[PACK_LV + 1];
-#pragma unroll
-            for (int q = 0; q <= PACK_LV; ++q) {
-                const size_t t = (size_t)min(t0 + q, nt - 1);          // (past the series: the last level again, never used)
-                a[q] = u[t * plane + so];
-                b[q] = v[t * plane + so];
-            }
-#pragma unroll
-            for (int q = 0; q < PACK_LV; ++q) {
-                const int t = t0 + q;
-                if (t >= nt) break;
-                if (lin) LCS_PACK_STORE((T2 *)(lin + ((size_t)t * level + po) * 2), ((T2){a[q], b[q]}));
-                if (ext && t + 1 < nt)
-                    LCS_PACK_STORE((T2 *)(ext + ((size_t)t * level + po) * 2), ((T2){T(2) * a[q] - a[q + 1], T(2) * b[q] - b[q + 1]}));
-            }
-        }
+        for (int t0 = blockIdx.z * PACK_LV; t0 < nt; t0 += gridDim.z * PACK_LV)
+            pack_node_levels<T, PACK_LV>(u, v, lin, ext, plane, level, so, po, t0, nt, 0);
     }
 }
 
@@ -1056,15 +1032,23 @@ static FirTaps cubic_fir_taps() {
     return T;
 }
 
+// pack_fused_kernel over the levels [t_lo, nt) of a series: lin[t_lo .. nt - 1] and ext[t_lo .. nt - 2], as the series that
+// begins at level t_lo (the kernel and its arguments are those of a whole pack)
+template <typename T>
+static void launch_pack_fused(hipStream_t st, const T *u, const T *v, T *lin, T *ext, int nt, int ny, int nx, int t_lo) {
+    const size_t plane = (size_t)ny * nx * t_lo, image = lc_level_elems(ny, nx) * (size_t)t_lo;
+    // (grid.y and grid.z are capped at 65535 blocks: the kernel loops over what is beyond)
+    const int nchunk = (nt - t_lo + PACK_LV - 1) / PACK_LV;
+    hipLaunchKernelGGL(pack_fused_kernel<T>, dim3((nx + LC_PAD + 255) / 256, ny + LC_PAD < 65535 ? ny + LC_PAD : 65535, nchunk < 65535 ? nchunk : 65535),
+                       dim3(256), 0, st, u + plane, v + plane, lin ? lin + image : lin, ext ? ext + image : ext, nt - t_lo, ny, nx);
+}
+
 template <typename T, typename TIN = T>
 int pack_impl(lc_ctx *ctx, const TIN *u, const TIN *v, int nt, int ny, int nx, int order, T *packed, T *ext) {
     const size_t nodes = (size_t)nt * ny * nx;
     const int threads = 256;
     if constexpr (std::is_same<T, TIN>::value) if (order == 1) {
-        // (grid.y and grid.z are capped at 65535 blocks: the kernel loops over what is beyond)
-        const int nchunk = (nt + PACK_LV - 1) / PACK_LV;
-        hipLaunchKernelGGL(pack_fused_kernel<T>, dim3((nx + LC_PAD + 255) / 256, ny + LC_PAD < 65535 ? ny + LC_PAD : 65535, nchunk < 65535 ? nchunk : 65535),
-                           dim3(threads), 0, ctx->stream, u, v, packed, ext, nt, ny, nx);
+        launch_pack_fused<T>(ctx->stream, u, v, packed, ext, nt, ny, nx, 0);
         ctx->last_pack_kernel = "pack_fused_kernel";
         LC_HIP_CHECK(hipGetLastError());
         return LC_OK;
@@ -1174,4 +1158,81 @@ int lc_launch_pack(lc_ctx *ctx, const void *u, const void *v, int dtype, int nt,
         return pack_impl<double, float>(ctx, (const float *)u, (const float *)v, nt, ny_f, nx_f, order, (double *)packed, (double *)ext);
     return pack_impl<double>(ctx, (const double *)u, (const double *)v, nt, ny_f, nx_f, order, (double *)packed,
                              (double *)ext);
+}
+
+// ---- deferred pack (float32, order 1, both images) ---------------------------------------------------------------------------
+// lc_field_pack_deferred packs the levels the first launch of a fused advect call reads and leaves the rest PENDING in the
+// context: the eligible lc_advect call on these images packs them inside its own launches (advect.hip), everything else
+// completes them first with the stand-alone kernel (lc_pack_flush: every entry point that takes image pointers or packs,
+// a change of stream, lc_sync, lc_free, lc_ctx_destroy).  The C ABI therefore never reads an incomplete image.
+int lc_pack_flush(lc_ctx *ctx) {
+    lc_pending_pack &P = ctx->pend;
+    if (P.next <= 0) return LC_OK;
+    const int next = P.next;
+    P.next = 0;
+    // from level next - 1 on: ext[next - 1] is the first level of ext that is missing; lin[next - 1] is written again, the same bits
+    // (nothing reads it meanwhile: the flush is ordered on the pack's stream like everything else that touches the images)
+    launch_pack_fused<float>(P.stream, P.u, P.v, P.lin, P.ext, P.nt, P.ny_f, P.nx_f, next - 1);
+    LC_HIP_CHECK(hipGetLastError());
+    return LC_OK;
+}
+
+int lc_pack_flush_before(lc_ctx *ctx, hipStream_t next) {
+    if (ctx->pend.next <= 0) return LC_OK;
+    const hipStream_t began = ctx->pend.stream;
+    const int rc = lc_pack_flush(ctx);
+    if (rc != LC_OK || began == next) return rc;
+    hipEvent_t done;
+    LC_HIP_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(done, began);
+    if (e == hipSuccess) e = hipStreamWaitEvent(next, done, 0);
+    (void)hipEventDestroy(done);   // (the wait holds what it needs of the event)
+    LC_HIP_CHECK(e);
+    return LC_OK;
+}
+
+extern "C" int lc_ctx_flush_pack(lc_ctx *ctx) {
+    LC_REQUIRE(ctx, "lc_ctx_flush_pack: null context");
+    LC_HIP_CHECK(hipSetDevice(ctx->device));
+    return lc_pack_flush(ctx);
+}
+
+extern "C" int lc_ctx_pack_pending(const lc_ctx *ctx) { return ctx ? ctx->pend.next : 0; }
+
+extern "C" int lc_ctx_set_deferred_pack(lc_ctx *ctx, int on) {
+    LC_REQUIRE(ctx, "lc_ctx_set_deferred_pack: null context");
+    ctx->defer_pack = on != 0;
+    return LC_OK;
+}
+
+extern "C" int lc_ctx_set_deferred_pack_mix(lc_ctx *ctx, int pack_blocks, int period, int item_levels) {
+    LC_REQUIRE(ctx, "lc_ctx_set_deferred_pack_mix: null context");
+    LC_REQUIRE(pack_blocks == 8 || pack_blocks == 16 || pack_blocks == 24, "lc_ctx_set_deferred_pack_mix: 8, 16 or 24 pack workgroups per period (got %d)", pack_blocks);
+    int shift = 0;   // period 0: by the pack's size
+    for (int s = lcplan::PACK_SHIFT_MIN; s <= lcplan::PACK_SHIFT_MAX; ++s)
+        if (period == 1 << s) shift = s;
+    LC_REQUIRE(shift > 0 || period == 0, "lc_ctx_set_deferred_pack_mix: the period is 0 (by size) or a power of two, 32 to 16384 (got %d)", period);
+    LC_REQUIRE(item_levels == 2 || item_levels == 4 || item_levels == 8, "lc_ctx_set_deferred_pack_mix: 2, 4 or 8 levels per item (got %d)", item_levels);
+    ctx->pack_share = pack_blocks;
+    ctx->pack_period_shift = shift;
+    ctx->pack_item_levels = item_levels;
+    return LC_OK;
+}
+
+extern "C" int lc_field_pack_deferred(lc_ctx *ctx, const void *u_dev, const void *v_dev, int nt, int ny_f, int nx_f, int first_levels,
+                                      void *packed_dev, void *ext_dev) {
+    LC_REQUIRE(ctx, "lc_field_pack_deferred: null context");
+    LC_REQUIRE(u_dev && v_dev && packed_dev && ext_dev && packed_dev != ext_dev, "lc_field_pack_deferred: both images and both planes are required");
+    LC_REQUIRE(nt >= 2 && ny_f >= 4 && nx_f >= 4, "lc_field_pack_deferred: field too small (nt=%d ny_f=%d nx_f=%d)", nt, ny_f, nx_f);
+    LC_HIP_CHECK(hipSetDevice(ctx->device));
+    const int rc = lc_pack_flush(ctx);   // one pending pack per context
+    if (rc != LC_OK) return rc;
+    const int L0 = first_levels > 0 ? first_levels : lcplan::chunk_for_k(4);
+    if (!ctx->defer_pack || L0 >= nt - 1) return lc_launch_pack(ctx, u_dev, v_dev, LC_F32, nt, ny_f, nx_f, 1, packed_dev, ext_dev);
+    // lin[0 .. L0] and ext[0 .. L0 - 1] now: the series as if it ended after level L0
+    launch_pack_fused<float>(ctx->stream, (const float *)u_dev, (const float *)v_dev, (float *)packed_dev, (float *)ext_dev, L0 + 1, ny_f, nx_f, 0);
+    ctx->last_pack_kernel = "pack_fused_kernel";
+    LC_HIP_CHECK(hipGetLastError());
+    ctx->pend = {(const float *)u_dev, (const float *)v_dev, (float *)packed_dev, (float *)ext_dev, nt, ny_f, nx_f, L0 + 1, ctx->stream};
+    return LC_OK;
 }

@@ -15,7 +15,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from collections import namedtuple
-from dataclasses import dataclass
+from dataclasses import dataclass, field as _dc_field
 
 import numpy as np
 
@@ -91,6 +91,42 @@ def _on_grid(cls, lat_f, lon_f, dtype, nt, ny_f, nx_f, **buffers):
                lon_max=float(lo[-1]), dtype=dtype, **buffers)
 
 
+class PendingPack:
+    """The rest of a deferred pack in ``engine``'s context: the four tensors the context still reads and writes (the planes
+    ``u``, ``v`` -- borrowed, as given to ``prepare_field`` -- and the images), alive while it is pending whatever becomes of
+    the field, and the planes' version stamps: the levels not packed yet are read from the planes LATER, so writing them in
+    place before the pack is complete is refused like any other change of borrowed planes (``Engine._check_planes``)."""
+
+    def __init__(self, engine, u, v, lin, ext):
+        self.engine, self.tensors, self.versions = engine, (u, v, lin, ext), (u._version, v._version)
+        self.spoiled = False   # the pack was completed from planes written meanwhile (Engine.close could not refuse): the images are no field's
+
+    def live(self) -> bool:
+        """Still the engine's pending pack and not complete yet (the C side completes it on its own in many calls)."""
+        e = self.engine
+        if e._pending is self and not (e.ctx and e.lib.lc_ctx_pack_pending(e.ctx)):
+            e._pending = None
+        if e._pending is not self:
+            self.tensors = None
+        return e._pending is self
+
+    def moved(self) -> bool:
+        return (self.tensors[0]._version, self.tensors[1]._version) != self.versions
+
+    def check(self):
+        if self.spoiled or (self.live() and self.moved()):
+            raise RuntimeError("the wind tensors given to prepare_field were modified in place while the field's pack was still "
+                               "pending: its later levels would be packed from the new values (prepare the field again, or pass copies)")
+
+    def complete(self):
+        """Completes the pack (``lc_ctx_flush_pack``) on the stream it began on, unless it is complete already."""
+        self.check()
+        if self.live():
+            e = self.engine
+            _capi.check(e.lib.lc_ctx_flush_pack(e.ctx), e.lib)
+            e._pending = self.tensors = None
+
+
 @dataclass
 class PackedField:
     """Gather-ready image(s) of a wind time series, resident on the device.  Built by :meth:`on_grid`."""
@@ -117,6 +153,27 @@ class PackedField:
     u32: "torch.Tensor | None" = None      # wind_f32: the float32 planes as given (the float64 copies u, v are made when a call needs them)
     v32: "torch.Tensor | None" = None
     planes32_version: "tuple | None" = None  # (u32._version, v32._version) when the field was prepared: borrowed like u, v
+    # A deferred pack (Engine.prepare_field: float32 at order 1 with both images, a series longer than the first launch of a
+    # fused advect call reaches): only the first levels of ``lin`` / ``ext`` are packed, the rest is pending in the engine's
+    # context (``pending``: a PendingPack) and is packed inside the launches of the advect call that follows -- or, before
+    # anything else reads the images, by ``pending.complete()``.  READING ``field.lin`` or ``field.ext`` completes the pack
+    # first: whoever takes the images through the attributes sees whole images.  ``image(name)`` is the attribute as it is, for
+    # the advect path of the engine that holds the pack, whose C entry point decides itself (lc_field_pack_deferred in
+    # include/lcs_hip.h).
+    pending: "PendingPack | None" = _dc_field(default=None, repr=False, compare=False)
+
+    def __getattribute__(self, name):
+        if name == "lin" or name == "ext":
+            d = object.__getattribute__(self, "__dict__")
+            pack = d.get("pending")
+            if pack is not None:
+                pack.complete()        # (refuses if the planes it still reads were written meanwhile: the pack stays pending)
+                d["pending"] = None
+        return object.__getattribute__(self, name)
+
+    def image(self, name):
+        """Attribute ``name`` without completing a pending pack."""
+        return object.__getattribute__(self, name)
 
 
 @dataclass
@@ -216,12 +273,17 @@ class Engine:
         self.lds_tiles_mode = -1      # what set_lds_tiles was last given (-1: the library's default, or LCS_LDS_TILES)
         self.verify_mode = 0          # lc_ctx_set_verify
         self._poison = bool(os.environ.get("LCS_DEBUG_POISON"))
+        self._pending = None   # the context's pending pack (PendingPack; prepare_field), until it is complete
         self.ctx = ctx
 
     def close(self):
         if getattr(self, "ctx", None):
-            self.lib.lc_ctx_destroy(self.ctx)
+            pack = getattr(self, "_pending", None)
+            if pack is not None and pack.live() and pack.moved():
+                pack.spoiled = True        # (closing cannot be refused: the field is, wherever it is used next)
+            self.lib.lc_ctx_destroy(self.ctx)   # (completes a pending pack: its tensors are alive until here)
             self.ctx = None
+            self._pending = None
 
     def __del__(self):
         try:
@@ -399,6 +461,12 @@ class Engine:
         return self.lib.lc_ctx_last_pack_kernel(self.ctx).decode()
 
     def _use_current_stream(self):
+        """The context works on torch's current stream.  It precedes every call the engine makes into the library, and most
+        of those complete a pending pack on their own, from the planes as they are at that moment (a change of stream here,
+        ``lc_advect_ex`` of another field, ``lc_sample``, the copies): so this is where the planes' version stamps are looked
+        at -- whatever completes the pack next, the planes are still the ones ``prepare_field`` was given."""
+        if self._pending is not None:
+            self._pending.check()
         s = self.torch.cuda.current_stream(self.device).cuda_stream
         _capi.check(self.lib.lc_ctx_set_stream(self.ctx, C.c_void_p(s)), self.lib)
 
@@ -491,10 +559,30 @@ class Engine:
         self._use_current_stream()
         field, ud, vd = self._planned_field(plan, u, v, lat_f, lon_f, dtype, nt, ny_f, nx_f)
         for code, order, image, with_ext in plan.packs:
+            if code == _capi.LC_F32 and order == 1 and image == "lin" and with_ext and nt - 1 > self.DEFER_FIRST_LEVELS:
+                # the series is longer than the first launch of a fused advect call reaches: the first levels now, the rest
+                # inside the launches of that call (PackedField.pending; a context with deferring switched off packs it all)
+                if self._pending is not None:
+                    self._pending.check()      # (the call below completes it, from its planes as they are now)
+                _capi.check(self.lib.lc_field_pack_deferred(self.ctx, self._ptr(ud), self._ptr(vd), nt, ny_f, nx_f,
+                                                            self.DEFER_FIRST_LEVELS, self._ptr(field.lin), self._ptr(field.ext)), self.lib)
+                self._pending = None
+                if self.lib.lc_ctx_pack_pending(self.ctx):
+                    field.pending = self._pending = PendingPack(self, ud, vd, field.lin, field.ext)
+                continue
             _capi.check(self.lib.lc_field_pack(self.ctx, self._ptr(ud), self._ptr(vd), code, nt, ny_f, nx_f, order,
                                                self._ptr(getattr(field, image) if image else None),
                                                self._ptr(field.ext if with_ext else None)), self.lib)
         return field
+
+    DEFER_FIRST_LEVELS = 32   # the default level chunk (lcplan::chunk_for_k): what launch 0 of a chunked call reads
+
+    def _pack_settled(self, field):
+        """After a call that may have completed the pending pack: its tensors are dropped, by the engine and by the field."""
+        if self._pending is not None:
+            self._pending.live()
+        if field.pending is not None and not field.pending.spoiled and not field.pending.live():
+            field.pending = None
 
     def _planned_field(self, plan: FieldPlan, u, v, lat_f, lon_f, dtype, nt, ny_f, nx_f):
         """``(field, u, v)``: the planes on the device and the field of ``plan`` with its images allocated, not yet packed."""
@@ -601,6 +689,7 @@ class Engine:
                               x_boundary_mode(cyclic_xboundary, noncyclic_clamp, whole), row0=row0, ny_global=ny_global,
                               start=start, t0=t0, nsteps=nsteps, out=(x, y), traj=traj)
         _capi.check(self.lib.lc_advect_ex(self.ctx, C.byref(a)), self.lib)
+        self._pack_settled(field)
         if halo:
             x, y = x_buf, y_buf
         return (x, y, *traj) if return_traj else (x, y)
@@ -655,6 +744,12 @@ class Engine:
         """``lc_advect_args`` of one call on ``field``: the borrowed planes checked, what the call's source (:func:`call_source`)
         needs made, then the structure, filled here and nowhere else.  ``start``, ``out``, ``traj``: ``(x, y)`` pairs of tensors."""
         self._check_planes(field)
+        pack = field.pending
+        if pack is not None and pack.engine is self and pack.live():
+            pack.check()           # this context's own pending pack: lc_advect_ex carries or completes it
+        elif pack is not None:
+            pack.complete()        # another engine's: whole images before this context reads them (refused if it was spoiled)
+            field.pending = None
         src = call_source(field, interp_order, xmode)
         if src.planes64:
             self._planes64(field)
@@ -663,7 +758,7 @@ class Engine:
         p = lambda t: t.data_ptr() if t is not None else None
         (sx, sy), (tx, ty) = start or (None, None), traj or (None, None)
         return _capi.AdvectArgs(
-            struct_size=C.sizeof(_capi.AdvectArgs), **{arg: p(getattr(field, name)) for arg, name in src.buffers.items()},
+            struct_size=C.sizeof(_capi.AdvectArgs), **{arg: p(field.image(name)) for arg, name in src.buffers.items()},
             dtype=src.dtype, nt=field.nt, ny_f=field.ny_f, nx_f=field.nx_f, lat_min=field.lat_min, lat_max=field.lat_max,
             lon_min=field.lon_min, lon_max=field.lon_max, seed_lat_dev=p(slat), ny=int(ny), seed_lon_dev=p(slon), nx=int(nx),
             row0=int(row0), ny_global=int(ny if ny_global is None else ny_global), x_start=p(sx), y_start=p(sy),
@@ -694,7 +789,7 @@ class Engine:
         available"): its kernels read the order-1 image's 16-byte node pairs, so the image is packed here, once, and kept on
         the field (``advect`` and ``sample`` alike).  Everywhere else the raw planes ``field.u`` / ``field.v`` are the source."""
         self._check_planes(field)
-        if field.lin is None and field.dtype == np.dtype(np.float32) and interp_order == 1:
+        if field.image("lin") is None and field.dtype == np.dtype(np.float32) and interp_order == 1:
             field.lin = self._empty((self.lib.lc_packed_elems(field.nt, field.ny_f, field.nx_f),), field.dtype)
             self._use_current_stream()
             _capi.check(self.lib.lc_field_pack(self.ctx, self._ptr(field.u), self._ptr(field.v), _NP2LC[field.dtype], field.nt,
