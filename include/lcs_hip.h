@@ -764,6 +764,51 @@ typedef struct lc_distance_args {
 } lc_distance_args;
 int lc_distance_transform(lc_ctx *ctx, const lc_distance_args *args);
 
+/* ---- great-circle distance to the nearest ridge pixel ----------------------------------
+ * Replaces nothing in the reference: it is the latitude-dependent metric that the index-unit transform above, the driver's
+ * LCS/area_of_influence.py:231, cannot give on a latitude-longitude grid (wrong by 1 / cos(latitude) along longitude, blind
+ * across the poles and, without cyclic_x, across the seam).  Added at LC_VERSION 104 without a bump: nothing that existed
+ * changed.  n_members independent planes [n_members][ny*nx] per call, all on the same grid.
+ *
+ * Foreground: as above, a pixel whose value is != 0 and not NaN; mask: `dtype` elements, LC_F32 or LC_F64.
+ * Coordinates: the caller hands over, float64 on the device, cos_lat / sin_lat [ny] and cos_lon / sin_lon [nx] of its
+ * latitudes and longitudes (any grid: not uniform, not global, not sorted); no kernel evaluates a trigonometric function of a
+ * coordinate.  Node (r, c) is the unit vector X = fl(cos_lat[r] cos_lon[c]), Y = fl(cos_lat[r] sin_lon[c]), Z = sin_lat[r].
+ *   cost_out     float64 [n_members][ny*nx], or NULL: the smallest, over the foreground pixels q of the plane, squared chord
+ *                cost = fl(fl(fl(dX dX) + fl(dY dY)) + fl(dZ dZ)) with dX = fl(Xp - Xq), ...: every operation rounded once to
+ *                float64 and nothing fused.  0 on foreground.
+ *   nearest_out  int32 [n_members][ny*nx], or NULL: the linear index into its plane of the foreground pixel that cost belongs
+ *                to.  Tie rule: among pixels of equal cost the smallest linear index.
+ *   dist_out     float64 [n_members][ny*nx], or NULL: 2 radius asin(min(1, sqrt(cost) / 2)), exactly 0 on foreground.
+ *                (At least one of the three outputs is given.)
+ *   empty plane  a plane without a foreground pixel is +inf everywhere, nearest -1.
+ *   max_chord2 > 0: (2 sin(max_distance / (2 radius)))^2, squared by the caller in float64; a pixel keeps its result where
+ *                cost <= max_chord2 and is +inf, nearest -1, elsewhere -- exactly the unbounded result under that mask.  A
+ *                query row is searched against the rows whose same-meridian chord to it is within the bound only (plus a
+ *                margin far above every rounding: no culling changes a result).  <= 0: unbounded.
+ *   max_distance the same bound in the unit of radius: > 0 beside a max_chord2 > 0, not read otherwise.
+ *   work_dev     int32 [lc_sphere_distance_work_elems(ny, nx, n_members)] scratch, 8-byte aligned (0 elements for bad sizes,
+ *                a plane of 2^31 pixels or more among them)
+ * A plane of 2^31 pixels or more and non-positive sizes are refused with LC_EINVAL before any HIP call.  Every query pixel is
+ * compared with every foreground pixel of its band: the cost of a call is their product.
+ * No kernel of this call waits for another workgroup. */
+size_t lc_sphere_distance_work_elems(int ny, int nx, int n_members);
+typedef struct lc_sphere_distance_args {
+    size_t struct_size; /* sizeof(lc_sphere_distance_args): checked before any other field */
+    const void *mask;
+    int dtype, ny, nx, n_members;
+    const double *cos_lat, *sin_lat; /* device, [ny] */
+    const double *cos_lon, *sin_lon; /* device, [nx] */
+    double radius;                   /* > 0, finite */
+    double max_chord2;               /* <= 0: unbounded */
+    double max_distance;             /* > 0 where max_chord2 > 0 */
+    void *dist_out;                  /* float64, or NULL */
+    void *nearest_out;               /* int32, or NULL */
+    void *cost_out;                  /* float64, or NULL */
+    void *work_dev;
+} lc_sphere_distance_args;
+int lc_sphere_distance(lc_ctx *ctx, const lc_sphere_distance_args *args);
+
 /* ---- thinning and dilating a ridge mask (skeletonize_ridges, dilate_ridges) -------------
  * The two morphological steps of the driver's chain: skeletonize(ridges.values) between the Hessian mask and the filter
  * (LCS/area_of_influence.py:207) and binary_dilation(ridges.values) at its end (:233).  Both entry points were added at

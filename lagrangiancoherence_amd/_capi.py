@@ -172,6 +172,20 @@ class DistanceArgs(C.Structure):
 PROTOTYPES["lc_distance_work_elems"] = (_sz, [_i, _i, _i])
 PROTOTYPES["lc_distance_transform"] = (_i, [_vp, C.POINTER(DistanceArgs)])
 
+
+class SphereDistanceArgs(C.Structure):
+    """``lc_sphere_distance_args`` of include/lcs_hip.h, field for field."""
+    _fields_ = [("struct_size", _sz),
+                ("mask", _vp),
+                ("dtype", _i), ("ny", _i), ("nx", _i), ("n_members", _i),
+                ("cos_lat", _vp), ("sin_lat", _vp), ("cos_lon", _vp), ("sin_lon", _vp),
+                ("radius", _d), ("max_chord2", _d), ("max_distance", _d),
+                ("dist_out", _vp), ("nearest_out", _vp), ("cost_out", _vp), ("work_dev", _vp)]
+
+
+PROTOTYPES["lc_sphere_distance_work_elems"] = (_sz, [_i, _i, _i])
+PROTOTYPES["lc_sphere_distance"] = (_i, [_vp, C.POINTER(SphereDistanceArgs)])
+
 LC_MORPH_THIN, LC_MORPH_DILATE = 0, 1
 
 

@@ -1254,6 +1254,82 @@ class Engine:
             dist, nearest = dist[0], nearest[0] if return_nearest else None
         return (dist, nearest) if return_nearest else dist
 
+    # ------------------------------------------------------------------ great-circle distance to the nearest pixel of a mask
+    @staticmethod
+    def sphere_tables(lat, lon, radius=6371000.0, max_distance=None):
+        """What :meth:`sphere_distance` hands to the device, computed with numpy on the host and checked there (no device is
+        touched): ``(cos lat, sin lat, cos lon, sin lon, radius, max_chord2, max_distance)``.  ``lat`` / ``lon`` in degrees;
+        ``max_chord2 = fl(c c)`` with ``c = 2 sin(max_distance / (2 radius))``, 0 where there is no bound (None, or a bound
+        of half the sphere's circumference or more)."""
+        lat, lon = np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64)
+        if lat.ndim != 1 or lon.ndim != 1 or lat.size == 0 or lon.size == 0:
+            raise ValueError("lat and lon: one-dimensional and not empty")
+        if not (np.isfinite(lat).all() and np.isfinite(lon).all()):
+            raise ValueError("lat and lon: finite degrees")
+        if np.abs(lat).max() > 90.0:
+            raise ValueError(f"lat: within [-90, 90] degrees, got {lat.min()!r} .. {lat.max()!r}")
+        radius = float(radius)
+        if not (radius > 0 and np.isfinite(radius)):
+            raise ValueError(f"radius {radius!r}: a positive, finite number")
+        chord2, bound = 0.0, 0.0
+        if max_distance is not None:
+            if not float(max_distance) > 0:
+                raise ValueError(f"max_distance {max_distance!r}: a positive number, or None for no bound")
+            if float(max_distance) < np.pi * radius:
+                bound = float(max_distance)
+                c = np.float64(2.0) * np.sin(np.float64(bound) / (np.float64(2.0) * np.float64(radius)))
+                chord2 = float(c * c)
+                if not chord2 > 0.0:
+                    raise ValueError(f"max_distance {max_distance!r}: its squared chord on a sphere of radius {radius!r} underflows")
+        y, x = lat * np.pi / 180, lon * np.pi / 180
+        return np.cos(y), np.sin(y), np.cos(x), np.sin(x), radius, chord2, bound
+
+    def sphere_distance(self, mask, lat, lon, radius=6371000.0, max_distance=None, return_nearest=False, return_cost=False):
+        """Great-circle distance from every node of a latitude-longitude grid to the nearest foreground pixel of ``mask``
+        (``lc_sphere_distance``), as a float64 device tensor shaped like ``mask`` -- ``(ny, nx)``, or ``(n_members, ny, nx)``,
+        every plane on its own in the same launches -- in the unit of ``radius`` (metres by default).
+
+        A pixel is foreground when it is ``!= 0`` and not NaN (float32 / float64 kept, any other dtype converted to float64).
+        ``lat`` ``(ny,)`` and ``lon`` ``(nx,)`` are degrees, finite, ``|lat| <= 90``; the grid need be neither uniform nor
+        global nor sorted.  Their cosines and sines are numpy's, computed here; node ``(r, c)`` is the unit vector ``(cos lat
+        cos lon, cos lat sin lon, sin lat)`` and the cost of a pair the squared chord ``((dX dX + dY dY) + dZ dZ)``, every
+        operation rounded once to float64: a pixel gets the smallest cost over its plane's foreground, the smallest linear
+        index among the pixels of that cost, and ``dist = 2 radius asin(min(1, sqrt(cost) / 2))``.  The seam and the poles
+        need no flag.  ``max_distance`` (> 0, in the unit of ``radius``): pixels further away -- ``cost > (2 sin(max_distance /
+        (2 radius)))^2`` -- are ``+inf``, and a row is searched against the rows within that bound only; the result is exactly
+        the unbounded one under that mask.  None, or ``>= pi radius``: unbounded.  A plane without foreground is ``+inf``.
+
+        ``return_nearest``: also the int32 linear index, into its plane, of the nearest foreground pixel (-1 where the
+        distance is ``+inf``).  ``return_cost``: also the float64 squared chord.  Returns ``dist``, then ``nearest``, then
+        ``cost``, as asked for.  Every pixel is compared with every foreground pixel of its band."""
+        cl, sl, cx, sx, radius, chord2, bound = self.sphere_tables(lat, lon, radius, max_distance)
+        shape = tuple(int(s) for s in mask.shape) if hasattr(mask, "shape") else np.shape(mask)
+        if len(shape) not in (2, 3) or shape[-2:] != (cl.size, cx.size):
+            raise ValueError(f"mask {shape}: (ny, nx) or (n_members, ny, nx) with ny = len(lat) = {cl.size} and nx = len(lon) = {cx.size}")
+        m = self._planes(mask)
+        n, ny, nx = (int(s) for s in m.shape)
+        torch = self.torch
+        elems = int(self.lib.lc_sphere_distance_work_elems(ny, nx, n))
+        # int64 elements: the list's float64 parts come first and want 8-byte alignment whatever the allocator does; the
+        # call's own checks refuse what cannot be sized (a plane too large) before they touch the buffer
+        work = torch.empty((max(1, (elems + 1) // 2),), dtype=torch.int64, device=self.device)
+        dist = self._empty((n, ny, nx), np.float64)
+        nearest = torch.empty((n, ny, nx), dtype=torch.int32, device=self.device) if return_nearest else None
+        cost = self._empty((n, ny, nx), np.float64) if return_cost else None
+        tables = [self.to_device(t, np.float64) for t in (cl, sl, cx, sx)]
+        a = _capi.SphereDistanceArgs(struct_size=C.sizeof(_capi.SphereDistanceArgs))
+        a.mask, a.dtype = m.data_ptr(), _NP2LC[np.dtype(str(m.dtype).replace("torch.", ""))]
+        a.ny, a.nx, a.n_members = ny, nx, n
+        a.cos_lat, a.sin_lat, a.cos_lon, a.sin_lon = (t.data_ptr() for t in tables)
+        a.radius, a.max_chord2, a.max_distance = radius, chord2, bound
+        a.dist_out, a.work_dev = dist.data_ptr(), work.data_ptr()
+        a.nearest_out = nearest.data_ptr() if return_nearest else None
+        a.cost_out = cost.data_ptr() if return_cost else None
+        self._use_current_stream()
+        _capi.check(self.lib.lc_sphere_distance(self.ctx, C.byref(a)), self.lib)
+        out = [t if len(shape) == 3 else t[0] for t in (dist, nearest, cost) if t is not None]
+        return out[0] if len(out) == 1 else tuple(out)
+
     # ------------------------------------------------------------------ adaptive local threshold
     _THRESHOLD_PLANES = ("threshold", "mask")
 

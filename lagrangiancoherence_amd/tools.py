@@ -212,18 +212,31 @@ def filter_ridges(ridges, ftle, criteria, thresholds, verbose=True, connectivity
     return _make(ridges, _to_np(out), order, coords, getattr(ridges, "name", None)).transpose(*dims)
 
 
-def distance_to_ridges(ridges, cyclic=False, sampling=None, max_distance=None, return_labels=False, connectivity=2):
-    """Distance from every grid point to the nearest ridge pixel: ``scipy.ndimage.distance_transform_edt(~ridges_bool)`` of
-    LCS/area_of_influence.py:231, bit for bit, on the device (``Engine.distance_transform``).
+def distance_to_ridges(ridges, cyclic=False, sampling=None, max_distance=None, return_labels=False, connectivity=2,
+                       metric='index', radius=6371000.0):
+    """Distance from every grid point to the nearest ridge pixel, on the device.  ``metric='index'`` (the default):
+    ``scipy.ndimage.distance_transform_edt(~ridges_bool)`` of LCS/area_of_influence.py:231, bit for bit
+    (``Engine.distance_transform``).  ``metric='sphere'``: the great-circle distance on the array's own ``latitude`` and
+    ``longitude`` (``Engine.sphere_distance``).
 
     ``ridges`` is a labelled array over ``latitude`` and ``longitude`` (sorted ascending here, as ``filter_ridges`` sorts),
     2-D, or 3-D with one more dimension (time, member): every plane is then transformed on its own, all of them in the same
-    kernel launches.  A pixel is part of a ridge when it is ``!= 0`` and not NaN.  Distances are in INDEX units times
-    ``sampling`` (a scalar or ``(latitude step, longitude step)``, default 1), as the driver's are; a latitude-dependent
-    metric (great-circle distance) is out of scope.  ``cyclic``: longitude offsets are taken the shorter way round a global
-    axis.  ``max_distance``: points further away are ``+inf`` and cost no search -- ``max_distance=12`` is the driver's
-    ``dist.where(dist < 12)`` up to the points at exactly 12, which it drops and this keeps.  A plane without a ridge is
-    ``+inf`` everywhere.
+    kernel launches.  A pixel is part of a ridge when it is ``!= 0`` and not NaN.  A plane without a ridge is ``+inf``
+    everywhere.
+
+    ``metric='index'``: distances are in INDEX units times ``sampling`` (a scalar or ``(latitude step, longitude step)``,
+    default 1), as the driver's are.  ``cyclic``: longitude offsets are taken the shorter way round a global axis.
+    ``max_distance``: points further away are ``+inf`` and cost no search -- ``max_distance=12`` is the driver's
+    ``dist.where(dist < 12)`` up to the points at exactly 12, which it drops and this keeps.
+
+    ``metric='sphere'``: distances are great-circle distances in the unit of ``radius`` (metres on the default Earth), from
+    the coordinates in degrees, which need be neither uniform nor global: ``2 radius asin(chord / 2)`` of the smallest chord
+    between the unit vectors of the two nodes, float64 (``Engine.sphere_distance`` states every rounding).  On a
+    latitude-longitude grid the index metric is wrong by ``1 / cos(latitude)`` along longitude and blind across the poles;
+    this one is neither, and it sees across the seam without a flag: ``cyclic`` then applies to the labels only.
+    ``max_distance`` is in the unit of ``radius`` -- ``max_distance=330e3`` is the swath within 330 km of a ridge, what the
+    driver's ``dist < 12`` stands for at 0.25 degrees -- and cuts the search to the latitudes within it.  ``sampling`` has no
+    meaning here and must be None.  Every point is compared with every ridge pixel within the bound's band of latitudes.
 
     ``return_labels=True`` also returns, per point, the label of the ridge its nearest pixel belongs to (0 where the distance
     is ``+inf``): ``Engine.label_components(ridges, connectivity, cyclic)`` gathered through the nearest-pixel index, on the
@@ -231,6 +244,10 @@ def distance_to_ridges(ridges, cyclic=False, sampling=None, max_distance=None, r
     plane into every ridge's own area of influence, which the driver approximates by dilation and a second filter.
 
     Returns float64 distances (and int32 labels) in the caller's class and dimension order."""
+    if metric not in ('index', 'sphere'):
+        raise ValueError(f"metric {metric!r}: 'index' or 'sphere'")
+    if metric == 'sphere' and sampling is not None:
+        raise ValueError("sampling belongs to metric='index': on the sphere the coordinates are the metric")
     dims = tuple(ridges.dims)
     lead = [d for d in dims if d not in ("latitude", "longitude")]
     if len(lead) > 1 or len(dims) - len(lead) != 2:
@@ -238,6 +255,8 @@ def distance_to_ridges(ridges, cyclic=False, sampling=None, max_distance=None, r
     order = (*lead, "latitude", "longitude")
     lat, lon = _coord(ridges, "latitude"), _coord(ridges, "longitude")
     ilat, ilon = np.argsort(lat, kind="stable"), np.argsort(lon, kind="stable")
+    if metric == 'sphere':
+        Engine.sphere_tables(lat, lon, radius, max_distance)        # every refusal of the coordinates and the bound, before a device
     v = np.asarray(ridges.transpose(*order).values)
     v = v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)
     v = np.ascontiguousarray(v[..., ilat, :][..., ilon])
@@ -249,9 +268,14 @@ def distance_to_ridges(ridges, cyclic=False, sampling=None, max_distance=None, r
 
     def out(t):
         return _make(ridges, _to_np(t), order, coords, getattr(ridges, "name", None)).transpose(*dims)
+
+    def transform(return_nearest=False):
+        if metric == 'sphere':
+            return eng.sphere_distance(mask, lat[ilat], lon[ilon], radius, max_distance, return_nearest=return_nearest)
+        return eng.distance_transform(mask, cyclic, sampling, max_distance, return_nearest=return_nearest)
     if not return_labels:
-        return out(eng.distance_transform(mask, cyclic, sampling, max_distance))
-    dist, nearest = eng.distance_transform(mask, cyclic, sampling, max_distance, return_nearest=True)
+        return out(transform())
+    dist, nearest = transform(return_nearest=True)
     labels, _ = eng.label_components(mask, connectivity, cyclic)
     planes = labels.reshape(-1, labels.shape[-2] * labels.shape[-1])
     index = nearest.reshape(planes.shape).to(eng.torch.int64)
