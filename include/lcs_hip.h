@@ -729,6 +729,49 @@ int lc_component_sums(lc_ctx *ctx, const lc_component_sums_args *args);
 int lc_component_apply(lc_ctx *ctx, const void *labels, const void *mask, int dtype, int ny, int nx, int n_members,
                        const void *keep, int n_max, double fill, void *mask_out);
 
+/* ---- ridges followed through time (track_ridges, persistent_ridges) -------------------
+ * The filter above (LCS/area_of_influence.py:210-211) extended through time: its components end at the plane, so it cannot
+ * measure how long a ridge lasts.  Added at LC_VERSION 104 without a bump: nothing that existed changed.
+ *
+ * A record is n_times planes [n_times][ny*nx] in the order given; consecutive means adjacent index, nothing is sorted along
+ * time.  Foreground: as above, a voxel whose value is != 0 and not NaN.  Two foreground voxels are LINKED when
+ *   - they lie in the same plane and are neighbours under `connectivity` (1: edges; 2: edges and corners), with cyclic_x across
+ *     the longitude seam too: exactly what lc_label_components joins; or
+ *   - they lie in adjacent planes and are at most `reach` pixels apart in both row and column (Chebyshev distance), with
+ *     cyclic_x the column offset taken the shorter way round.  reach 0: the same pixel.  reach 1 with connectivity 2 is
+ *     scipy's generate_binary_structure(3, 3); reach 0 with connectivity 1 is generate_binary_structure(3, 1).
+ * A TRACK is a connected component of that relation.  Ridges that merge or split therefore belong to ONE track: a track is
+ * not cut where two ridges meet, and everything that ever touched it through time carries its label.
+ * Tracks are numbered 1 .. N in the order of their first voxel in raster order (time, latitude, longitude) -- the numbering
+ * of scipy.ndimage.label on the 3-D array; background is 0.  A track's first / last are the smallest / largest plane index it
+ * occupies, its duration last - first + 1, its volume its voxel count.
+ * reach is an integer in 0 .. LC_TRACK_MAX_REACH: a stated condition, not a tuned value -- every foreground voxel reads a
+ * window of (2 reach + 1)^2 voxels of the plane before it, and ridge masks are sparse.  A record of 2^31 voxels or more is
+ * refused ("record too large").
+ *
+ * lc_label_tracks
+ *   labels_out    int32 [n_times][ny*nx]
+ *   count_out     int32 [1]: N
+ *   work_dev      int32 [lc_track_work_elems(ny, nx, n_times)] scratch (0 elements for a bad or oversized geometry)
+ * lc_track_spans: entry [l-1] belongs to track l; labels above min(count, n_max) are not measured; entries past the count hold
+ * first = last = -1 and volume = 0.  All integer: the result does not depend on the order the voxels arrive in.
+ * To apply a keep table, call lc_component_apply on the record viewed as ONE plane of n_times*ny rows.
+ * No kernel of these calls waits for another workgroup: each stage hands over at the end of its launch. */
+#define LC_TRACK_MAX_REACH 16
+size_t lc_track_work_elems(int ny, int nx, int n_times);
+int lc_label_tracks(lc_ctx *ctx, const void *mask, int dtype, int ny, int nx, int n_times, int connectivity, int cyclic_x,
+                    int reach, void *labels_out, void *count_out, void *work_dev);
+typedef struct lc_track_spans_args {
+    size_t struct_size; /* sizeof(lc_track_spans_args): checked first */
+    const void *labels; /* int32 [n_times][ny*nx], as lc_label_tracks wrote them */
+    const void *count;  /* int32 [1] */
+    int ny, nx, n_times;
+    int n_max; /* capacity of every output */
+    void *first_out, *last_out; /* int32 [n_max] */
+    void *volume_out;           /* int64 [n_max] */
+} lc_track_spans_args;
+int lc_track_spans(lc_ctx *ctx, const lc_track_spans_args *args);
+
 /* ---- distance to the nearest ridge pixel (exact Euclidean distance transform) ----------
  * The driver's next step after the filter (LCS/area_of_influence.py:231): scipy.ndimage.distance_transform_edt(~ridges_bool),
  * of which it keeps `dist < 12` as the swath a ridge influences.  n_members independent planes [n_members][ny*nx] per call.

@@ -19,6 +19,7 @@ LC_X_CLAMP_POINT, LC_X_CYCLIC, LC_X_CLAMP_REFERENCE_OUTER = 0, 1, 2
 LC_GRID_REGULAR, LC_GRID_GAUSSIAN = 0, 1
 LC_F64_AUTO, LC_F64_EXACT_ORDER, LC_F64_FAST = 0, 1, 2
 LC_EXACT_ORDER_MAX_SEEDS = 1 << 18
+LC_TRACK_MAX_REACH = 16
 
 _vp, _i, _d, _sz = C.c_void_p, C.c_int, C.c_double, C.c_size_t
 
@@ -156,6 +157,19 @@ PROTOTYPES["lc_label_components"] = (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp,
 PROTOTYPES["lc_component_sums"] = (_i, [_vp, C.POINTER(ComponentSumsArgs)])
 PROTOTYPES["lc_component_apply"] = (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _d, _vp])
 
+
+class TrackSpansArgs(C.Structure):
+    """``lc_track_spans_args`` of include/lcs_hip.h, field for field."""
+    _fields_ = [("struct_size", _sz),
+                ("labels", _vp), ("count", _vp),
+                ("ny", _i), ("nx", _i), ("n_times", _i),
+                ("n_max", _i),
+                ("first_out", _vp), ("last_out", _vp), ("volume_out", _vp)]
+
+
+PROTOTYPES["lc_track_work_elems"] = (_sz, [_i, _i, _i])
+PROTOTYPES["lc_label_tracks"] = (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp])
+PROTOTYPES["lc_track_spans"] = (_i, [_vp, C.POINTER(TrackSpansArgs)])
 
 
 class DistanceArgs(C.Structure):

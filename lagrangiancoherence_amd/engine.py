@@ -1217,6 +1217,92 @@ class Engine:
                                                 ny, nx, n, self._ptr(keep), int(keep.shape[1]), float(fill), self._ptr(out)), self.lib)
         return out if len(mask.shape) == 3 else out[0]
 
+    # ------------------------------------------------------------------ ridges followed through time (track_ridges)
+    MAX_TRACK_REACH = _capi.LC_TRACK_MAX_REACH
+
+    @classmethod
+    def checked_track_options(cls, connectivity, reach):
+        """``(connectivity, reach)`` as ints, or ``ValueError``: what ``lc_label_tracks`` would refuse, without a device."""
+        if connectivity not in (1, 2):
+            raise ValueError(f"connectivity {connectivity!r}: 1 (edges) or 2 (edges and corners)")
+        if isinstance(reach, bool) or not isinstance(reach, (int, np.integer)) or not 0 <= reach <= cls.MAX_TRACK_REACH:
+            raise ValueError(f"reach {reach!r}: an integer in 0 .. {cls.MAX_TRACK_REACH} (pixels per time step)")
+        return int(connectivity), int(reach)
+
+    def _record(self, mask):
+        """``mask`` on the device as a ``(n_times, ny, nx)`` record (float32 / float64 kept, anything else float64)."""
+        dtype = np.dtype(str(mask.dtype).replace("torch.", ""))
+        t = self.to_device(mask, dtype if dtype in _NP2LC else np.dtype(np.float64))
+        if t.dim() != 3 or t.numel() == 0:
+            raise ValueError("a record (n_times, ny, nx), not empty")
+        return t
+
+    def label_tracks(self, mask, connectivity=2, cyclic=False, reach=1):
+        """Space-time labels of a record of ridge masks (``lc_label_tracks``): ``(labels, count)``.
+
+        ``mask``: ``(n_times, ny, nx)``, float32 or float64, planes in the order given; a voxel is foreground when it is
+        ``!= 0`` and not NaN.  Two foreground voxels are linked when they are neighbours in one plane (``connectivity`` and
+        ``cyclic`` as in :meth:`label_components`), or lie in adjacent planes at most ``reach`` pixels apart in both row and
+        column (``cyclic``: the column offset the shorter way round).  A track is a connected component of that relation, so
+        ridges that merge or split are ONE track.  ``labels``: int32 device tensor shaped like ``mask``, 0 on background, else
+        ``1..N`` in the order of each track's first voxel in raster order -- ``scipy.ndimage.label``'s numbering on the 3-D
+        array (``reach=1, connectivity=2`` is its ``generate_binary_structure(3, 3)``, ``reach=0, connectivity=1`` its
+        ``(3, 1)``).  ``count``: int32 ``(1,)``, N.  One plane gives :meth:`label_components` of that plane."""
+        connectivity, reach = self.checked_track_options(connectivity, reach)
+        m = self._record(mask)
+        n, ny, nx = (int(s) for s in m.shape)
+        labels = self.torch.empty((n, ny, nx), dtype=self.torch.int32, device=self.device)
+        count = self.torch.empty((1,), dtype=self.torch.int32, device=self.device)
+        work = self.torch.empty((max(1, int(self.lib.lc_track_work_elems(ny, nx, n))),), dtype=self.torch.int32, device=self.device)
+        self._use_current_stream()
+        _capi.check(self.lib.lc_label_tracks(self.ctx, self._ptr(m), _NP2LC[np.dtype(str(m.dtype).replace("torch.", ""))], ny, nx, n,
+                                             connectivity, int(bool(cyclic)), reach, self._ptr(labels), self._ptr(count),
+                                             self._ptr(work)), self.lib)
+        return labels, count
+
+    def track_spans(self, labels, count, n_max=None):
+        """``lc_track_spans``: per track of :meth:`label_tracks`' result, as a dict of device tensors ``(n_max,)`` -- ``first``
+        and ``last`` (int32: the smallest and largest plane index the track occupies), ``duration`` (int32, ``last - first +
+        1``) and ``volume`` (int64, voxels).  Entries past the count hold ``first = last = -1`` and ``duration = volume = 0``.
+        ``n_max`` None: the count, read back from the device (one synchronisation)."""
+        torch = self.torch
+        if labels.dim() != 3 or labels.dtype != torch.int32 or not labels.is_contiguous():
+            raise ValueError("labels: the int32 tensor label_tracks returned")
+        n, ny, nx = (int(s) for s in labels.shape)
+        if n_max is None:
+            n_max = int(count[0].item())
+        n_max = max(1, int(n_max))
+        out = {"first": torch.empty((n_max,), dtype=torch.int32, device=self.device),
+               "last": torch.empty((n_max,), dtype=torch.int32, device=self.device),
+               "volume": torch.empty((n_max,), dtype=torch.int64, device=self.device)}
+        a = _capi.TrackSpansArgs(struct_size=C.sizeof(_capi.TrackSpansArgs))
+        a.labels, a.count = labels.data_ptr(), count.data_ptr()
+        a.ny, a.nx, a.n_times, a.n_max = ny, nx, n, n_max
+        a.first_out, a.last_out, a.volume_out = (out[k].data_ptr() for k in ("first", "last", "volume"))
+        self._use_current_stream()
+        _capi.check(self.lib.lc_track_spans(self.ctx, C.byref(a)), self.lib)
+        out["duration"] = torch.where(out["first"] >= 0, out["last"] - out["first"] + 1, torch.zeros_like(out["first"]))
+        return out
+
+    def filter_tracks(self, mask, min_duration=1, min_volume=1, connectivity=2, cyclic=False, reach=1, fill=0.0):
+        """``mask`` with the voxels of every track that lasts fewer than ``min_duration`` planes or holds fewer than
+        ``min_volume`` voxels replaced by ``fill`` (background becomes ``fill`` too).  Label, spans and apply run on the device
+        (``lc_label_tracks``, ``lc_track_spans``, and ``lc_component_apply`` on the record viewed as one plane of ``n_times *
+        ny`` rows); the count is read back once in between.  Returns a device tensor shaped and typed like ``mask``."""
+        torch = self.torch
+        m = self._record(mask)
+        n, ny, nx = (int(s) for s in m.shape)
+        labels, count = self.label_tracks(m, connectivity, cyclic, reach)
+        spans = self.track_spans(labels, count)
+        keep = (spans["volume"] >= max(1, int(min_volume))) & (spans["duration"] >= int(min_duration))
+        keep = keep.to(torch.uint8).contiguous()
+        dtype = np.dtype(str(m.dtype).replace("torch.", ""))
+        out = self._empty((n, ny, nx), dtype)
+        self._use_current_stream()
+        _capi.check(self.lib.lc_component_apply(self.ctx, self._ptr(labels), self._ptr(m), _NP2LC[dtype], n * ny, nx, 1,
+                                                self._ptr(keep), int(keep.shape[0]), float(fill), self._ptr(out)), self.lib)
+        return out
+
     # ------------------------------------------------------------------ distance to the nearest pixel of a mask
     def distance_transform(self, mask, cyclic=False, sampling=None, max_distance=None, return_nearest=False):
         """Exact Euclidean distance from every pixel to the nearest foreground pixel of ``mask`` (``lc_distance_transform``):

@@ -15,6 +15,9 @@
 * ``threshold_local``               LCS/area_of_influence.py:194-199: ``threshold_local(ftle_local.values, block_size=301,
                                     offset=-.8)`` (scikit-image there: the Gaussian rule it documents is restated here), and
                                     ``above_local_threshold``, that threshold and the driver's comparison with it in one call
+* ``track_ridges``                  the filter of LCS/area_of_influence.py:210-211 extended through time: space-time labels of a
+                                    ridge series (which ridge is the same ridge as in the plane before, how long it lasts), and
+                                    ``persistent_ridges``, the ridges that last at least so many planes (defined here)
 
 The remaining functions of that module (IDW regridding, harvesine, latlonsel) have no caller on the
 path.
@@ -28,7 +31,7 @@ from .engine import Engine, common_dtype
 
 __all__ = ["xr_map_coordinates", "fourth_order_derivative", "derivative_spherical_coords",
            "find_ridges_spherical_hessian", "filter_ridges", "distance_to_ridges", "skeletonize_ridges", "dilate_ridges",
-           "threshold_local", "above_local_threshold"]
+           "threshold_local", "above_local_threshold", "track_ridges", "persistent_ridges"]
 
 
 def xr_map_coordinates(da, new_x, new_y, isglobal=True, order=1):
@@ -359,6 +362,79 @@ def dilate_ridges(ridges, iterations=1, connectivity=1, cyclic=False, fill=0.0):
     was = (mask != 0) & ~torch.isnan(mask)
     added = torch.where(grown != 0, torch.ones_like(mask), torch.full_like(mask, float(fill)))
     return out(torch.where(was, mask, added))
+
+
+def _ridge_record(ridges, connectivity, reach, min_duration):
+    """What the two tracking functions share: every argument check, before an engine exists; then ``ridges`` sorted as
+    ``filter_ridges`` sorts it, on the device as ``(time, latitude, longitude)``, and the way back to the caller's class and
+    dimension order.  Returns ``(engine, record, out, time coordinate, connectivity, reach, min_duration)``."""
+    connectivity, reach = Engine.checked_track_options(connectivity, reach)
+    if isinstance(min_duration, bool) or not isinstance(min_duration, (int, np.integer)) or min_duration < 1:
+        raise ValueError(f"min_duration {min_duration!r}: an integer >= 1 (planes)")
+    dims = tuple(ridges.dims)
+    lead = [d for d in dims if d not in ("latitude", "longitude")]
+    if len(lead) != 1 or len(dims) != 3:
+        raise ValueError("ridges: dims latitude, longitude and exactly one more (the time a ridge is followed through)")
+    order = (lead[0], "latitude", "longitude")
+    lat, lon = _coord(ridges, "latitude"), _coord(ridges, "longitude")
+    ilat, ilon = np.argsort(lat, kind="stable"), np.argsort(lon, kind="stable")
+    v = np.asarray(ridges.transpose(*order).values)
+    dtype = v.dtype
+    v = v if dtype in (np.float32, np.float64) else v.astype(np.float64)
+    v = np.ascontiguousarray(v[..., ilat, :][..., ilon])
+    time = _coord(ridges, lead[0])
+    coords = {lead[0]: time, "latitude": lat[ilat], "longitude": lon[ilon]}
+    eng = get_engine()
+
+    def out(t, keep_dtype=False):
+        a = _to_np(t)
+        return _make(ridges, a.astype(dtype, copy=False) if keep_dtype else a, order, coords, getattr(ridges, "name", None)).transpose(*dims)
+    return eng, eng.to_device(v, v.dtype), out, time, connectivity, reach, int(min_duration)
+
+
+def track_ridges(ridges, reach=1, connectivity=2, cyclic=False, min_duration=1, return_table=False):
+    """Follow the ridges of a mask series through time, on the device (``Engine.label_tracks``): which ridge of a plane is
+    the same ridge as in the plane before, and how long it lasts -- what ``filter_ridges`` (LCS/area_of_influence.py:210-211)
+    cannot measure, because its components end at the plane.
+
+    ``ridges`` is a labelled array over ``latitude``, ``longitude`` (sorted ascending here, as ``filter_ridges`` sorts) and
+    exactly one more dimension, the time; its planes are taken in the order given, consecutive means adjacent index, nothing
+    is sorted along time.  A voxel is part of a ridge when it is ``!= 0`` and not NaN.  Two ridge voxels are linked when they
+    are neighbours in one plane (``connectivity`` 1: edges, 2: edges and corners; ``cyclic``: across the longitude seam too),
+    or lie in adjacent planes at most ``reach`` pixels apart in both latitude and longitude index (``cyclic``: the longitude
+    offset the shorter way round); ``reach`` is an integer in 0 .. 16, 0 meaning the same pixel.  A track is a connected
+    component of that relation: ridges that MERGE or SPLIT therefore belong to one track, which is not cut where they meet.
+    A thinned ridge moves, so ``reach`` should be about its displacement per time step in pixels (or dilate first).
+
+    Returns int32 track ids in the caller's class and dimension order: 0 off the ridges, else ``1..N`` in the order of each
+    track's first voxel in ``(time, latitude, longitude)`` raster order.  Tracks that occupy fewer than ``min_duration``
+    consecutive-index planes (``last - first + 1``) become 0 and the survivors are renumbered ``1..M`` in the same order.
+    ``return_table=True`` also returns a dict of numpy arrays with one entry per surviving track: ``first``, ``last`` (plane
+    indices), ``duration``, ``volume`` (voxels), and ``first_time``, ``last_time``, the time coordinate's labels there."""
+    eng, record, out, time, connectivity, reach, min_duration = _ridge_record(ridges, connectivity, reach, min_duration)
+    torch = eng.torch
+    labels, count = eng.label_tracks(record, connectivity, cyclic, reach)
+    spans = eng.track_spans(labels, count)
+    keep = (spans["volume"] > 0) & (spans["duration"] >= min_duration)
+    # new id of every old one: the running count of the kept tracks, 0 for a dropped one and for the background
+    new_id = torch.where(keep, torch.cumsum(keep.to(torch.int32), 0, dtype=torch.int32), torch.zeros_like(spans["first"]))
+    table = torch.cat([torch.zeros((1,), dtype=torch.int32, device=new_id.device), new_id])
+    ids = table.gather(0, labels.reshape(-1).to(torch.int64)).reshape(labels.shape)
+    if not return_table:
+        return out(ids)
+    kept = {k: _to_np(spans[k][keep]) for k in ("first", "last", "duration", "volume")}
+    kept["first_time"], kept["last_time"] = np.asarray(time)[kept["first"]], np.asarray(time)[kept["last"]]
+    return out(ids), kept
+
+
+def persistent_ridges(ridges, min_duration, reach=1, connectivity=2, cyclic=False, fill=0.0):
+    """Keep the ridges that last: ``filter_ridges``' convention along time (``Engine.filter_tracks``).  The input's value on
+    the voxels of tracks that occupy at least ``min_duration`` planes, ``fill`` elsewhere (on the background too), in the
+    caller's class, dimension order and dtype.  ``ridges``, ``reach``, ``connectivity``, ``cyclic`` and what a track is: as
+    for ``track_ridges`` -- a short-lived ridge that merges into a lasting one is part of its track and stays."""
+    eng, record, out, _, connectivity, reach, min_duration = _ridge_record(ridges, connectivity, reach, min_duration)
+    return out(eng.filter_tracks(record, min_duration=min_duration, connectivity=connectivity, cyclic=cyclic, reach=reach, fill=fill),
+               keep_dtype=True)
 
 
 def _local_threshold(da, block_size, method, offset, mode, param, cyclic, want):
