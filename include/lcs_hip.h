@@ -724,6 +724,55 @@ typedef struct lc_component_sums_args {
 } lc_component_sums_args;
 int lc_component_sums(lc_ctx *ctx, const lc_component_sums_args *args);
 
+/* The same per label ON THE SPHERE: area-weighted moment sums and the properties that follow from them, so that a filter or a
+ * table measures a ridge in square metres and metres, not in pixels whose size shrinks with cos(latitude).  Added at
+ * LC_VERSION 104 without a bump: nothing that existed changed.
+ *   labels       int32 [n_members][ny*nx]; any label map with values in 0 .. counts[m] (it need not be connected: the owner map
+ *                of a distance transform and track ids are valid); 0, negative values and labels above min(counts[m], n_max) are
+ *                not measured
+ *   tables       float64 on the device: cos_lat, sin_lat, row_weight [ny]; cos_lon, sin_lon, col_weight [nx].  Node (r, c) is the
+ *                unit vector n = (fl(cos_lat[r] cos_lon[c]), fl(cos_lat[r] sin_lon[c]), sin_lat[r]) as in lc_sphere_distance, its
+ *                cell has the area w = fl(row_weight[r] col_weight[c]) in steradians; no kernel evaluates a trigonometric
+ *                function of a coordinate.
+ *   root_out     int32: the label's first pixel in raster order (-1: no pixel of that label in the plane), as lc_component_sums
+ *   sums_out     float64 [11][n_members][n_max]: with d = fl(n - n(root)) per axis, the sums over the label's pixels of
+ *                w | w dx, w dy, w dz | w dx dx, w dx dy, w dx dz, w dy dy, w dy dz, w dz dz | w v -- every term formed as
+ *                fl(fl(w d_i) d_j), every operation rounded once to float64 and nothing fused, so a host restatement forms the
+ *                same terms bit for bit.  The ORDER of the sum is not fixed (float64 atomic adds): last bits may differ from
+ *                run to run.  The eleventh plane (w v) is 0 without an intensity.  Offsets about the root: nothing large is
+ *                subtracted from anything large.
+ *   max_out, min_out  float64: extrema of the intensity, exact; NaN if the label holds a NaN (its w v sum is NaN too); NULL
+ *                allowed without an intensity
+ *   props_out    float64 [8][n_members][n_max], or NULL.  With W, M1, M2, S the sums above, m = M1 / W, C = M2 / W - m m^T and
+ *                e1 >= e2 >= e3 the eigenvalues of C (cyclic Jacobi, a fixed number of sweeps), v the eigenvector of e1:
+ *                  0 area               radius^2 W
+ *                  1 major_axis_length  4 radius sqrt(max(e1, 0))   the regionprops formula on chords: it saturates for
+ *                  2 minor_axis_length  4 radius sqrt(max(e2, 0))   labels that are not small against the sphere
+ *                  3 centroid_latitude  degrees, of the direction c = n(root) + m: asin(c_z / |c|), evaluated as
+ *                                       atan2(c_z, hypot(c_x, c_y)) so that it keeps its accuracy at the poles
+ *                  4 centroid_longitude degrees(atan2(c_y, c_x)); both NaN when |c| < 1e-6
+ *                  5 orientation        degrees(atan2(v . north, v . east)) at the centroid, folded into (-90, 90]: 0 zonal, 90
+ *                                       meridional, positive from SW to NE; NaN unless e1 > 0 (one pixel) and where the
+ *                                       centroid is NaN
+ *                  6 mean_intensity     S / W (area-weighted)        7 total_intensity  radius^2 S      (NaN without an intensity)
+ *                Entries past a plane's count and labels without a pixel in the plane: area 0, everything else NaN.
+ * A null context or argument structure, a wrong struct_size, ny, nx, n_members or n_max below 1, a dtype other than LC_F32 /
+ * LC_F64 (of the intensity; not read without one, but still checked) and a radius that is not positive and finite are refused
+ * with LC_EINVAL before any HIP call.  No kernel of this call waits for another workgroup. */
+typedef struct lc_component_sphere_sums_args {
+    size_t struct_size; /* sizeof(lc_component_sphere_sums_args): checked before any other field */
+    const void *labels; /* int32 [n_members][ny*nx] */
+    const void *counts; /* int32 [n_members] */
+    const void *intensity; /* `dtype` elements [n_members][ny*nx], or NULL */
+    int dtype, ny, nx, n_members;
+    int n_max; /* capacity per plane of every output */
+    const double *cos_lat, *sin_lat, *row_weight; /* device, [ny] */
+    const double *cos_lon, *sin_lon, *col_weight; /* device, [nx] */
+    double radius;                                /* > 0, finite */
+    void *root_out, *sums_out, *max_out, *min_out, *props_out;
+} lc_component_sphere_sums_args;
+int lc_component_sphere_sums(lc_ctx *ctx, const lc_component_sphere_sums_args *args);
+
 /* mask_out[p] = mask[p] where keep[m][label[p]-1] != 0, else fill (on background pixels and on labels above n_max too).
  * keep: uint8 [n_members][n_max]; mask, mask_out: `dtype` elements, two distinct buffers. */
 int lc_component_apply(lc_ctx *ctx, const void *labels, const void *mask, int dtype, int ny, int nx, int n_members,

@@ -158,6 +158,21 @@ PROTOTYPES["lc_component_sums"] = (_i, [_vp, C.POINTER(ComponentSumsArgs)])
 PROTOTYPES["lc_component_apply"] = (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _d, _vp])
 
 
+class ComponentSphereSumsArgs(C.Structure):
+    """``lc_component_sphere_sums_args`` of include/lcs_hip.h, field for field."""
+    _fields_ = [("struct_size", _sz),
+                ("labels", _vp), ("counts", _vp), ("intensity", _vp),
+                ("dtype", _i), ("ny", _i), ("nx", _i), ("n_members", _i),
+                ("n_max", _i),
+                ("cos_lat", _vp), ("sin_lat", _vp), ("row_weight", _vp),
+                ("cos_lon", _vp), ("sin_lon", _vp), ("col_weight", _vp),
+                ("radius", _d),
+                ("root_out", _vp), ("sums_out", _vp), ("max_out", _vp), ("min_out", _vp), ("props_out", _vp)]
+
+
+PROTOTYPES["lc_component_sphere_sums"] = (_i, [_vp, C.POINTER(ComponentSphereSumsArgs)])
+
+
 class TrackSpansArgs(C.Structure):
     """``lc_track_spans_args`` of include/lcs_hip.h, field for field."""
     _fields_ = [("struct_size", _sz),

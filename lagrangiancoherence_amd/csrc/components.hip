@@ -14,6 +14,10 @@
 //   rank     every tile scans its own root flags again, adds its offset: the root of rank k holds -(k + 2)
 //   relabel  label = 0 on background, rank of the root + 1 elsewhere: 1..N in the order of the first pixels, which is the
 //            numbering scipy.ndimage.label gives
+// The sums come twice: exact integer moments in index units (lc_component_sums), and float64 moments of the nodes' unit vectors
+// weighted by cell area (lc_component_sphere_sums), from which one thread per label derives area, axis lengths, centroid and
+// orientation on the sphere (tools.ridge_properties, filter_ridges(metric='sphere'); pinned against a numpy restatement in
+// tests/test_sphere_props_gpu.py).
 // No kernel waits for another workgroup: there is no flag, no look-back and no grid synchronisation anywhere in this file --
 // what one stage needs from all workgroups of the stage before is handed over by the end of that launch.  The atomics are
 // ordinary ones in plain C++.
@@ -366,6 +370,217 @@ __global__ void cs_finish_roots_kernel(int *root, size_t n) {
         if (root[i] == INT_MAX) root[i] = -1;
 }
 
+// ------------------------------------------------------------------ area-weighted sums on the sphere
+// The same walk as cs_sums_kernel with float64 sums: node (r, c) is the unit vector n = (fl(cl[r] cx[c]), fl(cl[r] sx[c]), sl[r]),
+// d = fl(n - n(root)) per axis, w = fl(rw[r] cw[c]); the terms are w, fl(w d_i), fl(fl(w d_i) d_j) (i <= j) and fl(w v).  Nothing is
+// contracted, so a host restatement forms the same terms bit for bit; the order of the sum is the only freedom (atomicAdd(double)).
+constexpr int SP_SUMS = 11;      // W, M1 x y z, M2 xx xy xz yy yz zz, S
+constexpr int SP_PROPS = 8;      // area, major, minor, centroid latitude, centroid longitude, orientation, mean, total
+constexpr int SP_SWEEPS = 8;     // cyclic Jacobi sweeps of the 3 x 3 solve: it converges quadratically, 5 leave nothing to rotate
+
+struct SphereTables {
+    const double *cl, *sl, *rw;   // [ny]
+    const double *cx, *sx, *cw;   // [nx]
+};
+
+struct SphereOut {
+    int *root;                        // [n_members][n_max]
+    double *sums;                     // [SP_SUMS][n_members][n_max]
+    unsigned long long *kmax, *kmin;  // order keys while the sums run, doubles after sp_finish_kernel; NULL without an intensity
+    double *props;                    // [SP_PROPS][n_members][n_max], or NULL
+};
+
+__global__ void sp_init_kernel(SphereOut o, size_t n) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        o.root[i] = INT_MAX;
+        for (int k = 0; k < SP_SUMS; ++k) o.sums[k * n + i] = 0.0;
+        if (o.kmax) {
+            o.kmax[i] = 0ull;
+            o.kmin[i] = ~0ull;
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(CC_THREADS) void sp_sums_kernel(const int *__restrict__ labels_all, const T *__restrict__ intensity_all,
+                                                            int nx, int npix, int tiles, const int *__restrict__ counts, int n_max,
+                                                            size_t n_slots, SphereTables g, SphereOut o) {
+#pragma clang fp contract(off)
+    const int m = blockIdx.x / tiles;
+    const Tile w = tile_of_block(tiles, npix, CS_TILE);
+    const int *labels = labels_all + w.base;
+    const T *intensity = intensity_all ? intensity_all + w.base : nullptr;
+    const int cap = plane_capacity(counts, m, n_max);
+    int cur = 0;
+    double x0 = 0.0, y0 = 0.0, z0 = 0.0;   // the node of the root of `cur`
+    double acc[SP_SUMS];
+#pragma unroll
+    for (int k = 0; k < SP_SUMS; ++k) acc[k] = 0.0;
+    unsigned long long kmax = 0ull, kmin = ~0ull;
+    auto flush = [&]() {   // atomics only: no arithmetic of the sums happens in here
+        if (!cur) return;
+        const size_t i = (size_t)m * n_max + (cur - 1);
+        atomicAdd(o.sums + i, acc[0]);
+#pragma unroll
+        for (int k = 1; k < SP_SUMS - 1; ++k)
+            if (acc[k] != 0.0) atomicAdd(o.sums + k * n_slots + i, acc[k]);   // a NaN is != 0; the root pixel itself adds nothing
+        if (intensity) {
+            atomicAdd(o.sums + (SP_SUMS - 1) * n_slots + i, acc[SP_SUMS - 1]);
+            atomicMax(o.kmax + i, kmax);
+            atomicMin(o.kmin + i, kmin);
+        }
+    };
+    const long long p0 = (long long)w.p0 + (long long)threadIdx.x * CS_ITEMS;
+    for (int k = 0; k < CS_ITEMS; ++k) {
+        const long long pl = p0 + k;
+        if (pl >= npix) break;
+        const int p = (int)pl, l = labels[p];
+        if (l < 1 || l > cap) continue;
+        if (l != cur) {
+            flush();
+            cur = l;
+            const int root = o.root[(size_t)m * n_max + (l - 1)];   // a pixel of the plane: cs_root_kernel saw this label
+            const int rr = root / nx, rc = root - rr * nx;
+            const double c = g.cl[rr];
+            x0 = c * g.cx[rc];
+            y0 = c * g.sx[rc];
+            z0 = g.sl[rr];
+#pragma unroll
+            for (int j = 0; j < SP_SUMS; ++j) acc[j] = 0.0;
+            kmax = 0ull;
+            kmin = ~0ull;
+        }
+        const int r = p / nx, c = p - r * nx;
+        const double clr = g.cl[r];
+        const double dx = clr * g.cx[c] - x0, dy = clr * g.sx[c] - y0, dz = g.sl[r] - z0;
+        const double wt = g.rw[r] * g.cw[c];
+        const double wx = wt * dx, wy = wt * dy, wz = wt * dz;
+        acc[0] += wt;
+        acc[1] += wx;
+        acc[2] += wy;
+        acc[3] += wz;
+        acc[4] += wx * dx;
+        acc[5] += wx * dy;
+        acc[6] += wx * dz;
+        acc[7] += wy * dy;
+        acc[8] += wy * dz;
+        acc[9] += wz * dz;
+        if (intensity) {
+            const double v = (double)intensity[p];
+            acc[10] += wt * v;
+            if (v != v) {   // a NaN is the largest and the smallest of its component
+                kmax = ~0ull;
+                kmin = 0ull;
+            } else {
+                const unsigned long long key = order_key(v);
+                if (key > kmax) kmax = key;
+                if (key < kmin) kmin = key;
+            }
+        }
+    }
+    flush();
+}
+
+// one rotation of the cyclic Jacobi method on the symmetric 3 x 3 `a`: it zeroes a[P][Q]; R is the third index.  v collects
+// the rotations: its columns become the eigenvectors.  No data-dependent loop; an element that is 0 already is left alone.
+template <int P, int Q, int R>
+__device__ __forceinline__ void jacobi_rotate(double (&a)[3][3], double (&v)[3][3]) {
+    const double apq = a[P][Q];
+    if (apq == 0.0) return;
+    const double theta = (a[Q][Q] - a[P][P]) / (2.0 * apq);
+    // the smaller root of t^2 + 2 theta t - 1: |t| <= 1; a theta whose square overflows gives t = 0
+    const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + __dsqrt_rn(theta * theta + 1.0));
+    const double c = 1.0 / __dsqrt_rn(t * t + 1.0), s = t * c;
+    a[P][P] -= t * apq;
+    a[Q][Q] += t * apq;
+    a[P][Q] = a[Q][P] = 0.0;
+    const double arp = a[R][P], arq = a[R][Q];
+    a[R][P] = a[P][R] = c * arp - s * arq;
+    a[R][Q] = a[Q][R] = s * arp + c * arq;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double vp = v[k][P], vq = v[k][Q];
+        v[k][P] = c * vp - s * vq;
+        v[k][Q] = s * vp + c * vq;
+    }
+}
+
+// One thread per (plane, label): keys back to doubles, the sums into properties.
+__global__ __launch_bounds__(CC_THREADS) void sp_finish_kernel(SphereOut o, size_t n, int nx, double radius, SphereTables g) {
+    const double nan = __longlong_as_double(0x7ff8000000000000ll), deg = 57.29577951308232;   // 180 / pi
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        if (o.kmax) {
+            const unsigned long long kx = o.kmax[i], kn = o.kmin[i];
+            ((double *)o.kmax)[i] = key_value(kx);
+            ((double *)o.kmin)[i] = key_value(kn);
+        }
+        const int root = o.root[i];
+        const bool empty = root == INT_MAX;
+        if (empty) o.root[i] = -1;   // no such label in this plane
+        if (!o.props) continue;
+        double *q = o.props + i;
+        if (empty) {
+            q[0] = 0.0;
+            for (int k = 1; k < SP_PROPS; ++k) q[k * n] = nan;
+            continue;
+        }
+        const double *s = o.sums + i;
+        const double W = s[0];
+        const double mx = s[1 * n] / W, my = s[2 * n] / W, mz = s[3 * n] / W;
+        double a[3][3], v[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+        a[0][0] = s[4 * n] / W - mx * mx;
+        a[0][1] = a[1][0] = s[5 * n] / W - mx * my;
+        a[0][2] = a[2][0] = s[6 * n] / W - mx * mz;
+        a[1][1] = s[7 * n] / W - my * my;
+        a[1][2] = a[2][1] = s[8 * n] / W - my * mz;
+        a[2][2] = s[9 * n] / W - mz * mz;
+#pragma unroll 1
+        for (int sweep = 0; sweep < SP_SWEEPS; ++sweep) {
+            jacobi_rotate<0, 1, 2>(a, v);
+            jacobi_rotate<0, 2, 1>(a, v);
+            jacobi_rotate<1, 2, 0>(a, v);
+        }
+        // e1 >= e2 >= e3 and the eigenvector of e1, by selects: no indexing by a value
+        const double d0 = a[0][0], d1 = a[1][1], d2 = a[2][2];
+        const int i1 = (d0 >= d1 && d0 >= d2) ? 0 : (d1 >= d2 ? 1 : 2);
+        const double e1 = i1 == 0 ? d0 : (i1 == 1 ? d1 : d2);
+        const double ra = i1 == 0 ? d1 : d0, rb = i1 == 2 ? d1 : d2;   // the other two
+        const double e2 = ra >= rb ? ra : rb;
+        const double vx = i1 == 0 ? v[0][0] : (i1 == 1 ? v[0][1] : v[0][2]);
+        const double vy = i1 == 0 ? v[1][0] : (i1 == 1 ? v[1][1] : v[1][2]);
+        const double vz = i1 == 0 ? v[2][0] : (i1 == 1 ? v[2][1] : v[2][2]);
+        const double r2 = radius * radius;
+        q[0] = r2 * W;
+        q[1 * n] = 4.0 * radius * __dsqrt_rn(e1 > 0.0 ? e1 : (e1 == e1 ? 0.0 : e1));
+        q[2 * n] = 4.0 * radius * __dsqrt_rn(e2 > 0.0 ? e2 : (e2 == e2 ? 0.0 : e2));
+        // the centroid: the root's node plus the mean offset, as a direction
+        const int rr = root / nx, rc = root - rr * nx;
+        const double cx = g.cl[rr] * g.cx[rc] + mx, cy = g.cl[rr] * g.sx[rc] + my, cz = g.sl[rr] + mz;
+        const double h = __dsqrt_rn(cx * cx + cy * cy), rho = __dsqrt_rn(cx * cx + cy * cy + cz * cz);
+        double lat = nan, lon = nan, orient = nan;
+        if (rho >= 1e-6) {
+            lat = atan2(cz, h);   // asin(cz / rho), in the form that keeps its accuracy at the poles
+            lon = atan2(cy, cx);
+            if (e1 > 0.0) {
+                const double sphi = sin(lat), cphi = cos(lat), slam = sin(lon), clam = cos(lon);
+                const double ve = vy * clam - vx * slam;
+                const double vn = vz * cphi - sphi * (vx * clam + vy * slam);
+                double t = atan2(vn, ve) * deg;   // (-180, 180]: the axis has no sign, fold into (-90, 90]
+                if (t > 90.0) t -= 180.0;
+                else if (t <= -90.0) t += 180.0;
+                orient = t;
+            }
+            lat *= deg;
+            lon *= deg;
+        }
+        q[3 * n] = lat;
+        q[4 * n] = lon;
+        q[5 * n] = orient;
+        q[6 * n] = o.kmax ? s[10 * n] / W : nan;
+        q[7 * n] = o.kmax ? r2 * s[10 * n] : nan;
+    }
+}
+
 // ------------------------------------------------------------------ apply
 template <typename T>
 __global__ __launch_bounds__(CC_THREADS) void cc_apply_kernel(const int *__restrict__ labels, const T *__restrict__ mask,
@@ -476,6 +691,47 @@ extern "C" int lc_component_sums(lc_ctx *ctx, const lc_component_sums_args *a) {
         hipLaunchKernelGGL(cs_finish_kernel, dim3(grid_cap(n_slots)), block, 0, ctx->stream, o, n_slots);
     else
         hipLaunchKernelGGL(cs_finish_roots_kernel, dim3(grid_cap(n_slots)), block, 0, ctx->stream, o.root, n_slots);
+    LC_HIP_CHECK(hipGetLastError());
+    return LC_OK;
+}
+
+extern "C" int lc_component_sphere_sums(lc_ctx *ctx, const lc_component_sphere_sums_args *a) {
+    const char *who = "lc_component_sphere_sums";
+    LC_REQUIRE(ctx, "%s: null context", who);
+    LC_REQUIRE(a, "%s: null argument structure", who);
+    LC_REQUIRE(a->struct_size == sizeof(lc_component_sphere_sums_args), "%s: struct_size %zu, this library has %zu", who,
+               (size_t)a->struct_size, sizeof(lc_component_sphere_sums_args));
+    int tiles = 0, tiles_root = 0;
+    int st = components_geometry(who, ctx, a->dtype, a->ny, a->nx, a->n_members, CS_TILE, &tiles);
+    if (st == LC_OK) st = components_geometry(who, ctx, a->dtype, a->ny, a->nx, a->n_members, CC_TILE, &tiles_root);
+    if (st != LC_OK) return st;
+    LC_REQUIRE(a->n_max >= 1, "%s: bad capacity n_max=%d (>= 1)", who, a->n_max);
+    LC_REQUIRE(a->radius > 0.0 && a->radius < INFINITY, "%s: bad radius %g: > 0 and finite", who, a->radius);
+    LC_REQUIRE(a->labels && a->counts && a->root_out && a->sums_out, "%s: null pointer", who);
+    LC_REQUIRE(a->cos_lat && a->sin_lat && a->row_weight && a->cos_lon && a->sin_lon && a->col_weight, "%s: null pointer (six tables)", who);
+    LC_REQUIRE(!a->intensity || (a->max_out && a->min_out), "%s: null pointer (an intensity needs max_out and min_out)", who);
+    LC_HIP_CHECK(hipSetDevice(ctx->device));
+    const int npix = a->ny * a->nx;
+    const size_t n_slots = (size_t)a->n_members * (size_t)a->n_max;
+    SphereOut o;
+    o.root = (int *)a->root_out;
+    o.sums = (double *)a->sums_out;
+    o.kmax = a->intensity ? (unsigned long long *)a->max_out : nullptr;
+    o.kmin = a->intensity ? (unsigned long long *)a->min_out : nullptr;
+    o.props = (double *)a->props_out;
+    const SphereTables g{a->cos_lat, a->sin_lat, a->row_weight, a->cos_lon, a->sin_lon, a->col_weight};
+    const dim3 block(CC_THREADS);
+    hipLaunchKernelGGL(sp_init_kernel, dim3(grid_cap(n_slots)), block, 0, ctx->stream, o, n_slots);
+    hipLaunchKernelGGL(cs_root_kernel, dim3((unsigned)(tiles_root * a->n_members)), block, 0, ctx->stream, (const int *)a->labels, a->nx,
+                       npix, tiles_root, (const int *)a->counts, a->n_max, o.root);
+    const dim3 grid((unsigned)(tiles * a->n_members));
+    if (a->dtype == LC_F32)
+        hipLaunchKernelGGL(sp_sums_kernel<float>, grid, block, 0, ctx->stream, (const int *)a->labels, (const float *)a->intensity, a->nx,
+                           npix, tiles, (const int *)a->counts, a->n_max, n_slots, g, o);
+    else
+        hipLaunchKernelGGL(sp_sums_kernel<double>, grid, block, 0, ctx->stream, (const int *)a->labels, (const double *)a->intensity, a->nx,
+                           npix, tiles, (const int *)a->counts, a->n_max, n_slots, g, o);
+    hipLaunchKernelGGL(sp_finish_kernel, dim3(grid_cap(n_slots)), block, 0, ctx->stream, o, n_slots, a->nx, a->radius, g);
     LC_HIP_CHECK(hipGetLastError());
     return LC_OK;
 }

@@ -1188,12 +1188,129 @@ class Engine:
             props.update(mean_intensity=torch.where(valid, s["sum"] / n, nan), max_intensity=s["max"], min_intensity=s["min"])
         return props if labels.dim() == 3 else {k: v[0] for k, v in props.items()}
 
-    def filter_components(self, mask, intensity, criteria, thresholds, connectivity=2, cyclic=False, fill=0.0):
+    # ------------------------------------------------------------------ the same on the sphere
+    SPHERE_PROPS = ("area", "major_axis_length", "minor_axis_length", "centroid_latitude", "centroid_longitude", "orientation",
+                    "mean_intensity", "total_intensity")      # the planes of lc_component_sphere_sums' props_out, in order
+    METRICS = ("index", "sphere")
+
+    @staticmethod
+    def sphere_cell_tables(lat, lon, cyclic=False):
+        """``(row_weight, col_weight)``: the exact areas of the cells of a latitude-longitude grid in steradians, in separable
+        form -- cell ``(r, c)`` has the area ``row_weight[r] * col_weight[c]`` on the unit sphere.  numpy on the host; no device
+        is touched.  ``lat`` / ``lon``: degrees, at least two each, finite, strictly ascending, ``|lat| <= 90``.
+
+        Latitude: the band edges are the midpoints between neighbouring latitudes, the two outer edges lie half the
+        neighbouring spacing beyond the first and last latitude, and all edges are clipped to ``[-90, 90]``; ``row_weight =
+        sin(top edge) - sin(bottom edge)``.  Longitude: the edges are the midpoints; without ``cyclic`` the outer edges lie half
+        the neighbouring spacing out, with ``cyclic`` the first and last cell share the gap ``lon[0] + 360 - lon[-1]`` (which
+        must be positive); ``col_weight`` is the width in radians.  On a global grid the weights sum to ``4 pi``."""
+        lat, lon = np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64)
+        if lat.ndim != 1 or lon.ndim != 1 or lat.size < 2 or lon.size < 2:
+            raise ValueError("lat and lon: one-dimensional, at least two values each (a cell needs a neighbour to have a width)")
+        if not (np.isfinite(lat).all() and np.isfinite(lon).all()):
+            raise ValueError("lat and lon: finite degrees")
+        if np.abs(lat).max() > 90.0:
+            raise ValueError(f"lat: within [-90, 90] degrees, got {lat.min()!r} .. {lat.max()!r}")
+        if not ((np.diff(lat) > 0).all() and (np.diff(lon) > 0).all()):
+            raise ValueError("lat and lon: strictly ascending")
+
+        def edges(x, first, last):
+            e = np.empty(x.size + 1)
+            e[1:-1] = (x[:-1] + x[1:]) / 2
+            e[0], e[-1] = x[0] - first / 2, x[-1] + last / 2
+            return e
+        ey = np.clip(edges(lat, lat[1] - lat[0], lat[-1] - lat[-2]), -90.0, 90.0)
+        sy = np.sin(ey * np.pi / 180)
+        if cyclic:
+            gap = lon[0] + 360.0 - lon[-1]
+            if not gap > 0:
+                raise ValueError(f"lon: with cyclic the axis must leave a gap before it closes: lon[0] + 360 - lon[-1] = {gap!r} (> 0)")
+            ex = edges(lon, gap, gap)
+        else:
+            ex = edges(lon, lon[1] - lon[0], lon[-1] - lon[-2])
+        return sy[1:] - sy[:-1], (ex[1:] - ex[:-1]) * np.pi / 180
+
+    def component_sphere_props(self, labels, counts, lat, lon, intensity=None, cyclic=False, radius=6371000.0, n_max=None,
+                               return_sums=False):
+        """Properties of every label of a label map measured ON THE SPHERE (``lc_component_sphere_sums``), as a dict of
+        float64 device tensors ``(n_max,)`` (``(n_members, n_max)`` for a stack; ``n_max`` None: the largest count, read back
+        from the device).  ``labels``: int32, as :meth:`label_components` returns them, or any other label map with values in
+        ``0..counts[m]`` -- it need not be connected.  ``lat`` ``(ny,)``, ``lon`` ``(nx,)``: degrees, as
+        :meth:`sphere_cell_tables` wants them; ``cyclic`` there decides the width of the outer columns only: on the sphere a
+        label that straddles the seam is in one piece without a flag.
+
+        Node ``(r, c)`` is the unit vector ``n = (cos lat cos lon, cos lat sin lon, sin lat)`` and has the cell area ``w =
+        row_weight[r] col_weight[c]`` (steradians).  With ``d = n - n(root)`` about the label's first pixel in raster order --
+        nothing large is subtracted from anything large -- the device sums ``W = sum w``, ``M1 = sum w d``, ``M2 = sum w d d^T``
+        and ``S = sum w v`` per label in float64; then ``m = M1 / W``, ``C = M2 / W - m m^T``, ``e1 >= e2 >= e3`` its
+        eigenvalues (cyclic Jacobi, a fixed number of sweeps) and ``v`` the eigenvector of ``e1``:
+
+        ``area`` = ``radius^2 W``; ``major_axis_length`` = ``4 radius sqrt(max(e1, 0))`` and ``minor_axis_length`` likewise of
+        ``e2``: for a ridge that is small against the sphere the regionprops formula of :meth:`component_props` in the unit of
+        ``radius``.  It measures CHORDS, so it saturates for planet-sized labels.  ``centroid_latitude``,
+        ``centroid_longitude``: degrees, of the direction ``c = n(root) + m`` (``asin(c_z / |c|)``, ``atan2(c_y, c_x)``), NaN
+        where ``|c| < 1e-6``.  ``orientation``: degrees, ``atan2(v . north, v . east)`` at the centroid folded into ``(-90,
+        90]`` -- 0 zonal, 90 meridional, positive from SW to NE; NaN for a single pixel (``e1 == 0``) and where the centroid
+        is.  With an ``intensity``: ``mean_intensity`` = ``S / W`` (area-weighted), ``total_intensity`` = ``radius^2 S``,
+        ``max_intensity``, ``min_intensity`` (exact); a NaN in the label makes all four NaN.  Entries past a plane's count
+        and labels without a pixel in the plane: ``area`` 0, everything else NaN.
+
+        The sums are float64 atomic adds whose order is not fixed: the last bits can differ from run to run (as those of
+        ``mean_intensity`` of :meth:`component_props` do).  ``return_sums``: also the raw ``root`` (int32), ``W``, ``M1``
+        ``(..., 3)``, ``M2`` ``(..., 6)``: xx, xy, xz, yy, yz, zz) and, with an intensity, ``S``."""
+        torch = self.torch
+        cl, sl, cx, sx, radius, _, _ = self.sphere_tables(lat, lon, radius)
+        rw, cw = self.sphere_cell_tables(lat, lon, cyclic)
+        lab = labels if labels.dim() == 3 else labels[None]
+        if lab.dtype != torch.int32 or not lab.is_contiguous():
+            raise ValueError("labels: a contiguous int32 tensor (what label_components returns)")
+        n, ny, nx = (int(s) for s in lab.shape)
+        if (ny, nx) != (cl.size, cx.size):
+            raise ValueError(f"labels {tuple(lab.shape)}: ny = len(lat) = {cl.size} and nx = len(lon) = {cx.size}")
+        if n_max is None:
+            n_max = int(counts.max().item())
+        n_max = max(1, int(n_max))
+        inten = None
+        if intensity is not None:
+            inten = self._planes(intensity)
+            if tuple(inten.shape) != (n, ny, nx):
+                raise ValueError("intensity and labels differ in shape")
+        root = torch.empty((n, n_max), dtype=torch.int32, device=self.device)
+        sums = self._empty((11, n, n_max), np.float64)
+        props = self._empty((len(self.SPHERE_PROPS), n, n_max), np.float64)
+        ext = self._empty((2, n, n_max), np.float64) if inten is not None else None
+        tables = [self.to_device(t, np.float64) for t in (cl, sl, rw, cx, sx, cw)]
+        a = _capi.ComponentSphereSumsArgs(struct_size=C.sizeof(_capi.ComponentSphereSumsArgs))
+        a.labels, a.counts, a.intensity = lab.data_ptr(), counts.data_ptr(), inten.data_ptr() if inten is not None else None
+        a.dtype = _NP2LC[np.dtype(str(inten.dtype).replace("torch.", ""))] if inten is not None else _capi.LC_F64
+        a.ny, a.nx, a.n_members, a.n_max = ny, nx, n, n_max
+        a.cos_lat, a.sin_lat, a.row_weight, a.cos_lon, a.sin_lon, a.col_weight = (t.data_ptr() for t in tables)
+        a.radius = radius
+        a.root_out, a.sums_out, a.props_out = root.data_ptr(), sums.data_ptr(), props.data_ptr()
+        if inten is not None:
+            a.max_out, a.min_out = ext[0].data_ptr(), ext[1].data_ptr()
+        self._use_current_stream()
+        _capi.check(self.lib.lc_component_sphere_sums(self.ctx, C.byref(a)), self.lib)
+        out = {k: props[i] for i, k in enumerate(self.SPHERE_PROPS) if inten is not None or not k.endswith("_intensity")}
+        if inten is not None:
+            out.update(max_intensity=ext[0], min_intensity=ext[1])
+        if return_sums:
+            out.update(root=root, W=sums[0], M1=sums[1:4].permute(1, 2, 0), M2=sums[4:10].permute(1, 2, 0))
+            if inten is not None:
+                out["S"] = sums[10]
+        return out if labels.dim() == 3 else {k: v[0] for k, v in out.items()}
+
+    def filter_components(self, mask, intensity, criteria, thresholds, connectivity=2, cyclic=False, fill=0.0, metric='index',
+                          lat=None, lon=None, radius=6371000.0):
         """``mask`` with every connected component that fails a threshold replaced by ``fill`` (background becomes ``fill``
         too): a component is kept when ``prop >= threshold`` for every ``(criterion, threshold)`` pair -- criteria from
         :attr:`COMPONENT_PROPS`, measured on ``intensity`` -- and a NaN property fails.  Label, sums and apply run on the
         device (``lc_label_components``, ``lc_component_sums``, ``lc_component_apply``); the counts are read back once in
-        between, to size the per-component arrays.  Returns a device tensor shaped and typed like ``mask``."""
+        between, to size the per-component arrays.  Returns a device tensor shaped and typed like ``mask``.
+
+        ``metric='index'`` (the default) measures in index units (:meth:`component_props`); ``metric='sphere'`` takes the same
+        criteria names from :meth:`component_sphere_props` on the grid ``lat``, ``lon`` (degrees): ``area`` in ``radius^2``,
+        the axis lengths in the unit of ``radius``, ``mean_intensity`` area-weighted."""
         criteria, thresholds = list(criteria), list(thresholds)
         if len(criteria) != len(thresholds):
             raise ValueError("criteria and thresholds differ in length")
@@ -1202,11 +1319,18 @@ class Engine:
                 raise ValueError(f"criterion {k!r}: one of {', '.join(self.COMPONENT_PROPS)}")
             if intensity is None and k.endswith("_intensity"):
                 raise ValueError(f"criterion {k!r} needs an intensity")
+        if metric not in self.METRICS:
+            raise ValueError(f"metric {metric!r}: 'index' or 'sphere'")
+        if metric == 'sphere' and (lat is None or lon is None):
+            raise ValueError("metric='sphere' needs lat and lon")
         torch = self.torch
         m = self._planes(mask)
         n, ny, nx = (int(s) for s in m.shape)
         labels, counts = self.label_components(m, connectivity, cyclic)
-        props = self.component_props(labels, counts, intensity, cyclic)
+        if metric == 'sphere':
+            props = self.component_sphere_props(labels, counts, lat, lon, intensity, cyclic, radius)
+        else:
+            props = self.component_props(labels, counts, intensity, cyclic)
         keep = props["area"] > 0
         for k, th in zip(criteria, thresholds):
             keep = keep & (props[k] >= float(th))          # a NaN compares False

@@ -18,6 +18,12 @@
 * ``track_ridges``                  the filter of LCS/area_of_influence.py:210-211 extended through time: space-time labels of a
                                     ridge series (which ridge is the same ridge as in the plane before, how long it lasts), and
                                     ``persistent_ridges``, the ridges that last at least so many planes (defined here)
+* ``ridge_properties``              the per-ridge table behind the filter, on the sphere (``metric='sphere'``: square metres, metres,
+                                    centroid and orientation in degrees, area-weighted intensities) or in index units; with
+                                    ``labelled=True`` of any label map: the areas of influence ``distance_to_ridges`` hands out --
+                                    whose per-zone totals are the driver's last step, LCS/area_of_influence.py's
+                                    ``np.sum(ridges_ * pr_)`` -- or the ids of ``track_ridges``.  ``filter_ridges(metric='sphere')``
+                                    decides on the same numbers (defined here)
 
 The remaining functions of that module (IDW regridding, harvesine, latlonsel) have no caller on the
 path.
@@ -31,7 +37,7 @@ from .engine import Engine, common_dtype
 
 __all__ = ["xr_map_coordinates", "fourth_order_derivative", "derivative_spherical_coords",
            "find_ridges_spherical_hessian", "filter_ridges", "distance_to_ridges", "skeletonize_ridges", "dilate_ridges",
-           "threshold_local", "above_local_threshold", "track_ridges", "persistent_ridges"]
+           "threshold_local", "above_local_threshold", "track_ridges", "persistent_ridges", "ridge_properties"]
 
 
 def xr_map_coordinates(da, new_x, new_y, isglobal=True, order=1):
@@ -174,7 +180,8 @@ def find_ridges_spherical_hessian(da, sigma=.5, scheme='first_order', tolerance_
             out(grad, "elements", ["ddadx", "ddady"]), out(angle))
 
 
-def filter_ridges(ridges, ftle, criteria, thresholds, verbose=True, connectivity=2, cyclic=False, fill=0.0):
+def filter_ridges(ridges, ftle, criteria, thresholds, verbose=True, connectivity=2, cyclic=False, fill=0.0, metric='index',
+                  radius=6371000.0):
     """Keep the connected components of ``ridges`` whose properties, measured on ``ftle``, reach the thresholds.
     The call LCS/area_of_influence.py:210-211 makes: ``filter_ridges(ridges, ftle, criteria=['mean_intensity',
     'major_axis_length'], thresholds=[1.2, 30])``.
@@ -189,7 +196,23 @@ def filter_ridges(ridges, ftle, criteria, thresholds, verbose=True, connectivity
     components and the background become ``fill``: ``fill=np.nan`` is the form the driver's next line expects
     (``ridges.where(~isnan(ridges), 0)``).  ``verbose`` is accepted for the driver's signature.
 
+    ``metric='index'`` (the default) is the driver's: its ``30`` is 30 pixels, about 830 km at the equator of a 0.25 degree
+    grid and about 415 km at 60 degrees; ``area`` counts pixels whose true size shrinks with ``cos(latitude)`` and
+    ``mean_intensity`` weights a polar pixel like an equatorial one.  ``metric='sphere'`` measures the same criteria names on
+    the array's own ``latitude`` and ``longitude`` (degrees, distinct, ``|latitude| <= 90``; ``cyclic`` also makes the first
+    and last longitude cells share the gap that closes the axis): ``area`` in ``radius^2`` (square metres on the default
+    Earth), the axis lengths in the unit of ``radius`` -- the driver's ``30`` becomes ``830e3`` --, ``mean_intensity``
+    weighted by cell area; ``max_intensity`` and ``min_intensity`` are the same in both.  ``Engine.component_sphere_props``
+    states every formula.  The lengths measure chords, so they saturate for ridges that are not small against the sphere;
+    the sums behind ``area``, the lengths and the mean are float64 atomic adds whose last bits can differ from run to run
+    (as those of the index metric's mean do), so a threshold should not sit within rounding of a ridge's value.
+
     Returns the filtered mask in the caller's class and dimension order, in ``ridges``' dtype (float64 unless float32)."""
+    if metric not in Engine.METRICS:
+        raise ValueError(f"metric {metric!r}: 'index' or 'sphere'")
+    for k in criteria:
+        if k not in Engine.COMPONENT_PROPS:
+            raise ValueError(f"criterion {k!r}: one of {', '.join(Engine.COMPONENT_PROPS)}")
     dims = tuple(ridges.dims)
     lead = [d for d in dims if d not in ("latitude", "longitude")]
     if len(lead) > 1 or len(dims) - len(lead) != 2:
@@ -201,18 +224,140 @@ def filter_ridges(ridges, ftle, criteria, thresholds, verbose=True, connectivity
     if not (np.array_equal(_coord(ftle, "latitude"), lat) and np.array_equal(_coord(ftle, "longitude"), lon)):
         raise ValueError("ridges and ftle differ in their coordinates")
     ilat, ilon = np.argsort(lat, kind="stable"), np.argsort(lon, kind="stable")
+    if metric == 'sphere':
+        _check_sphere_grid(lat[ilat], lon[ilon], cyclic, radius)
 
     def sorted_values(da):
         v = np.asarray(da.transpose(*order).values)
         v = v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)
         return np.ascontiguousarray(v[..., ilat, :][..., ilon])
     eng = get_engine()
-    out = eng.filter_components(sorted_values(ridges), sorted_values(ftle), criteria, thresholds, connectivity=connectivity,
-                                cyclic=cyclic, fill=fill)
+    if metric == 'sphere':
+        out = eng.filter_components(sorted_values(ridges), sorted_values(ftle), criteria, thresholds, connectivity=connectivity,
+                                    cyclic=cyclic, fill=fill, metric=metric, lat=lat[ilat], lon=lon[ilon], radius=radius)
+    else:
+        out = eng.filter_components(sorted_values(ridges), sorted_values(ftle), criteria, thresholds, connectivity=connectivity,
+                                    cyclic=cyclic, fill=fill)
     coords = {"latitude": lat[ilat], "longitude": lon[ilon]}
     if lead:
         coords[lead[0]] = _coord(ridges, lead[0])
     return _make(ridges, _to_np(out), order, coords, getattr(ridges, "name", None)).transpose(*dims)
+
+
+def _check_sphere_grid(lat, lon, cyclic, radius):
+    """Every refusal of the sphere metric's coordinates and radius (``ValueError``), on the host: no engine is needed."""
+    Engine.sphere_tables(lat, lon, radius)
+    Engine.sphere_cell_tables(lat, lon, cyclic)
+
+
+def ridge_properties(ridges, intensity=None, connectivity=2, cyclic=False, metric='sphere', radius=6371000.0, labelled=False):
+    """The table of the ridges of a mask: where each one is, how large, how long, how it is oriented and how intense --
+    what ``filter_ridges`` measures to make its yes / no decision, handed out.  Returns ``(labels, table)``.
+
+    ``ridges`` is a labelled array over ``latitude`` and ``longitude`` (sorted ascending here, as ``filter_ridges`` sorts),
+    2-D, or 3-D with one more dimension (time, member): every plane is then measured on its own, all of them in the same
+    kernel launches.  ``labelled=False``: ``ridges`` is a mask; a pixel is part of a ridge when it is ``!= 0`` and not NaN,
+    and the ridges of each plane are its connected components (``Engine.label_components``: ``connectivity`` 1 edges, 2 edges
+    and corners; ``cyclic``: across the longitude seam too), numbered ``1..N`` in the order of their first pixel.
+    ``labelled=True``: ``ridges`` already holds labels -- the owner map of ``distance_to_ridges(return_labels=True)``, whose
+    areas of influence with a rain field as ``intensity`` give the driver's per-zone totals (``np.sum(ridges_ * pr_)``), or
+    the ids of ``track_ridges``.  Positive whole numbers up to ``2^31 - 1`` are labels; 0, negative values and NaN are
+    background; a positive non-integer raises ``ValueError``; a label need not be connected.  Every plane is measured on its
+    own, so track ids give one row per track AND plane: the track's path and intensity through time.
+
+    ``intensity``: a second field over the same dims and coordinates, or None.
+
+    ``labels``: int32, in the caller's class and dimension order.  ``table``: a dict of 1-D numpy arrays of equal length, one
+    row per (plane, label) that has at least one pixel, ordered by plane and then by label: ``plane`` (the index along the
+    extra dimension, 0 for 2-D input), ``label``, ``area``, ``major_axis_length``, ``minor_axis_length`` and, with an
+    ``intensity``, ``mean_intensity``, ``max_intensity``, ``min_intensity``, ``total_intensity`` (a NaN in a ridge makes all
+    four NaN).
+
+    ``metric='sphere'`` (the default) measures on the array's own coordinates (degrees, distinct, ``|latitude| <= 90``;
+    ``Engine.component_sphere_props`` states every rounding).  Each pixel is the unit vector ``n`` of its node and carries
+    the exact area ``w`` of its cell in steradians (band edges at the midpoints between neighbouring coordinates, the outer
+    ones half a spacing out and clipped at the poles; with ``cyclic`` the first and last longitude cells share the gap that
+    closes the axis).  With ``m`` the ``w``-weighted mean of ``n`` about the ridge's first pixel, ``C`` the weighted
+    covariance of ``n`` and ``e1 >= e2 >= e3`` its eigenvalues: ``area`` = ``radius^2 sum w`` (square metres on the default
+    Earth); ``major_axis_length`` = ``4 radius sqrt(e1)``, ``minor_axis_length`` = ``4 radius sqrt(e2)`` -- for a ridge that
+    is small against the sphere the regionprops formula of the index metric, in the unit of ``radius``; they measure CHORDS
+    and so saturate for planet-sized ridges --; ``centroid_latitude``, ``centroid_longitude``: degrees, the direction of the
+    weighted mean of ``n`` (NaN where that mean is shorter than ``1e-6``: a ridge spread evenly round the globe has no
+    centre); ``orientation``: degrees in ``(-90, 90]``, the angle of the eigenvector of ``e1`` from east towards north at
+    the centroid -- 0 zonal, 90 meridional, positive from SW to NE; NaN for a single pixel; ``mean_intensity`` is weighted by
+    cell area and ``total_intensity`` = ``radius^2 sum w v``, the area integral of the field over the ridge.  The sums are
+    float64 atomic adds whose order is not fixed: the last bits of every float column can differ from run to run.
+
+    ``metric='index'``: ``Engine.component_props``' values in index units, ``centroid_row`` and ``centroid_column`` (of the
+    sorted array) instead of the three columns of the sphere, and ``total_intensity`` the plain sum (its last bits, and the
+    mean's, can differ from run to run as well)."""
+    if metric not in Engine.METRICS:
+        raise ValueError(f"metric {metric!r}: 'index' or 'sphere'")
+    if connectivity not in (1, 2):
+        raise ValueError(f"connectivity {connectivity!r}: 1 (edges) or 2 (edges and corners)")
+    dims = tuple(ridges.dims)
+    lead = [d for d in dims if d not in ("latitude", "longitude")]
+    if len(lead) > 1 or len(dims) - len(lead) != 2:
+        raise ValueError("ridges: dims (latitude, longitude) and at most one more")
+    order = (*lead, "latitude", "longitude")
+    lat, lon = _coord(ridges, "latitude"), _coord(ridges, "longitude")
+    if intensity is not None:
+        if set(intensity.dims) != set(dims):
+            raise ValueError("ridges and intensity differ in their dims")
+        if not (np.array_equal(_coord(intensity, "latitude"), lat) and np.array_equal(_coord(intensity, "longitude"), lon)):
+            raise ValueError("ridges and intensity differ in their coordinates")
+    ilat, ilon = np.argsort(lat, kind="stable"), np.argsort(lon, kind="stable")
+    if metric == 'sphere':
+        _check_sphere_grid(lat[ilat], lon[ilon], cyclic, radius)
+
+    def sorted_values(da, keep=(np.float32, np.float64)):
+        v = np.asarray(da.transpose(*order).values)
+        v = v if v.dtype in keep else v.astype(np.float64)
+        return np.ascontiguousarray(v[..., ilat, :][..., ilon])
+    if labelled:
+        v = sorted_values(ridges, keep=(np.float64,))          # every int32 and float32 is a float64
+        positive = v > 0                                       # False on NaN
+        if (v[positive] != np.floor(v[positive])).any():
+            raise ValueError("ridges: with labelled=True every positive value is a whole number (a label)")
+        if positive.any() and v[positive].max() > 2 ** 31 - 1:
+            raise ValueError("ridges: with labelled=True labels are at most 2^31 - 1")
+        host_labels = np.where(positive, v, 0).astype(np.int32)
+    else:
+        v = sorted_values(ridges)
+    w = None if intensity is None else sorted_values(intensity)
+    eng = get_engine()
+    torch = eng.torch
+    if labelled:
+        labels = torch.from_numpy(host_labels).to(eng.device).contiguous()
+        counts = labels.reshape(1 if labels.dim() == 2 else labels.shape[0], -1).amax(dim=1).to(torch.int32)
+    else:
+        labels, counts = eng.label_components(eng.to_device(v, v.dtype), connectivity, cyclic)
+    if w is not None:
+        w = eng.to_device(w, w.dtype)
+    if metric == 'sphere':
+        props = eng.component_sphere_props(labels, counts, lat[ilat], lon[ilon], w, cyclic, radius)
+        names = [k for k in ("area", "major_axis_length", "minor_axis_length", "mean_intensity", "max_intensity", "min_intensity",
+                             "total_intensity", "centroid_latitude", "centroid_longitude", "orientation") if k in props]
+    else:
+        props = eng.component_props(labels, counts, w, cyclic)
+        props["centroid_row"], props["centroid_column"] = props["centroid"][..., 0], props["centroid"][..., 1]
+        names = ["area", "major_axis_length", "minor_axis_length"]
+        if w is not None:
+            props["total_intensity"] = torch.where(props["area"] > 0, eng.component_sums(labels, counts, w, cyclic)["sum"].reshape(
+                props["area"].shape), torch.full_like(props["mean_intensity"], float("nan")))
+            names += ["mean_intensity", "max_intensity", "min_intensity", "total_intensity"]
+        names += ["centroid_row", "centroid_column"]
+    area = _to_np(props["area"])
+    area = area if area.ndim == 2 else area[None]
+    plane, index = np.nonzero(area > 0)                        # by plane, then by label
+    table = {"plane": plane.astype(np.int64), "label": (index + 1).astype(np.int32)}
+    for k in names:
+        col = _to_np(props[k])
+        table[k] = (col if col.ndim == 2 else col[None])[plane, index]
+    coords = {"latitude": lat[ilat], "longitude": lon[ilon]}
+    if lead:
+        coords[lead[0]] = _coord(ridges, lead[0])
+    return _make(ridges, _to_np(labels), order, coords, getattr(ridges, "name", None)).transpose(*dims), table
 
 
 def distance_to_ridges(ridges, cyclic=False, sampling=None, max_distance=None, return_labels=False, connectivity=2,
