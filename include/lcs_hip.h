@@ -946,6 +946,101 @@ typedef struct lc_morph_args {
 } lc_morph_args;
 int lc_mask_morphology(lc_ctx *ctx, const lc_morph_args *args);
 
+/* ---- thinned ridges as ordered lines (trace_lines, ridge_lines) --------------------------
+ * The vector form of a one-pixel-wide mask: which pixels make up each ridge line and in which order, where lines end and branch,
+ * and how long they are on the sphere.  Nothing in the reference computes it (its chain, LCS/area_of_influence.py, ends at
+ * rasters), so the meaning is fixed here; tests/lines.py restates it as a plain pixel walk.  Added at LC_VERSION 104 without a
+ * bump: nothing that existed changed.  n_members independent planes [n_members][ny*nx] per call.
+ *
+ * Foreground: as above, a pixel whose value is != 0 and not NaN; mask: `dtype` elements, LC_F32 or LC_F64.  cyclic_x != 0: column
+ * nx-1 is the western neighbour of column 0; it needs nx >= 3 (a pixel would otherwise neighbour itself or one pixel twice).
+ *   direction codes  k = 0 .. 7: NW, N, NE, E, SE, S, SW, W with north at row r-1 -- the bit order of lc_morph_args; the opposite
+ *                of k is (k + 4) % 8.
+ *   links        a foreground pixel is linked to each foreground edge neighbour (N, E, S, W), and to a foreground corner neighbour
+ *                only if neither of the two pixels edge-adjacent to both is foreground: a staircase is a path, not a chain of
+ *                triangles.  links_out[p]: bit k set per link; the degree is its popcount (at most 4).
+ *   nodes        a pixel of degree 2 is INTERIOR; every other foreground pixel is a NODE: degree 0 isolated, 1 a free end, >= 3 a
+ *                junction.
+ *   darts        a link with a direction: id = p * 8 + k, p the linear index in the plane, k the code it leaves p by.
+ *   lines        two links belong to the same line when they meet in an interior pixel, so every link lies in exactly one line.
+ *                An open line is a path from node to node (both may be the same junction: its first and last point coincide and
+ *                it is still open); a ring consists of interior pixels only; a pixel of degree 0 is a line of one point.
+ *   key          the line's canonical first dart: of an open line the smaller id of the two darts that leave its end nodes along
+ *                it; of a ring the smallest id of all its darts (it leaves the ring's first pixel in raster order by its lower
+ *                code); of an isolated pixel p * 8.  The points of a line are the pixels met from that dart on, both end nodes
+ *                included; a ring does not repeat its first pixel.  Lines of a plane are numbered in the order of their keys.
+ *   measures     n_diag: corner links; position: links before a point; length of a link (with the tables): 2 radius
+ *                asin(min(1, sqrt(cost) / 2)) with lc_sphere_distance's node vectors and squared chord cost, from the same tables.
+ *
+ * The call ranks the STATES of the interior pixels: pixel q with links a < b has the states s = 2 q + 0, which leaves q through a,
+ * and 2 q + 1, which leaves through b; the HEAD of a state is the pixel its link leads to.  Per state, [n_members][2 * ny*nx]:
+ *   key_out      int32: the key of the line q lies on; -1 in the slots of pixels that are not interior, where flags_out is 0 and
+ *                nothing else is written
+ *   pos_out      int32: the position of q along its line (the same in both states)
+ *   ndiag_out    int32: corner links before q
+ *   dist_out     float64: sum of the link lengths before q (order of summation not fixed by this text; the call itself is
+ *                deterministic).  With the tables only.
+ *   head_out     int32: the head, as a linear index into the plane
+ *   link_length_out  float64: length of the link the state leaves by.  With the tables only.
+ *   flags_out    uint8: LC_LINE_STATE on every state; LC_LINE_CANONICAL: the state runs away from the line's first point;
+ *                LC_LINE_HEAD_IS_END: the head is an end node of the line or, on a ring, the ring's first pixel;
+ *                LC_LINE_RING; LC_LINE_CORNER_LINK: the link it leaves by is a corner link.
+ * So the points of a line that interior pixels do not give are the heads of the states flagged LC_LINE_HEAD_IS_END (position 0 from
+ * a state that is not canonical, position + 1 from a canonical one), and lines without an interior pixel -- node next to node,
+ * isolated pixels -- follow from links_out alone.
+ *   counts_out   int32 [n_members][4]: foreground pixels, interior pixels, nodes, links
+ *   rounds_out   HOST int, or NULL: the doubling rounds the call ran, at most 2 ceil(log2(I)) for I the largest interior count
+ *   tables       cos_lat, sin_lat [ny], cos_lon, sin_lon [nx]: float64 on the device, as for lc_sphere_distance; all four NULL:
+ *                no lengths, dist_out and link_length_out are not written
+ *   work_dev     int32 [lc_lines_work_elems(ny, nx, n_members)] scratch, 16-byte aligned: 96 bytes per pixel (two states, each
+ *                16 bytes and a float64, in two buffers) and 512 bytes (0 elements for bad sizes)
+ * Ranking is pointer doubling, one launch per round, double-buffered: a state carries its successor, the links covered, the corner
+ * links among them, their length and the smallest dart id seen, and ends at the first node.  What has not ended once 2^rounds is at
+ * least the largest interior count of a plane lies on a ring; the minimum it carries is then the ring's, the ring is broken at that
+ * dart and ranked again as an open chain.  Convergence is found as lc_mask_morphology finds it: one word read back per launch.
+ * A null context or argument structure, a wrong struct_size, a bad dtype, non-positive sizes, a plane of 2^28 pixels or more
+ * (dart ids are int32), cyclic_x with nx < 3, tables given in part and a radius that is not positive and finite beside them are
+ * refused with LC_EINVAL before any HIP call.
+ * No kernel of this call waits for another workgroup. */
+enum lc_line_flags {
+    LC_LINE_STATE = 1, LC_LINE_CANONICAL = 2, LC_LINE_HEAD_IS_END = 4, LC_LINE_RING = 8, LC_LINE_CORNER_LINK = 16
+};
+size_t lc_lines_work_elems(int ny, int nx, int n_members);
+typedef struct lc_lines_args {
+    size_t struct_size; /* sizeof(lc_lines_args): checked before any other field */
+    const void *mask;
+    int dtype, ny, nx, n_members;
+    int cyclic_x;
+    const double *cos_lat, *sin_lat; /* device, [ny]; or all four NULL */
+    const double *cos_lon, *sin_lon; /* device, [nx] */
+    double radius;                   /* > 0, finite (with the tables) */
+    void *links_out;                 /* uint8 [n_members][ny*nx] */
+    void *counts_out;                /* int32 [n_members][4] */
+    void *key_out, *pos_out, *ndiag_out, *head_out; /* int32 [n_members][2 * ny*nx] */
+    void *flags_out;                 /* uint8 [n_members][2 * ny*nx] */
+    void *dist_out, *link_length_out; /* float64 [n_members][2 * ny*nx]; with the tables */
+    int *rounds_out;                 /* host, or NULL */
+    void *work_dev;
+} lc_lines_args;
+int lc_trace_lines(lc_ctx *ctx, const lc_lines_args *args);
+
+/* The length of the links no state leaves by -- a node next to a node --, or of any list of pixel pairs of one grid:
+ * length_out[i] = 2 radius asin(min(1, sqrt(cost) / 2)) between pixels from[i] and to[i] (linear indices into a plane of ny x nx),
+ * the expression of lc_trace_lines' link_length_out; NaN for a pair that names no pixel of the plane.  n_pairs 0 is no work.  A
+ * null context, a wrong struct_size, bad sizes and a radius that is not positive and finite are refused with LC_EINVAL before any
+ * HIP call.  One kernel, which waits for no other workgroup. */
+typedef struct lc_link_lengths_args {
+    size_t struct_size;   /* sizeof(lc_link_lengths_args): checked before any other field */
+    const void *from, *to; /* int32 [n_pairs], device */
+    long long n_pairs;
+    int ny, nx;
+    const double *cos_lat, *sin_lat; /* device, [ny] */
+    const double *cos_lon, *sin_lon; /* device, [nx] */
+    double radius;
+    void *length_out;     /* float64 [n_pairs] */
+} lc_link_lengths_args;
+int lc_line_link_lengths(lc_ctx *ctx, const lc_link_lengths_args *args);
+
 /* ---- adaptive local threshold (threshold_local, above_local_threshold) ------------------
  * The other half of the driver's result, its "local strain" area (LCS/area_of_influence.py:194-199):
  *   local_thresh = threshold_local(ftle_local.values, block_size=301, offset=-.8);  binary_local = ftle_local > local_thresh

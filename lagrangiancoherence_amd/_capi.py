@@ -233,6 +233,42 @@ PROTOTYPES["lc_morph_work_elems"] = (_sz, [_i, _i, _i])
 PROTOTYPES["lc_mask_morphology"] = (_i, [_vp, C.POINTER(MorphArgs)])
 
 
+LC_LINE_STATE, LC_LINE_CANONICAL, LC_LINE_HEAD_IS_END, LC_LINE_RING, LC_LINE_CORNER_LINK = 1, 2, 4, 8, 16
+
+
+class LinesArgs(C.Structure):
+    """``lc_lines_args`` of include/lcs_hip.h, field for field."""
+    _fields_ = [("struct_size", _sz),
+                ("mask", _vp),
+                ("dtype", _i), ("ny", _i), ("nx", _i), ("n_members", _i),
+                ("cyclic_x", _i),
+                ("cos_lat", _vp), ("sin_lat", _vp), ("cos_lon", _vp), ("sin_lon", _vp),
+                ("radius", _d),
+                ("links_out", _vp), ("counts_out", _vp),
+                ("key_out", _vp), ("pos_out", _vp), ("ndiag_out", _vp), ("head_out", _vp),
+                ("flags_out", _vp),
+                ("dist_out", _vp), ("link_length_out", _vp),
+                ("rounds_out", C.POINTER(_i)), ("work_dev", _vp)]
+
+
+PROTOTYPES["lc_lines_work_elems"] = (_sz, [_i, _i, _i])
+PROTOTYPES["lc_trace_lines"] = (_i, [_vp, C.POINTER(LinesArgs)])
+
+
+class LinkLengthsArgs(C.Structure):
+    """``lc_link_lengths_args`` of include/lcs_hip.h, field for field."""
+    _fields_ = [("struct_size", _sz),
+                ("from_", _vp), ("to", _vp),
+                ("n_pairs", C.c_longlong),
+                ("ny", _i), ("nx", _i),
+                ("cos_lat", _vp), ("sin_lat", _vp), ("cos_lon", _vp), ("sin_lon", _vp),
+                ("radius", _d),
+                ("length_out", _vp)]
+
+
+PROTOTYPES["lc_line_link_lengths"] = (_i, [_vp, C.POINTER(LinkLengthsArgs)])
+
+
 class LocalThresholdArgs(C.Structure):
     """``lc_local_threshold_args`` of include/lcs_hip.h, field for field."""
     _fields_ = [("struct_size", _sz),

@@ -1692,6 +1692,203 @@ class Engine:
         return self._morphology(mask, _capi.LC_MORPH_DILATE, None, self.STRUCTURES[connectivity], cyclic, int(iterations),
                                 iterations_per_launch)
 
+    # ------------------------------------------------------------------ thinned ridges as ordered lines
+    LINE_STEPS = ((-1, -1), (-1, 0), (-1, 1), (0, 1), (1, 1), (1, 0), (1, -1), (0, -1))   # direction codes 0 .. 7: NW N NE E SE S SW W
+
+    @staticmethod
+    def checked_line_options(shape, cyclic, metric, lat, lon, radius, sampling):
+        """Every refusal of :meth:`trace_lines`' arguments (``ValueError``), on the host: no device is touched.  Returns
+        ``(tables or None, radius, sy, sx)``: the four tables of :meth:`sphere_tables` for ``metric='sphere'``."""
+        if metric not in Engine.METRICS:
+            raise ValueError(f"metric {metric!r}: 'index' or 'sphere'")
+        shape = tuple(int(s) for s in shape)
+        if len(shape) not in (2, 3) or min(shape) < 1:
+            raise ValueError("a plane (ny, nx) or a stack of planes (n_members, ny, nx), none of them empty")
+        ny, nx = shape[-2:]
+        if ny * nx >= 2 ** 28:
+            raise ValueError(f"plane too large: {ny} x {nx} pixels, dart ids 8 p + k are int32 (< 2^28 pixels)")
+        if cyclic and nx < 3:
+            raise ValueError(f"cyclic needs at least 3 columns, got {nx}: a pixel would neighbour itself or one pixel twice")
+        if metric == 'sphere':
+            if sampling is not None:
+                raise ValueError("sampling belongs to metric='index': on the sphere the coordinates are the metric")
+            if lat is None or lon is None:
+                raise ValueError("metric='sphere' needs lat and lon (degrees)")
+            cl, sl, cx, sx, radius, _, _ = Engine.sphere_tables(lat, lon, radius)
+            if (cl.size, cx.size) != (ny, nx):
+                raise ValueError(f"mask {shape}: ny = len(lat) = {cl.size} and nx = len(lon) = {cx.size}")
+            return (cl, sl, cx, sx), radius, 1.0, 1.0
+        s = np.asarray(1.0 if sampling is None else sampling, dtype=np.float64)
+        if s.shape not in ((), (2,)) or not (np.isfinite(s).all() and (s > 0).all()):
+            raise ValueError(f"sampling {sampling!r}: a positive finite scalar or (latitude step, longitude step)")
+        sy, sx = (float(v) for v in np.broadcast_to(s, (2,)))
+        return None, float(radius), sy, sx
+
+    def last_lines_rounds(self) -> int:
+        """Pointer-doubling rounds of the last :meth:`trace_lines` call (``lc_lines_args.rounds_out``)."""
+        return self._lines_rounds
+
+    _lines_rounds = 0
+
+    def trace_lines(self, mask, cyclic=False, metric='sphere', lat=None, lon=None, radius=6371000.0, sampling=None):
+        """The lines of a one-pixel-wide mask as ordered lists of pixels (``lc_trace_lines``; include/lcs_hip.h states the
+        definition, tests/lines.py restates it as a pixel walk).  ``mask``: ``(ny, nx)`` or ``(n_members, ny, nx)``, every plane
+        on its own in the same launches; a pixel is foreground when it is ``!= 0`` and not NaN; ``cyclic``: the last column is
+        the western neighbour of the first (at least 3 columns).
+
+        A foreground pixel is linked to its foreground edge neighbours, and to a foreground corner neighbour only if neither
+        of the two pixels edge-adjacent to both is foreground.  Pixels of degree 2 are interior, all others nodes; links that
+        meet in an interior pixel belong to one line.  A line starts with its canonical first dart (``pixel * 8 + direction
+        code``, codes NW N NE E SE S SW W): of an open line the smaller of the two darts that leave its end nodes along it, of
+        a ring the smallest of all its darts.  Lines are numbered by plane, then by that dart.
+
+        Returns a dict of device tensors.  Per line: ``plane``, ``offset``, ``count`` (its points are ``offset .. offset +
+        count``), ``closed`` (uint8: a ring, whose first pixel is not repeated), ``first``, ``last`` (int32 pixel indices into
+        the plane), ``first_degree``, ``last_degree`` (1 a free end, >= 3 a junction, 0 a lone pixel, 2 a ring), ``n_edge``,
+        ``n_diag`` (edge and corner links, a ring's closing link included), ``key`` (the canonical first dart) and ``length``
+        (float64).  Per point, ordered by line and position: ``line``, ``pixel`` (int32), ``distance`` (float64: along the line
+        from its first point) and ``step`` (the length of the link that leads to the point, 0 at a first point).  Per plane:
+        ``links`` (uint8 shaped like ``mask``: bit k set per link) and ``counts`` (int32 ``(n_members, 4)``: foreground,
+        interior pixels, nodes, links).
+
+        ``metric='sphere'``: a link is ``2 radius asin(min(1, sqrt(cost) / 2))`` long, with the node vectors and squared chord
+        of :meth:`sphere_distance` from ``lat`` / ``lon`` in degrees; ``length`` and ``distance`` are sums of those (float64,
+        in no stated order).  ``metric='index'``: ``length = n_edge * sy + n_diag * sqrt(sy * sy + sx * sx)``, every operation
+        rounded once, likewise ``distance`` from the counts before a point; ``sampling`` a scalar or ``(sy, sx)``, default 1
+        -- meant for uniform sampling, where an edge link is ``sy`` long whichever way it runs.
+
+        The ranking runs on the device (pointer doubling over the interior pixels, :meth:`last_lines_rounds` rounds, one word
+        read back per round); selection, one sort and the per-line gathers are torch on the device."""
+        torch = self.torch
+        shape = tuple(int(s) for s in mask.shape) if hasattr(mask, "shape") else np.shape(mask)
+        tables, radius, sy, sx = self.checked_line_options(shape, cyclic, metric, lat, lon, radius, sampling)
+        m = self._planes(mask)
+        n, ny, nx = (int(s) for s in m.shape)
+        npix, dev, i32, i64 = ny * nx, self.device, torch.int32, torch.int64
+        links = torch.empty((n, ny, nx), dtype=torch.uint8, device=dev)
+        counts = torch.empty((n, 4), dtype=i32, device=dev)
+        key, pos, ndiag, head = (torch.empty((n * 2 * npix,), dtype=i32, device=dev) for _ in range(4))
+        flags = torch.empty((n * 2 * npix,), dtype=torch.uint8, device=dev)
+        a = _capi.LinesArgs(struct_size=C.sizeof(_capi.LinesArgs))
+        a.mask, a.dtype = m.data_ptr(), _NP2LC[np.dtype(str(m.dtype).replace("torch.", ""))]
+        a.ny, a.nx, a.n_members, a.cyclic_x, a.radius = ny, nx, n, int(bool(cyclic)), radius
+        dist = link_len = dev_tables = None
+        if tables is not None:
+            dev_tables = [self.to_device(t, np.float64) for t in tables]
+            a.cos_lat, a.sin_lat, a.cos_lon, a.sin_lon = (t.data_ptr() for t in dev_tables)
+            dist, link_len = self._empty((n * 2 * npix,), np.float64), self._empty((n * 2 * npix,), np.float64)
+            a.dist_out, a.link_length_out = dist.data_ptr(), link_len.data_ptr()
+        work = torch.empty((max(1, (int(self.lib.lc_lines_work_elems(ny, nx, n)) + 1) // 2),), dtype=i64, device=dev)
+        rounds = C.c_int(0)
+        a.links_out, a.counts_out, a.flags_out = links.data_ptr(), counts.data_ptr(), flags.data_ptr()
+        a.key_out, a.pos_out, a.ndiag_out, a.head_out = key.data_ptr(), pos.data_ptr(), ndiag.data_ptr(), head.data_ptr()
+        a.rounds_out, a.work_dev = C.pointer(rounds), work.data_ptr()
+        self._use_current_stream()
+        _capi.check(self.lib.lc_trace_lines(self.ctx, C.byref(a)), self.lib)
+        self._lines_rounds = rounds.value
+        del work
+
+        F = _capi
+        S = 2 * npix
+        zero_f = torch.zeros((), dtype=torch.float64, device=dev)
+
+        def has(f, bit):
+            return (f & bit) != 0
+        # (a) every interior pixel, from its canonical state g; the link that leads to it is the one its other state leaves by
+        g = torch.nonzero(has(flags, F.LC_LINE_CANONICAL)).squeeze(1)
+        fg_, ring = flags[g], has(flags[g], F.LC_LINE_RING)
+        closing = ring & has(fg_, F.LC_LINE_HEAD_IS_END)          # the last point of a ring: its link closes it
+        corner = has(fg_, F.LC_LINE_CORNER_LINK).to(i64)
+        parts = [dict(plane=g // S, key=key[g].to(i64), pos=pos[g].to(i64), pixel=(g % S) // 2, nd=ndiag[g].to(i64), ring=ring,
+                      close_nd=torch.where(closing, corner, torch.zeros_like(corner)))]
+        if tables is not None:
+            parts[0].update(dist=dist[g], step=torch.where(pos[g] > 0, link_len[g ^ 1], zero_f),
+                            close_len=torch.where(closing, link_len[g], zero_f))
+        # (b) the end nodes of the open lines that have an interior pixel: the heads of the states that end at once
+        e = torch.nonzero(has(flags, F.LC_LINE_HEAD_IS_END) & ~has(flags, F.LC_LINE_RING)).squeeze(1)
+        fe = flags[e]
+        fwd = has(fe, F.LC_LINE_CANONICAL)
+        zero_i = torch.zeros_like(e)
+        parts.append(dict(plane=e // S, key=key[e].to(i64), pos=torch.where(fwd, pos[e].to(i64) + 1, zero_i), pixel=head[e].to(i64),
+                          nd=torch.where(fwd, ndiag[e].to(i64) + has(fe, F.LC_LINE_CORNER_LINK).to(i64), zero_i),
+                          ring=torch.zeros_like(fwd), close_nd=zero_i))
+        if tables is not None:
+            parts[1].update(dist=torch.where(fwd, dist[e] + link_len[e], zero_f), step=torch.where(fwd, link_len[e], zero_f),
+                            close_len=torch.zeros_like(dist[e]))
+        # (c) what has no interior pixel: isolated pixels, and nodes next to nodes (from the end with the smaller dart)
+        flat = links.reshape(-1)
+        popcount = torch.tensor([bin(i).count("1") for i in range(256)], dtype=i64, device=dev)
+        degree = popcount[flat.to(i64)]
+        lone = torch.nonzero(((m != 0) & ~torch.isnan(m)).reshape(-1) & (flat == 0)).squeeze(1)
+        zero_l = torch.zeros_like(lone)
+        parts.append(dict(plane=lone // npix, key=(lone % npix) * 8, pos=zero_l, pixel=lone % npix, nd=zero_l,
+                          ring=torch.zeros_like(lone, dtype=torch.bool), close_nd=zero_l))
+        if tables is not None:
+            z = torch.zeros(lone.shape, dtype=torch.float64, device=dev)
+            parts[2].update(dist=z, step=z, close_len=z)
+        nodes = torch.nonzero((flat != 0) & (degree != 2)).squeeze(1)
+        codes = torch.arange(8, device=dev, dtype=i64)
+        at, k = torch.nonzero(((flat[nodes].to(i64)[:, None] >> codes[None, :]) & 1) != 0, as_tuple=True)
+        p_all = nodes[at]
+        plane, p = p_all // npix, p_all % npix
+        steps = torch.tensor(self.LINE_STEPS, dtype=i64, device=dev)
+        h = (p // nx + steps[k, 0]) * nx + torch.remainder(p % nx + steps[k, 1], nx)       # a link: inside the plane, or across the seam
+        own = (degree[plane * npix + h] != 2) & (p * 8 + k < h * 8 + (k + 4) % 8)
+        plane, p, h, k = plane[own], p[own], h[own], k[own]
+        diag = 1 - k % 2
+        zero_n = torch.zeros_like(p)
+        parts.append(dict(plane=torch.cat([plane, plane]), key=torch.cat([p * 8 + k] * 2), pos=torch.cat([zero_n, zero_n + 1]),
+                          pixel=torch.cat([p, h]), nd=torch.cat([zero_n, diag]), ring=torch.zeros((2 * p.numel(),), dtype=torch.bool, device=dev),
+                          close_nd=torch.cat([zero_n, zero_n])))
+        if tables is not None:
+            length = self._empty((int(p.numel()),), np.float64)
+            if p.numel():
+                b = _capi.LinkLengthsArgs(struct_size=C.sizeof(_capi.LinkLengthsArgs))
+                p32, h32 = p.to(i32).contiguous(), h.to(i32).contiguous()
+                b.from_, b.to, b.n_pairs, b.ny, b.nx, b.radius = p32.data_ptr(), h32.data_ptr(), int(p.numel()), ny, nx, radius
+                b.cos_lat, b.sin_lat, b.cos_lon, b.sin_lon = (t.data_ptr() for t in dev_tables)
+                b.length_out = length.data_ptr()
+                _capi.check(self.lib.lc_line_link_lengths(self.ctx, C.byref(b)), self.lib)
+            z = torch.zeros_like(length)
+            parts[3].update(dist=torch.cat([z, length]), step=torch.cat([z, length]), close_len=torch.cat([z, z]))
+
+        pt = {name: torch.cat([part[name] for part in parts]) for name in parts[0]}
+        total = int(pt["pos"].numel())
+        span = int(pt["pos"].max().item()) + 1 if total else 1
+        if n * 8 * npix * span >= 2 ** 63:
+            raise ValueError(f"{n} planes of {ny} x {nx} with lines of up to {span} points: the sort key passes int64; trace fewer planes per call")
+        line_key = pt["plane"] * (8 * npix) + pt["key"]
+        order = torch.argsort(line_key * span + pt["pos"])
+        pt = {name: v[order] for name, v in pt.items()}
+        _, count = torch.unique_consecutive(line_key[order], return_counts=True)
+        offset = torch.cumsum(count, 0) - count
+        n_lines = int(count.numel())
+        line = torch.repeat_interleave(torch.arange(n_lines, device=dev, dtype=i64), count, output_size=total) if total else pt["pos"]
+        end = offset + count - 1
+        closed = pt["ring"][offset]
+        n_diag = pt["nd"][end] + pt["close_nd"][end]
+        n_edge = count - 1 + closed.to(i64) - n_diag
+        if tables is not None:
+            distance, step, length = pt["dist"], pt["step"], pt["dist"][end] + pt["close_len"][end]
+        else:
+            dg = float(np.sqrt(np.float64(sy) * np.float64(sy) + np.float64(sx) * np.float64(sx)))
+
+            def index_length(ne, nd):
+                return ne.to(torch.float64) * sy + nd.to(torch.float64) * dg      # three kernels: nothing is fused
+            distance, length = index_length(pt["pos"] - pt["nd"], pt["nd"]), index_length(n_edge, n_diag)
+            before = torch.cat([pt["nd"][:1] * 0, pt["nd"][:-1]]) if total else pt["nd"]
+            corner_step = pt["nd"] - before          # of the link that leads to the point (not read at a first point)
+            step = torch.where(pt["pos"] > 0, index_length(1 - corner_step, corner_step), zero_f)
+        first, last = pt["pixel"][offset], pt["pixel"][end]
+        planes_of = pt["plane"][offset]
+        out = {"plane": planes_of, "offset": offset, "count": count, "closed": closed.to(torch.uint8),
+               "first": first.to(i32), "last": last.to(i32),
+               "first_degree": degree[planes_of * npix + first].to(i32), "last_degree": degree[planes_of * npix + last].to(i32),
+               "n_edge": n_edge, "n_diag": n_diag, "key": pt["key"][offset], "length": length,
+               "line": line, "pixel": pt["pixel"].to(i32), "distance": distance, "step": step,
+               "links": links if len(shape) == 3 else links[0], "counts": counts}
+        return out
+
     # ------------------------------------------------------------------ multi-GPU (RCCL through the C ABI)
     COMM_ID_BYTES = 128
 

@@ -24,6 +24,10 @@
                                     whose per-zone totals are the driver's last step, LCS/area_of_influence.py's
                                     ``np.sum(ridges_ * pr_)`` -- or the ids of ``track_ridges``.  ``filter_ridges(metric='sphere')``
                                     decides on the same numbers (defined here)
+* ``ridge_lines``                   the ridges of a thinned mask as curves: the ordered latitude / longitude points of every line,
+                                    its great-circle length, its ends and branch points, the intensity along it -- the vector form
+                                    of what ``skeletonize_ridges`` returns, which the reference's chain of rasters never reaches
+                                    (defined here)
 
 The remaining functions of that module (IDW regridding, harvesine, latlonsel) have no caller on the
 path.
@@ -37,7 +41,7 @@ from .engine import Engine, common_dtype
 
 __all__ = ["xr_map_coordinates", "fourth_order_derivative", "derivative_spherical_coords",
            "find_ridges_spherical_hessian", "filter_ridges", "distance_to_ridges", "skeletonize_ridges", "dilate_ridges",
-           "threshold_local", "above_local_threshold", "track_ridges", "persistent_ridges", "ridge_properties"]
+           "threshold_local", "above_local_threshold", "track_ridges", "persistent_ridges", "ridge_properties", "ridge_lines"]
 
 
 def xr_map_coordinates(da, new_x, new_y, isglobal=True, order=1):
@@ -358,6 +362,113 @@ def ridge_properties(ridges, intensity=None, connectivity=2, cyclic=False, metri
     if lead:
         coords[lead[0]] = _coord(ridges, lead[0])
     return _make(ridges, _to_np(labels), order, coords, getattr(ridges, "name", None)).transpose(*dims), table
+
+
+LINE_COLUMNS = ("plane", "line", "offset", "count", "closed", "first_latitude", "first_longitude", "last_latitude", "last_longitude",
+                "first_degree", "last_degree", "length", "chord", "sinuosity", "component")
+POINT_COLUMNS = ("line", "latitude", "longitude", "row", "column", "distance")
+
+
+def ridge_lines(ridges, intensity=None, cyclic=False, metric='sphere', radius=6371000.0):
+    """The ridges of a thinned mask as curves: the ordered latitude / longitude points of every line, its arc length, where it
+    ends and where it branches, and the intensity along it -- the vector form of what ``skeletonize_ridges`` returns, for
+    plotting, export and measuring (``Engine.trace_lines``; include/lcs_hip.h states the definition).  Returns
+    ``(lines, points)``, two dicts of numpy arrays.
+
+    ``ridges`` is a labelled array over ``latitude`` and ``longitude`` (sorted ascending here, as ``filter_ridges`` sorts),
+    2-D, or 3-D with one more dimension (time, member): every plane is then traced on its own, all of them in the same
+    kernel launches.  A pixel is part of a ridge when it is ``!= 0`` and not NaN.  It is linked to its ridge neighbours N, E,
+    S, W, and to a diagonal one only where neither pixel beside both is ridge: a staircase is a path.  Pixels with two links
+    are interior; all others are nodes (no link: a lone pixel; one: a free end; three or more: a junction).  A line runs
+    from node to node through interior pixels, or is a ring of interior pixels.  ``cyclic``: the last longitude is the
+    western neighbour of the first (at least 3 longitudes).  The mask should be one pixel wide: on a thick one nearly every
+    pixel is a junction and every link a line of two points.
+
+    ``lines`` has one row per line, ordered by plane, then by the line's first link in raster order: ``plane`` (the index
+    along the extra dimension, 0 for 2-D input), ``line`` (its number within the plane), ``offset``, ``count`` (its points
+    are ``points[...][offset:offset + count]``), ``closed`` (1: a ring, whose first point is not repeated), ``first_latitude``,
+    ``first_longitude``, ``last_latitude``, ``last_longitude``, ``first_degree``, ``last_degree`` (links of the end pixels: 1 a
+    free end, >= 3 a junction, 0 a lone pixel, 2 a ring), ``length``, ``chord`` (first to last point; 0 for rings and for loops
+    through one junction), ``sinuosity`` (``length / chord``, NaN where the chord is 0) and ``component`` (the line's label
+    under ``Engine.label_components(connectivity=2, cyclic)``: the ``label`` of ``ridge_properties``).  With an
+    ``intensity`` -- a second field over the same dims and coordinates, the FTLE for instance --: ``mean_intensity``,
+    ``max_intensity``, ``min_intensity`` over the line's points.
+
+    ``points`` has one row per point, ordered by line and along it: ``line`` (a row of ``lines``), ``latitude``,
+    ``longitude``, ``row``, ``column`` (of the sorted array), ``distance`` (along the line from its first point) and, with
+    one, ``intensity``.
+
+    ``metric='sphere'`` (the default): lengths are great-circle arcs in the unit of ``radius`` (metres on the default Earth),
+    link by link, from the array's own coordinates in degrees (distinct, ``|latitude| <= 90``).  ``metric='index'``: a link
+    counts 1 along an edge and ``sqrt(2)`` across a corner."""
+    if metric not in Engine.METRICS:
+        raise ValueError(f"metric {metric!r}: 'index' or 'sphere'")
+    dims = tuple(ridges.dims)
+    lead = [d for d in dims if d not in ("latitude", "longitude")]
+    if len(lead) > 1 or len(dims) - len(lead) != 2:
+        raise ValueError("ridges: dims (latitude, longitude) and at most one more")
+    order = (*lead, "latitude", "longitude")
+    lat, lon = _coord(ridges, "latitude"), _coord(ridges, "longitude")
+    if intensity is not None:
+        if set(intensity.dims) != set(dims):
+            raise ValueError("ridges and intensity differ in their dims")
+        if not (np.array_equal(_coord(intensity, "latitude"), lat) and np.array_equal(_coord(intensity, "longitude"), lon)):
+            raise ValueError("ridges and intensity differ in their coordinates")
+    ilat, ilon = np.argsort(lat, kind="stable"), np.argsort(lon, kind="stable")
+    lat, lon = lat[ilat], lon[ilon]
+    if metric == 'sphere':
+        _check_sphere_grid(lat, lon, cyclic, radius)
+
+    def sorted_values(da):
+        v = np.asarray(da.transpose(*order).values)
+        v = v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)
+        return np.ascontiguousarray(v[..., ilat, :][..., ilon])
+    v = sorted_values(ridges)
+    Engine.checked_line_options(v.shape, cyclic, metric, lat, lon, radius, None)
+    w = None if intensity is None else sorted_values(intensity).astype(np.float64).reshape(-1, lat.size, lon.size)
+    eng = get_engine()
+    mask = eng.to_device(v, v.dtype)
+    t = eng.trace_lines(mask, cyclic, metric, lat if metric == 'sphere' else None, lon if metric == 'sphere' else None, radius)
+    labels, _ = eng.label_components(mask, 2, cyclic)
+    t = {k: _to_np(x) for k, x in t.items()}
+    labels = _to_np(labels).reshape(-1, lat.size * lon.size)
+    nx = lon.size
+    plane, first, last = t["plane"].astype(np.int64), t["first"].astype(np.int64), t["last"].astype(np.int64)
+    starts = np.flatnonzero(np.diff(plane, prepend=-1) != 0)             # the first line of every plane that has one
+    number = np.arange(plane.size) - np.repeat(starts, np.diff(np.append(starts, plane.size)))
+    if metric == 'sphere':
+        cl, sl, cx, sx = Engine.sphere_tables(lat, lon, radius)[:4]
+
+        def unit(p):
+            r, c = p // nx, p % nx
+            return cl[r] * cx[c], cl[r] * sx[c], sl[r]
+        (xa, ya, za), (xb, yb, zb) = unit(first), unit(last)
+        dx, dy, dz = xa - xb, ya - yb, za - zb
+        chord = 2.0 * float(radius) * np.arcsin(np.minimum(1.0, np.sqrt((dx * dx + dy * dy) + dz * dz) / 2.0))
+    else:
+        chord = np.hypot((first // nx - last // nx).astype(np.float64), (first % nx - last % nx).astype(np.float64))
+    chord = np.where(t["closed"] != 0, 0.0, chord)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sinuosity = np.where(chord > 0, t["length"] / chord, np.nan)
+    lines = {"plane": plane, "line": number.astype(np.int64), "offset": t["offset"].astype(np.int64), "count": t["count"].astype(np.int64),
+             "closed": t["closed"].astype(np.uint8),
+             "first_latitude": lat[first // nx], "first_longitude": lon[first % nx],
+             "last_latitude": lat[last // nx], "last_longitude": lon[last % nx],
+             "first_degree": t["first_degree"].astype(np.int32), "last_degree": t["last_degree"].astype(np.int32),
+             "length": t["length"], "chord": chord, "sinuosity": sinuosity,
+             "component": labels[plane, first].astype(np.int32)}
+    pixel = t["pixel"].astype(np.int64)
+    points = {"line": t["line"].astype(np.int64), "latitude": lat[pixel // nx], "longitude": lon[pixel % nx],
+              "row": (pixel // nx).astype(np.int32), "column": (pixel % nx).astype(np.int32), "distance": t["distance"]}
+    if w is not None:
+        value = w.reshape(w.shape[0], -1)[plane[points["line"]], pixel]
+        points["intensity"] = value
+        # per line: its points are one contiguous run
+        at = lines["offset"][lines["count"] > 0]
+        for name, op in (("max_intensity", np.maximum), ("min_intensity", np.minimum)):
+            lines[name] = op.reduceat(value, at) if at.size else np.zeros(0)
+        lines["mean_intensity"] = (np.add.reduceat(value, at) / lines["count"]) if at.size else np.zeros(0)
+    return lines, points
 
 
 def distance_to_ridges(ridges, cyclic=False, sampling=None, max_distance=None, return_labels=False, connectivity=2,
