@@ -1082,6 +1082,61 @@ typedef struct lc_local_threshold_args {
 int lc_local_threshold(lc_ctx *ctx, const lc_local_threshold_args *args);
 const char *lc_ctx_last_threshold_kernel(const lc_ctx *ctx);
 
+/* ---- inverse-distance weighting of scattered values on the sphere (Inverse_weighted_interpolation, xr_idx_interp) ----
+ * LCS/tools.py:285-333: values known at scattered longitude / latitude points, gridded with weights 1 / d^power of the
+ * great-circle distance d.  Two departures from the reference: its distance calls arctan(sqrt(a), sqrt(1 - a)) where it means
+ * arctan2 (the second argument is numpy's out=), and a source that coincides with a target gives inf / inf = NaN there.  Here
+ * the distance is the project's own (lc_sphere_distance's chord form) and a coincident source is the limit of the weighting.
+ * All three entry points were added at LC_VERSION 104 without a bump: nothing that existed changed.
+ *
+ * Points: the caller hands over, float64 on the device, the unit vectors of its sources and targets,
+ *   X = fl(cos lat cos lon), Y = fl(cos lat sin lon), Z = sin lat   (for a grid: from the row / column tables, one rounded
+ * product, as lc_sphere_distance's nodes); no kernel evaluates a trigonometric function of a coordinate.  A source or a target
+ * that is to be left out (a coordinate that is not finite, |lat| > 90) is given NaN components.
+ *   cost   = fl(fl(fl(dX dX) + fl(dY dY)) + fl(dZ dZ)), dX = fl(Xt - Xs), ...: float64, every operation rounded once, nothing
+ *            fused.  A source is within reach of a target where cost <= max_chord2 (unbounded: where cost is not NaN).
+ *   d      = 2 radius asin(min(1, sqrt(cost) / 2));  w = 1 / d^power, as 1 / (d d) for power 2, 1 / d for power 1, 1 / pow(d,
+ *            power) otherwise.
+ *   values `dtype` elements (LC_F32 or LC_F64) [n_planes][n_src] on shared positions; the geometry of a pair is evaluated once
+ *            for up to 4 planes.  A NaN value leaves its source out of that plane, in every sum below.
+ *   out    `dtype` [n_planes][n_tgt]: sum(w z) / sum(w) over the contributing sources, accumulated in float64 (w z + sum is
+ *            one fused operation) and rounded to `dtype` once.  Where one or more contributing sources have cost == 0: the mean
+ *            of their values.  Without a contributing source: NaN.
+ *   weight_out  float64 [n_planes][n_tgt], or NULL: sum(w); +inf on an exact hit, 0 without a contributing source.
+ *   count_out   int32 [n_tgt], or NULL: the sources within reach, whatever their values are.
+ *   max_chord2 > 0: (2 sin(max_distance / (2 radius)))^2, squared by the caller in float64.  Each workgroup of 256 targets then
+ *            walks only the smallest contiguous range of sources that holds every source whose same-meridian chord to the
+ *            latitudes of its targets is within the bound plus a margin far above every rounding: no culling changes a result.
+ *            The range is short where the sources are sorted by Z; they need not be.  <= 0: unbounded.
+ *   max_distance  the same bound in the unit of radius: > 0 beside a max_chord2 > 0, not read otherwise.
+ *   work_dev  float64 [lc_idw_work_elems(n_src, n_tgt, n_planes)] scratch (0 elements for bad sizes).
+ * The order of summation is not part of the contract; it is a function of the sizes alone -- with fewer than 256 workgroups of
+ * targets the sources of each are split over several workgroups, whose partial sums a second kernel adds in ascending order --
+ * so two calls on the same arguments give the same bits.  There is no atomic operation.
+ * Refused with LC_EINVAL before any HIP call: a null context, argument structure or pointer (weight_out and count_out may be
+ * NULL), a wrong struct_size, a dtype other than LC_F32 / LC_F64, a size <= 0 or one that cannot be sized, a power outside
+ * (0, 16], a radius that is not positive and finite, a NaN max_chord2, a max_chord2 > 0 without a max_distance > 0.
+ * lc_ctx_last_idw_kernel: the kernels of the last call joined by '+' ("" before the first call or for a null context).
+ * No kernel of this call waits for another workgroup. */
+size_t lc_idw_work_elems(int n_src, int n_tgt, int n_planes);
+typedef struct lc_idw_args {
+    size_t struct_size; /* sizeof(lc_idw_args): checked before any other field */
+    const double *src_x, *src_y, *src_z; /* device, [n_src] */
+    const void *values;                  /* dtype [n_planes][n_src] */
+    const double *tgt_x, *tgt_y, *tgt_z; /* device, [n_tgt] */
+    int dtype, n_src, n_tgt, n_planes;
+    double power;        /* in (0, 16] */
+    double radius;       /* > 0, finite */
+    double max_chord2;   /* <= 0: unbounded */
+    double max_distance; /* > 0 where max_chord2 > 0 */
+    void *out;           /* dtype [n_planes][n_tgt] */
+    void *weight_out;    /* float64 [n_planes][n_tgt], or NULL */
+    void *count_out;     /* int32 [n_tgt], or NULL */
+    void *work_dev;
+} lc_idw_args;
+int lc_idw_interp(lc_ctx *ctx, const lc_idw_args *args);
+const char *lc_ctx_last_idw_kernel(const lc_ctx *ctx);
+
 /* ---- multi-GPU: halo exchange on RCCL ----------------------------------------
  * New (the reference is single-process).  One process per GPU,
  * seed rows block-partitioned, wind replicated; lc_advect needs no communication

@@ -285,6 +285,22 @@ PROTOTYPES["lc_local_threshold"] = (_i, [_vp, C.POINTER(LocalThresholdArgs)])
 PROTOTYPES["lc_ctx_last_threshold_kernel"] = (C.c_char_p, [_vp])
 
 
+class IdwArgs(C.Structure):
+    """``lc_idw_args`` of include/lcs_hip.h, field for field."""
+    _fields_ = [("struct_size", _sz),
+                ("src_x", _vp), ("src_y", _vp), ("src_z", _vp),
+                ("values", _vp),
+                ("tgt_x", _vp), ("tgt_y", _vp), ("tgt_z", _vp),
+                ("dtype", _i), ("n_src", _i), ("n_tgt", _i), ("n_planes", _i),
+                ("power", _d), ("radius", _d), ("max_chord2", _d), ("max_distance", _d),
+                ("out", _vp), ("weight_out", _vp), ("count_out", _vp), ("work_dev", _vp)]
+
+
+PROTOTYPES["lc_idw_work_elems"] = (_sz, [_i, _i, _i])
+PROTOTYPES["lc_idw_interp"] = (_i, [_vp, C.POINTER(IdwArgs)])
+PROTOTYPES["lc_ctx_last_idw_kernel"] = (C.c_char_p, [_vp])
+
+
 
 class RidgesArgs(C.Structure):
     """``lc_ridges_args`` of include/lcs_hip.h, field for field."""

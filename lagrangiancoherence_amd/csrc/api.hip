@@ -101,6 +101,7 @@ extern "C" int lc_ctx_create(int device, lc_ctx **out) {
     c->last_strain_kernel = "";
     c->last_ridges_kernel = "";
     c->last_threshold_kernel = "";
+    c->last_idw_kernel = "";
     c->verify_dev = nullptr;
     c->trunc = nullptr;
     c->xfer = nullptr;

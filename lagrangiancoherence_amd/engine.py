@@ -1540,6 +1540,151 @@ class Engine:
         out = [t if len(shape) == 3 else t[0] for t in (dist, nearest, cost) if t is not None]
         return out[0] if len(out) == 1 else tuple(out)
 
+    # ------------------------------------------------------------------ inverse-distance weighting of scattered values
+    IDW_MAX_POWER = 16.0
+
+    @property
+    def last_idw_kernel(self) -> str:
+        """Names of the kernels the last :meth:`idw_interp` call launched (``lc_ctx_last_idw_kernel``), joined by ``+``."""
+        return self.lib.lc_ctx_last_idw_kernel(self.ctx).decode()
+
+    @staticmethod
+    def _host_degrees(a):
+        """Coordinates in degrees as a float64 numpy array, from a numpy array or a tensor (positions are small beside the
+        all-pairs work, and their cosines and sines are numpy's by definition)."""
+        if hasattr(a, "detach"):
+            a = a.detach().cpu().numpy()
+        return np.asarray(a, dtype=np.float64)
+
+    @staticmethod
+    def sphere_points(lon, lat, grid=False):
+        """Unit vectors ``(X, Y, Z)`` of points given in degrees: ``X = fl(cos lat cos lon)``, ``Y = fl(cos lat sin lon)``, ``Z =
+        sin lat`` with numpy's cos / sin of ``degrees * pi / 180``, as :meth:`sphere_tables` forms its tables.  ``lon`` and
+        ``lat`` have one shape, which the vectors take; ``grid=True``: ``lat`` is ``(ny,)``, ``lon`` is ``(nx,)`` and the
+        vectors are ``(ny, nx)``, one rounded product of the row and column tables each, as ``lc_sphere_distance`` defines its
+        nodes.  A point with a coordinate that is not finite or with ``|lat| > 90`` has NaN components: it is left out."""
+        lon, lat = np.asarray(lon, dtype=np.float64), np.asarray(lat, dtype=np.float64)
+        with np.errstate(invalid="ignore"):
+            y, x = lat * np.pi / 180, lon * np.pi / 180
+            cl, sl, cx, sx = np.cos(y), np.sin(y), np.cos(x), np.sin(x)
+            bad_lat, bad_lon = ~(np.isfinite(lat) & (np.abs(lat) <= 90.0)), ~np.isfinite(lon)
+            if grid:
+                cl, sl, bad_lat, cx, sx, bad_lon = cl[:, None], sl[:, None], bad_lat[:, None], cx[None, :], sx[None, :], bad_lon[None, :]
+            X, Y, bad = cl * cx, cl * sx, bad_lat | bad_lon
+        return tuple(np.where(bad, np.nan, v) for v in (X, Y, np.broadcast_to(sl, X.shape)))
+
+    @staticmethod
+    def idw_plan(src_lon, src_lat, values_shape, tgt_lon, tgt_lat, grid=False, power=2, radius=6371000.0, max_distance=None):
+        """Every check of :meth:`idw_interp` and what it hands to the device, computed with numpy on the host (no device is
+        touched): a dict of the source vectors ``src`` and target vectors ``tgt`` (tuples of flat float64 arrays), the targets'
+        ``shape``, ``n_planes`` (None for one-dimensional values), ``power``, ``radius``, ``max_chord2`` and ``max_distance``
+        (both 0 without a bound) and ``order`` -- with a bound, the permutation that sorts the sources by latitude (``src`` is
+        in that order), else None."""
+        power, radius = float(power), float(radius)
+        if not (0.0 < power <= Engine.IDW_MAX_POWER):
+            raise ValueError(f"power {power!r}: in (0, {Engine.IDW_MAX_POWER:g}]")
+        if not (radius > 0 and np.isfinite(radius)):
+            raise ValueError(f"radius {radius!r}: a positive, finite number")
+        chord2, bound = 0.0, 0.0
+        if max_distance is not None:
+            if not float(max_distance) > 0:
+                raise ValueError(f"max_distance {max_distance!r}: a positive number, or None for no bound")
+            if float(max_distance) < np.pi * radius:
+                bound = float(max_distance)
+                c = np.float64(2.0) * np.sin(np.float64(bound) / (np.float64(2.0) * np.float64(radius)))
+                chord2 = float(c * c)
+                if not chord2 > 0.0:
+                    raise ValueError(f"max_distance {max_distance!r}: its squared chord on a sphere of radius {radius!r} underflows")
+        shapes = [tuple(int(s) for s in (a.shape if hasattr(a, "shape") else np.shape(a))) for a in (src_lon, src_lat, tgt_lon, tgt_lat)]
+        values_shape = tuple(int(s) for s in values_shape)
+        if len(shapes[0]) != 1 or shapes[0] != shapes[1] or shapes[0][0] == 0:
+            raise ValueError(f"src_lon {shapes[0]} and src_lat {shapes[1]}: one-dimensional, equal and not empty")
+        if len(values_shape) not in (1, 2) or values_shape[-1] != shapes[0][0] or 0 in values_shape:
+            raise ValueError(f"values {values_shape}: (n_src,) or (n_planes, n_src) with n_src = {shapes[0][0]}")
+        if grid:
+            if len(shapes[2]) != 1 or len(shapes[3]) != 1 or shapes[2][0] == 0 or shapes[3][0] == 0:
+                raise ValueError(f"grid=True: tgt_lon {shapes[2]} is (nx,) and tgt_lat {shapes[3]} is (ny,), neither empty")
+            shape = (shapes[3][0], shapes[2][0])
+        else:
+            if shapes[2] != shapes[3] or 0 in shapes[2]:
+                raise ValueError(f"grid=False: tgt_lon {shapes[2]} and tgt_lat {shapes[3]} have equal shapes and are not empty")
+            shape = shapes[2]
+        n_tgt = int(np.prod(shape, dtype=np.int64))
+        if max(shapes[0][0], n_tgt) >= 1 << 31 or (len(values_shape) == 2 and values_shape[0] >= 1 << 31):
+            raise ValueError("sources, targets and planes: fewer than 2^31 each")
+        slon, slat, tlon, tlat = (Engine._host_degrees(a) for a in (src_lon, src_lat, tgt_lon, tgt_lat))
+        src = Engine.sphere_points(slon, slat)
+        tgt = tuple(np.ascontiguousarray(v).reshape(-1) for v in Engine.sphere_points(tlon, tlat, grid))
+        order = None
+        if chord2 > 0.0:
+            order = np.argsort(src[2], kind="stable")     # ascending latitude; the points left out (NaN) last
+            src = tuple(v[order] for v in src)
+        return {"src": tuple(np.ascontiguousarray(v) for v in src), "tgt": tgt, "shape": shape,
+                "n_planes": values_shape[0] if len(values_shape) == 2 else None,
+                "power": power, "radius": radius, "max_chord2": chord2, "max_distance": bound, "order": order}
+
+    def idw_interp(self, src_lon, src_lat, values, tgt_lon, tgt_lat, grid=False, power=2, radius=6371000.0, max_distance=None,
+                   return_weight=False, return_count=False):
+        """Values known at scattered points of the sphere, gridded by inverse-distance weighting with great-circle distances
+        (``lc_idw_interp``; LCS/tools.py:285-299): ``u = sum(w z) / sum(w)`` with ``w = 1 / d**power`` over the sources.
+
+        ``src_lon``, ``src_lat`` ``(n_src,)`` in degrees; ``values`` ``(n_src,)``, or ``(n_planes, n_src)`` -- several fields
+        on the same positions, for which the geometry of a pair is evaluated once -- float32 or float64 (anything else is
+        converted to float64), and the result has their dtype.  ``grid=False``: ``tgt_lon`` and ``tgt_lat`` have equal shapes,
+        which the result takes; ``grid=True``: ``tgt_lat`` is ``(ny,)``, ``tgt_lon`` is ``(nx,)`` and the result is ``(ny,
+        nx)``, in the order given (sorted or not).  With planes the result is ``(n_planes, ...)``.  Numpy arrays or device
+        tensors; the result is a device tensor.
+
+        A point is the unit vector ``(cos lat cos lon, cos lat sin lon, sin lat)``, formed here with numpy (:meth:`sphere_points`);
+        the cost of a pair is the squared chord ``((dX dX + dY dY) + dZ dZ)``, ``d = 2 radius asin(min(1, sqrt(cost) / 2))`` as
+        in :meth:`sphere_distance`, all arithmetic and every sum in float64.  ``0 < power <= 16``; powers 2 and 1 take forms
+        without ``pow``.  Where sources coincide with a target (cost 0) the result is the mean of their values, the limit of
+        the weighting (the reference divides ``inf`` by ``inf`` there).  A source whose value is NaN is left out of that
+        plane; a source with a coordinate that is not finite or ``|lat| > 90`` out of every plane.  Without a bound the result
+        does not depend on ``radius``.
+
+        ``max_distance`` (> 0, in the unit of ``radius``; None or ``>= pi radius``: no bound): a source contributes where ``cost
+        <= (2 sin(max_distance / (2 radius)))^2``; a target without a contributing source is NaN.  The sources are then sorted
+        by latitude and every 256 targets walk only the sources within the bound of their latitudes.
+
+        ``return_weight``: also ``sum(w)`` (float64, shaped like the result; ``+inf`` on an exact hit, 0 where nothing
+        contributes).  ``return_count``: also the int32 number of sources within reach of each target (shaped like the
+        targets), whatever their values are.  Returns ``u``, then the weight, then the count, as asked for.  The order of
+        summation depends on the sizes only: two calls on the same inputs agree bit for bit."""
+        vshape = tuple(int(s) for s in values.shape) if hasattr(values, "shape") else np.shape(values)
+        plan = self.idw_plan(src_lon, src_lat, vshape, tgt_lon, tgt_lat, grid, power, radius, max_distance)
+        torch = self.torch
+        dtype = np.dtype(str(values.dtype).replace("torch.", "")) if hasattr(values, "dtype") else np.asarray(values).dtype
+        dtype = dtype if dtype in _NP2LC else np.dtype(np.float64)
+        v = self.to_device(values, dtype).reshape(-1, vshape[-1])
+        if plan["order"] is not None:
+            v = v.index_select(1, torch.as_tensor(plan["order"], device=self.device)).contiguous()
+        n, n_src = (int(s) for s in v.shape)
+        n_tgt = plan["tgt"][0].size
+        elems = int(self.lib.lc_idw_work_elems(n_src, n_tgt, n))
+        work = torch.empty((max(1, elems),), dtype=torch.float64, device=self.device)
+        out = self._empty((n, n_tgt), dtype)
+        weight = self._empty((n, n_tgt), np.float64) if return_weight else None
+        count = torch.empty((n_tgt,), dtype=torch.int32, device=self.device) if return_count else None
+        vectors = [self.to_device(t, np.float64) for t in (*plan["src"], *plan["tgt"])]
+        a = _capi.IdwArgs(struct_size=C.sizeof(_capi.IdwArgs))
+        a.src_x, a.src_y, a.src_z, a.tgt_x, a.tgt_y, a.tgt_z = (t.data_ptr() for t in vectors)
+        a.values, a.dtype = v.data_ptr(), _NP2LC[dtype]
+        a.n_src, a.n_tgt, a.n_planes = n_src, n_tgt, n
+        a.power, a.radius, a.max_chord2, a.max_distance = plan["power"], plan["radius"], plan["max_chord2"], plan["max_distance"]
+        a.out, a.work_dev = out.data_ptr(), work.data_ptr()
+        a.weight_out = weight.data_ptr() if return_weight else None
+        a.count_out = count.data_ptr() if return_count else None
+        self._use_current_stream()
+        _capi.check(self.lib.lc_idw_interp(self.ctx, C.byref(a)), self.lib)
+        shape = plan["shape"] if plan["n_planes"] is None else (n, *plan["shape"])
+        res = [out.reshape(shape)]
+        if return_weight:
+            res.append(weight.reshape(shape))
+        if return_count:
+            res.append(count.reshape(plan["shape"]))
+        return res[0] if len(res) == 1 else tuple(res)
+
     # ------------------------------------------------------------------ adaptive local threshold
     _THRESHOLD_PLANES = ("threshold", "mask")
 

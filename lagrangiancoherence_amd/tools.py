@@ -28,9 +28,14 @@
                                     its great-circle length, its ends and branch points, the intensity along it -- the vector form
                                     of what ``skeletonize_ridges`` returns, which the reference's chain of rasters never reaches
                                     (defined here)
+* ``Inverse_weighted_interpolation`` LCS/tools.py:285-299 and its labelled wrapper ``xr_idx_interp`` (LCS/tools.py:302-333): values
+                                    known at scattered longitude / latitude points -- what ``parcel_propagation(..., C=)`` samples
+                                    along trajectories, at the positions ``return_traj`` hands out -- gridded by inverse-distance
+                                    weighting with great-circle distances, the way back to the rasters the rest of the chain takes.
+                                    The reference's function is broken as written (``arctan`` for ``arctan2``, NaN where a source
+                                    lies on a node): the definition is restated here, see their docstrings
 
-The remaining functions of that module (IDW regridding, harvesine, latlonsel) have no caller on the
-path.
+The remaining functions of that module (harvesine, latlonsel) have no caller on the path.
 """
 from __future__ import annotations
 
@@ -41,7 +46,8 @@ from .engine import Engine, common_dtype
 
 __all__ = ["xr_map_coordinates", "fourth_order_derivative", "derivative_spherical_coords",
            "find_ridges_spherical_hessian", "filter_ridges", "distance_to_ridges", "skeletonize_ridges", "dilate_ridges",
-           "threshold_local", "above_local_threshold", "track_ridges", "persistent_ridges", "ridge_properties", "ridge_lines"]
+           "threshold_local", "above_local_threshold", "track_ridges", "persistent_ridges", "ridge_properties", "ridge_lines",
+           "Inverse_weighted_interpolation", "xr_idx_interp"]
 
 
 def xr_map_coordinates(da, new_x, new_y, isglobal=True, order=1):
@@ -759,3 +765,69 @@ def above_local_threshold(da, block_size, offset=0, param=None, cyclic=False):
 
     Returns the boolean mask in the caller's class and dimension order."""
     return _local_threshold(da, block_size, 'gaussian', offset, 'reflect', param, cyclic, "mask")
+
+
+def Inverse_weighted_interpolation(x, y, z, xi, yi, power=2):
+    """Values ``z`` known at longitudes ``x`` and latitudes ``y`` (degrees), interpolated to the points ``(xi, yi)`` by
+    inverse-distance weighting with great-circle distances: ``u = sum(z / d**power) / sum(1 / d**power)``.  Signature of
+    LCS/tools.py:285 (an all-pairs numba loop there); returns an array of ``len(xi)`` in ``z``'s dtype (float32 / float64 kept,
+    anything else float64), where the reference returns a list.
+
+    Two departures from the reference, whose function is broken as written: its haversine distance calls ``np.arctan(sqrt(a),
+    sqrt(1 - a))`` where it means ``arctan2`` (the second argument is numpy's ``out=``) -- the distance here is the true
+    great-circle distance, ``2 R asin(chord / 2)`` as everywhere in this package (``Engine.idw_interp`` states every rounding)
+    --, and a point ``(xi, yi)`` that coincides with a source gives ``inf / inf = NaN`` there and that source's value here (the
+    mean of several), the limit of the weighting.  The result does not depend on the radius: the reference's 6378.1 km and this
+    package's 6371 km give one field.  A NaN in ``z`` leaves its source out."""
+    x, y, xi, yi = (np.asarray(getattr(a, "values", a)) for a in (x, y, xi, yi))
+    z = np.asarray(getattr(z, "values", z))
+    plan = Engine.idw_plan(x, y, z.shape, xi, yi, False, power)               # every refusal, before a device
+    if z.ndim != 1 or len(plan["shape"]) != 1:
+        raise ValueError("x, y, z and xi, yi: one-dimensional")
+    return _to_np(get_engine().idw_interp(x, y, z, xi, yi, power=power))
+
+
+def xr_idx_interp(ds_y_for_spline, lon, lat, p=2, max_distance=None, radius=6371000.0, return_weight=False, return_count=False):
+    """Grid the values of a labelled array of scattered points -- one ``points``-like dimension along which it carries
+    ``longitude`` and ``latitude`` coordinates in degrees -- onto ``lat`` x ``lon`` by inverse-distance weighting on the
+    sphere.  Signature of LCS/tools.py:302 with four keywords more; the result has dims ``(latitude, longitude)`` on the
+    coordinates given (in the order given, sorted or not), in the class and the dtype of the input.  A leading dimension in
+    front of the points (time, tracer) is a stack of fields on the same positions: every plane is gridded on its own, the
+    geometry of a pair evaluated once for all of them, and the result is ``(that dimension, latitude, longitude)``.
+
+    ``p``: the power of the distance, ``0 < p <= 16``.  ``max_distance`` (in the unit of ``radius``, metres on the default
+    Earth): only sources within that great-circle distance contribute, a node without one is NaN, and the search is cut to
+    the sources within the bound's band of latitudes; None: every source contributes to every node, as in the reference.
+    ``return_weight``: also ``sum(1 / d**p)``, float64 (``+inf`` where a source lies on the node).  ``return_count``: also the
+    int32 number of sources within reach of each node, dims ``(latitude, longitude)``.  Returns the field, then the weight,
+    then the count, as asked for.
+
+    The departures from the reference are those of ``Inverse_weighted_interpolation``: the true great-circle distance where
+    the reference's haversine misuses ``arctan``, and the source's own value, not NaN, where a source lies on a node.  NaN
+    values are left out, plane by plane; sources whose coordinates are not finite, or beyond the poles, altogether."""
+    da = ds_y_for_spline
+    dims = tuple(da.dims)
+    if len(dims) not in (1, 2):
+        raise ValueError(f"dims {dims}: one dimension of points, and at most one in front of it")
+    x, y = _coord(da, "longitude"), _coord(da, "latitude")
+    # the dimension the coordinates run along: xarray names it; a class that does not is asked for the (last) dimension of
+    # their length
+    along = tuple(getattr(da["longitude"], "dims", ()))
+    fits = [d for d, n in zip(dims, np.shape(da.values)) if n == x.size]
+    points = along[0] if len(along) == 1 and along[0] in dims else fits[-1] if fits else dims[-1]
+    lead = [d for d in dims if d != points]
+    v = np.asarray(da.transpose(*lead, points).values)
+    v = v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)
+    lon, lat = np.asarray(getattr(lon, "values", lon)), np.asarray(getattr(lat, "values", lat))
+    Engine.idw_plan(x, y, v.shape, lon, lat, True, p, radius, max_distance)    # every refusal, before a device
+    got = get_engine().idw_interp(x, y, v, lon, lat, grid=True, power=p, radius=radius, max_distance=max_distance,
+                                  return_weight=return_weight, return_count=return_count)
+    got = got if isinstance(got, tuple) else (got,)
+    order, coords = (*lead, "latitude", "longitude"), {"latitude": lat, "longitude": lon}
+    if lead and lead[0] in da.coords:
+        coords[lead[0]] = _coord(da, lead[0])
+    name = getattr(da, "name", None)
+    out = [_make(da, _to_np(t), order, coords, name) for t in got[:1 + bool(return_weight)]]
+    if return_count:
+        out.append(_make(da, _to_np(got[-1]), ("latitude", "longitude"), {"latitude": lat, "longitude": lon}, name))
+    return out[0] if len(out) == 1 else tuple(out)
