@@ -1137,6 +1137,78 @@ typedef struct lc_idw_args {
 int lc_idw_interp(lc_ctx *ctx, const lc_idw_args *args);
 const char *lc_ctx_last_idw_kernel(const lc_ctx *ctx);
 
+/* ---- great-circle transects across ridge lines and their composites (tools.ridge_transects) ----
+ * Replaces LCS/area_of_influence.py:17-87 (find_area), as far as that function is well defined: it paints pixels along the
+ * Hessian eigenvector of every ridge pixel in a Python loop, steps in degrees with argmin lookups (wrong away from the equator)
+ * and gives the sign of the normal no meaning; its painted mask is not reproduced.  Here a second field is sampled along the
+ * great circle through every point of a traced line (lc_trace_lines; Engine.trace_lines orders the points), at right angles to
+ * the line, at signed distances s_k = k spacing, k = -K .. K, and the samples of a line are averaged offset by offset.
+ * tests/transects.py restates what follows point by point in numpy.  Both entry points were added at LC_VERSION 104 without a
+ * bump: nothing that existed changed.
+ *
+ * Lines: pixel int32 [n_points] (the linear index of a point in its plane), point_line int32 [n_points], and per line
+ *   line_offset, line_count, line_plane int32 [n_lines], line_closed uint8 [n_lines]: the points of line l are offset ..
+ *   offset + count, ordered along it; a ring's first point is not repeated.
+ * Grid: cos_lat, sin_lat [ny], cos_lon, sin_lon [nx] float64 as for lc_sphere_distance (the caller's cos / sin of the
+ *   coordinates), and the coordinates themselves in degrees, lat_deg [ny], lon_deg [nx], strictly ascending, |lat| <= 90; with
+ *   cyclic_x lon_deg[nx - 1] - lon_deg[0] < 360.  The latitudes need not be uniform.
+ * Offsets: cos_off[k] = cos(s_k / radius), sin_off[k] = sin(s_k / radius), float64 [n_offsets], n_offsets = 2 K + 1, formed by
+ *   the caller with |s_k| / radius < pi / 2.  No kernel evaluates a trigonometric function of a coordinate or of a distance.
+ * Every operation below is float64, rounded once, nothing fused, in the order written:
+ *   point    p_i = (cl cx, cl sx, sl) of the point's row and column.
+ *   tangent  with m = smooth: a = max(i - m, 0), b = min(i + m, count - 1) within an open line; on a ring m is capped at
+ *            (count - 1) / 2 and a = (i - m) mod count, b = (i + m) mod count.  d = p_b - p_a, dot = (d_x p_x + d_y p_y) + d_z p_z,
+ *            u = d - dot p, len = sqrt((u_x u_x + u_y u_y) + u_z u_z), t = u / len.  Where a == b or len is not > 0 the point has
+ *            no tangent: its normal, its components and all its samples are NaN (lone pixels, lines of one point).
+ *   normal   the left normal n = p x t = (p_y t_z - p_z t_y, p_z t_x - p_x t_z, p_x t_y - p_y t_x).  Components against the point's
+ *            own column (so they are defined at a pole): east (-sx, cx, 0), north (-(sl cx), -(sl sx), cl);
+ *            n_east = cx n_y - sx n_x, n_north = (north_x n_x + north_y n_y) + cl n_z, likewise t_east, t_north.
+ *            LC_ORIENT_LEFT keeps n; LC_ORIENT_NORTH negates it where n_north < 0, or n_north == 0 and n_east < 0;
+ *            LC_ORIENT_EAST the same with the roles exchanged.
+ *   sample   q = cos_off[k] p + sin_off[k] n; latitude = atan2(q_z, sqrt(q_x q_x + q_y q_y)) (180 / pi), longitude = atan2(q_y,
+ *            q_x) (180 / pi) -- the hypotenuse as a rounded square root of the rounded sum: |q| is about 1, nothing overflows --;
+ *            with cyclic_x the longitude x becomes x - floor((x - lon[0]) / 360) 360, then + 360 if below lon[0], then - 360 if
+ *            not below lon[0] + 360.  lat_out / lon_out hold these positions.
+ *   cell     from the stored position by exact comparisons: j0 the last row with lat[j0] <= y, j1 = min(j0 + 1, ny - 1), the
+ *            columns likewise; with cyclic_x the cell after the last column ends at lon[0] + 360 in column 0.  A position
+ *            outside [lat[0], lat[ny - 1]], or without cyclic_x outside [lon[0], lon[nx - 1]], is NaN.
+ *   value    LC_TRANSECT_LINEAR: w_y = (y - lat[j0]) / (lat[j1] - lat[j0]) (0 where j1 == j0), w_x likewise,
+ *            ((w00 v00 + w01 v01) + w10 v10) + w11 v11 with w00 = (1 - w_y)(1 - w_x), w01 = (1 - w_y) w_x, w10 = w_y (1 - w_x),
+ *            w11 = w_y w_x, the corners widened to float64, the sum rounded to `dtype` once; NaN when a corner is NaN.
+ *            LC_TRANSECT_NEAREST: row j1 where y - lat[j0] > lat[j1] - y, else j0 (ties to the lower index), columns likewise.
+ *   fields   `dtype` [n_fields][n_planes][ny][nx]; the points of a line of plane m read plane m of every field.
+ * Outputs: normal_out float64 [7][n_points]: n_x, n_y, n_z, n_east, n_north, t_east, t_north; lat_out, lon_out float64
+ *   [n_points][n_offsets]; values_out `dtype` [n_fields][n_points][n_offsets]; mean_out `dtype` and count_out int32
+ *   [n_fields][n_lines][n_offsets]: the mean of the finite values of the line's points at that offset, accumulated in float64,
+ *   and how many there were; NaN where there were none.  The order of summation depends on the sizes alone: two calls agree
+ *   bit for bit.  There is no atomic operation and no kernel waits for another workgroup.
+ * Refused with LC_EINVAL before any HIP call: a null context, argument structure or pointer, a wrong struct_size, a dtype other
+ * than LC_F32 / LC_F64, ny or nx < 2, another size < 1, an even n_offsets, smooth < 1, an unknown orient or method, cyclic_x with
+ * fewer than 3 columns; with LC_EUNSUPPORTED: ny nx, n_points n_offsets or n_lines n_offsets of 2^31 or more, more than 65535
+ * fields.  lc_ctx_last_transects_kernel: the kernels of the last call joined by '+' ("" before the first call or for a null
+ * context); it replaces nothing of LCS/area_of_influence.py:17-87 but names what ran in its place. */
+enum { LC_ORIENT_LEFT = 0, LC_ORIENT_NORTH = 1, LC_ORIENT_EAST = 2 };
+enum { LC_TRANSECT_LINEAR = 0, LC_TRANSECT_NEAREST = 1 };
+typedef struct lc_transects_args {
+    size_t struct_size; /* sizeof(lc_transects_args): checked before any other field */
+    const int *pixel, *point_line;                      /* device, int32 [n_points] */
+    const int *line_offset, *line_count, *line_plane;   /* device, int32 [n_lines] */
+    const unsigned char *line_closed;                   /* device, [n_lines] */
+    const double *cos_lat, *sin_lat, *cos_lon, *sin_lon; /* device */
+    const double *lat_deg, *lon_deg;                    /* device, ascending degrees */
+    const double *cos_off, *sin_off;                    /* device, [n_offsets] */
+    const void *fields;                                 /* dtype [n_fields][n_planes][ny][nx] */
+    int dtype, ny, nx, n_planes, n_points, n_lines, n_offsets, n_fields;
+    int smooth, orient, method, cyclic_x;
+    double *normal_out;        /* [7][n_points] */
+    double *lat_out, *lon_out; /* [n_points][n_offsets] */
+    void *values_out;          /* dtype [n_fields][n_points][n_offsets] */
+    void *mean_out;            /* dtype [n_fields][n_lines][n_offsets] */
+    int *count_out;            /* [n_fields][n_lines][n_offsets] */
+} lc_transects_args;
+int lc_ridge_transects(lc_ctx *ctx, const lc_transects_args *args);
+const char *lc_ctx_last_transects_kernel(const lc_ctx *ctx);
+
 /* ---- multi-GPU: halo exchange on RCCL ----------------------------------------
  * New (the reference is single-process).  One process per GPU,
  * seed rows block-partitioned, wind replicated; lc_advect needs no communication

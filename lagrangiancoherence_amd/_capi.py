@@ -301,6 +301,28 @@ PROTOTYPES["lc_idw_interp"] = (_i, [_vp, C.POINTER(IdwArgs)])
 PROTOTYPES["lc_ctx_last_idw_kernel"] = (C.c_char_p, [_vp])
 
 
+LC_ORIENT_LEFT, LC_ORIENT_NORTH, LC_ORIENT_EAST = 0, 1, 2
+LC_TRANSECT_LINEAR, LC_TRANSECT_NEAREST = 0, 1
+
+
+class TransectsArgs(C.Structure):
+    """``lc_transects_args`` of include/lcs_hip.h, field for field."""
+    _fields_ = [("struct_size", _sz),
+                ("pixel", _vp), ("point_line", _vp),
+                ("line_offset", _vp), ("line_count", _vp), ("line_plane", _vp), ("line_closed", _vp),
+                ("cos_lat", _vp), ("sin_lat", _vp), ("cos_lon", _vp), ("sin_lon", _vp),
+                ("lat_deg", _vp), ("lon_deg", _vp), ("cos_off", _vp), ("sin_off", _vp),
+                ("fields", _vp),
+                ("dtype", _i), ("ny", _i), ("nx", _i), ("n_planes", _i), ("n_points", _i), ("n_lines", _i), ("n_offsets", _i),
+                ("n_fields", _i),
+                ("smooth", _i), ("orient", _i), ("method", _i), ("cyclic_x", _i),
+                ("normal_out", _vp), ("lat_out", _vp), ("lon_out", _vp), ("values_out", _vp), ("mean_out", _vp), ("count_out", _vp)]
+
+
+PROTOTYPES["lc_ridge_transects"] = (_i, [_vp, C.POINTER(TransectsArgs)])
+PROTOTYPES["lc_ctx_last_transects_kernel"] = (C.c_char_p, [_vp])
+
+
 
 class RidgesArgs(C.Structure):
     """``lc_ridges_args`` of include/lcs_hip.h, field for field."""

@@ -102,6 +102,7 @@ extern "C" int lc_ctx_create(int device, lc_ctx **out) {
     c->last_ridges_kernel = "";
     c->last_threshold_kernel = "";
     c->last_idw_kernel = "";
+    c->last_transects_kernel = "";
     c->verify_dev = nullptr;
     c->trunc = nullptr;
     c->xfer = nullptr;

@@ -2034,6 +2034,132 @@ class Engine:
                "links": links if len(shape) == 3 else links[0], "counts": counts}
         return out
 
+    # ------------------------------------------------------------------ great-circle transects across ridge lines
+    ORIENTS = {"left": _capi.LC_ORIENT_LEFT, "north": _capi.LC_ORIENT_NORTH, "east": _capi.LC_ORIENT_EAST}
+    TRANSECT_METHODS = {"linear": _capi.LC_TRANSECT_LINEAR, "nearest": _capi.LC_TRANSECT_NEAREST}
+
+    @property
+    def last_transects_kernel(self) -> str:
+        """Names of the kernels the last :meth:`ridge_transects` call launched (``lc_ctx_last_transects_kernel``), joined by
+        ``+``."""
+        return self.lib.lc_ctx_last_transects_kernel(self.ctx).decode()
+
+    @staticmethod
+    def checked_transect_options(shape, lat, lon, half_width, spacing, smooth=3, orient='left', method='linear', cyclic=False,
+                                 radius=6371000.0, n_points=0, n_lines=0):
+        """Every refusal of :meth:`ridge_transects`' arguments (``ValueError``), on the host: no device is touched.  ``shape``
+        is the planes' ``(ny, nx)`` or ``(n_planes, ny, nx)``; ``n_points`` and ``n_lines`` are the sizes of the trace, where
+        they are known.  Returns what the call hands to the device: a dict of ``tables`` (:meth:`sphere_tables`' four), ``lat``,
+        ``lon`` (float64 degrees), ``offset`` (``s_k = k spacing``, ``k = -K .. K``, ``K = floor(half_width / spacing)``),
+        ``cos_off`` / ``sin_off`` (numpy's ``cos(s_k / radius)`` and ``sin(s_k / radius)``), ``K``, ``M = 2 K + 1``,
+        ``smooth``, ``orient`` and ``method`` (the library's codes) and ``radius``."""
+        if orient not in Engine.ORIENTS:
+            raise ValueError(f"orient {orient!r}: 'left', 'north' or 'east'")
+        if method not in Engine.TRANSECT_METHODS:
+            raise ValueError(f"method {method!r}: 'linear' or 'nearest'")
+        spacing, half_width = float(spacing), float(half_width)
+        if not (spacing > 0 and np.isfinite(spacing)):
+            raise ValueError(f"spacing {spacing!r}: a positive, finite number")
+        if not (half_width >= 0 and np.isfinite(half_width)):
+            raise ValueError(f"half_width {half_width!r}: >= 0 and finite")
+        if int(smooth) != smooth or int(smooth) < 1 or int(smooth) >= 2 ** 30:
+            raise ValueError(f"smooth {smooth!r}: a whole number >= 1 (points before and after, below 2^30)")
+        shape = tuple(int(s) for s in shape)
+        if len(shape) not in (2, 3) or min(shape) < 1:
+            raise ValueError("a plane (ny, nx) or a stack of planes (n_planes, ny, nx), none of them empty")
+        ny, nx = shape[-2:]
+        cl, sl, cx, sx, radius, _, _ = Engine.sphere_tables(lat, lon, radius)
+        lat, lon = np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64)
+        if (lat.size, lon.size) != (ny, nx):
+            raise ValueError(f"planes {shape}: ny = len(lat) = {lat.size} and nx = len(lon) = {lon.size}")
+        if ny < 2 or nx < 2:
+            raise ValueError("lat and lon: at least two values each (a cell needs a neighbour)")
+        if not ((np.diff(lat) > 0).all() and (np.diff(lon) > 0).all()):
+            raise ValueError("lat and lon: distinct and ascending (tools.ridge_transects sorts them)")
+        if not half_width / radius < np.pi / 2:
+            raise ValueError(f"half_width {half_width!r} on a sphere of radius {radius!r}: below a quarter of the circumference "
+                             "(half_width / radius < pi / 2)")
+        if cyclic and nx < 3:
+            raise ValueError(f"cyclic needs at least 3 columns, got {nx}: a pixel would neighbour itself or one pixel twice")
+        if cyclic and not lon[-1] - lon[0] < 360.0:
+            raise ValueError(f"cyclic: the longitudes span {lon[-1] - lon[0]!r} degrees, which must be less than 360 (the seam cell "
+                             "lies between the last one and the first one + 360)")
+        K = int(np.floor(half_width / spacing))
+        M = 2 * K + 1
+        if ny * nx >= 2 ** 31 or M >= 2 ** 31 or int(n_points) * M >= 2 ** 31 or int(n_lines) * M >= 2 ** 31:
+            raise ValueError(f"too large: {ny} x {nx} pixels, {int(n_points)} points and {int(n_lines)} lines with {M} offsets "
+                             "(ny nx, n_points M and n_lines M stay below 2^31)")
+        offset = np.arange(-K, K + 1, dtype=np.float64) * np.float64(spacing)
+        angle = offset / np.float64(radius)
+        return {"tables": (cl, sl, cx, sx), "lat": lat, "lon": lon, "offset": offset, "cos_off": np.cos(angle), "sin_off": np.sin(angle),
+                "K": K, "M": M, "smooth": int(smooth), "orient": Engine.ORIENTS[orient], "method": Engine.TRANSECT_METHODS[method],
+                "radius": radius}
+
+    def ridge_transects(self, trace, fields, lat, lon, half_width, spacing, smooth=3, orient='left', method='linear', cyclic=False,
+                        radius=6371000.0):
+        """Fields sampled along great circles across the lines of a thinned mask, and the samples averaged per line
+        (``lc_ridge_transects``; include/lcs_hip.h states the definition, tests/transects.py restates it in numpy).
+
+        ``trace`` is what :meth:`trace_lines` returned for the mask (its ``line``, ``pixel``, ``plane``, ``offset``, ``count``
+        and ``closed`` are read).  ``fields``: ``(n_fields, ny, nx)``, or ``(n_fields, n_planes, ny, nx)`` for a trace of a stack
+        -- the points of plane ``m`` read plane ``m`` of every field --, float32 or float64 (anything else is converted to
+        float64), numpy or device tensor.  ``lat`` ``(ny,)`` and ``lon`` ``(nx,)`` are degrees, ascending and distinct (they
+        need not be uniform); ``cyclic``: the cell after the last longitude ends at ``lon[0] + 360``.
+
+        Through every point a great circle at right angles to the line -- to the chord between the points ``smooth`` before and
+        after it, clamped at the ends of an open line and wrapped on a ring -- is sampled at the signed distances ``k spacing``,
+        ``|k| <= floor(half_width / spacing)``, in the unit of ``radius``; positive offsets lie to the left of the direction of
+        travel (``orient='left'``), or on the side whose normal points north (``'north'``) or east (``'east'``).
+        ``method``: ``'linear'`` (bilinear in degrees, NaN where a corner is NaN) or ``'nearest'``.  Positions outside the grid
+        give NaN; so do points without a tangent (lines of one point).
+
+        Returns a dict of device tensors: ``offset`` ``(M,)``; per point ``normal`` ``(n_points, 3)``, ``normal_east``,
+        ``normal_north``, ``tangent_east``, ``tangent_north``; ``latitude``, ``longitude`` ``(n_points, M)`` float64 degrees;
+        ``values`` ``(n_fields, n_points, M)`` in the fields' dtype; ``line_mean`` (that dtype) and ``line_count`` (int32)
+        ``(n_fields, n_lines, M)``: the mean of the finite values of a line's points, offset by offset, NaN where there are
+        none.  Two calls agree bit for bit."""
+        torch = self.torch
+        fshape = tuple(int(s) for s in fields.shape) if hasattr(fields, "shape") else np.shape(fields)
+        if len(fshape) not in (3, 4) or min(fshape, default=0) < 1:
+            raise ValueError(f"fields {fshape}: (n_fields, ny, nx) or (n_fields, n_planes, ny, nx), none of them empty")
+        n_points, n_lines = int(trace["pixel"].numel()), int(trace["count"].numel())
+        opt = self.checked_transect_options(fshape[1:], lat, lon, half_width, spacing, smooth, orient, method, cyclic, radius,
+                                            n_points, n_lines)
+        links = tuple(int(s) for s in trace["links"].shape)
+        if links != fshape[1:]:
+            raise ValueError(f"fields {fshape}: their planes {fshape[1:]} are not the traced mask's {links}")
+        if fshape[0] > 65535:
+            raise ValueError(f"{fshape[0]} fields: at most 65535 per call")
+        dtype = np.dtype(str(fields.dtype).replace("torch.", "")) if hasattr(fields, "dtype") else np.asarray(fields).dtype
+        dtype = dtype if dtype in _NP2LC else np.dtype(np.float64)
+        f = self.to_device(fields, dtype)
+        n_fields, (ny, nx) = fshape[0], fshape[-2:]
+        n_planes = fshape[1] if len(fshape) == 4 else 1
+        M, dev, i32 = opt["M"], self.device, torch.int32
+        normal = self._empty((7, n_points), np.float64)
+        latitude, longitude = self._empty((n_points, M), np.float64), self._empty((n_points, M), np.float64)
+        values = self._empty((n_fields, n_points, M), dtype)
+        mean = self._empty((n_fields, n_lines, M), dtype)
+        count = torch.zeros((n_fields, n_lines, M), dtype=i32, device=dev)
+        if n_points:
+            keep = [trace[k].to(i32).contiguous() for k in ("pixel", "line", "offset", "count", "plane")]
+            closed = trace["closed"].to(torch.uint8).contiguous()
+            tables = [self.to_device(t, np.float64) for t in (*opt["tables"], opt["lat"], opt["lon"], opt["cos_off"], opt["sin_off"])]
+            a = _capi.TransectsArgs(struct_size=C.sizeof(_capi.TransectsArgs))
+            a.pixel, a.point_line, a.line_offset, a.line_count, a.line_plane = (t.data_ptr() for t in keep)
+            a.line_closed = closed.data_ptr()
+            a.cos_lat, a.sin_lat, a.cos_lon, a.sin_lon, a.lat_deg, a.lon_deg, a.cos_off, a.sin_off = (t.data_ptr() for t in tables)
+            a.fields, a.dtype = f.data_ptr(), _NP2LC[dtype]
+            a.ny, a.nx, a.n_planes, a.n_points, a.n_lines, a.n_offsets, a.n_fields = ny, nx, n_planes, n_points, n_lines, M, n_fields
+            a.smooth, a.orient, a.method, a.cyclic_x = opt["smooth"], opt["orient"], opt["method"], int(bool(cyclic))
+            a.normal_out, a.lat_out, a.lon_out = normal.data_ptr(), latitude.data_ptr(), longitude.data_ptr()
+            a.values_out, a.mean_out, a.count_out = values.data_ptr(), mean.data_ptr(), count.data_ptr()
+            self._use_current_stream()
+            _capi.check(self.lib.lc_ridge_transects(self.ctx, C.byref(a)), self.lib)
+        return {"offset": self.to_device(opt["offset"], np.float64), "normal": normal[:3].T, "normal_east": normal[3],
+                "normal_north": normal[4], "tangent_east": normal[5], "tangent_north": normal[6], "latitude": latitude,
+                "longitude": longitude, "values": values, "line_mean": mean, "line_count": count}
+
     # ------------------------------------------------------------------ multi-GPU (RCCL through the C ABI)
     COMM_ID_BYTES = 128
 

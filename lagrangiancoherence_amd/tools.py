@@ -28,6 +28,10 @@
                                     its great-circle length, its ends and branch points, the intensity along it -- the vector form
                                     of what ``skeletonize_ridges`` returns, which the reference's chain of rasters never reaches
                                     (defined here)
+* ``ridge_transects``                what other fields do beside a ridge: great-circle transects across the traced lines, the
+                                    profile of rain, water vapour or pressure against the signed distance from the ridge and its
+                                    composite per line -- the well-defined part of ``find_area`` (LCS/area_of_influence.py:17-87;
+                                    defined here)
 * ``Inverse_weighted_interpolation`` LCS/tools.py:285-299 and its labelled wrapper ``xr_idx_interp`` (LCS/tools.py:302-333): values
                                     known at scattered longitude / latitude points -- what ``parcel_propagation(..., C=)`` samples
                                     along trajectories, at the positions ``return_traj`` hands out -- gridded by inverse-distance
@@ -47,6 +51,7 @@ from .engine import Engine, common_dtype
 __all__ = ["xr_map_coordinates", "fourth_order_derivative", "derivative_spherical_coords",
            "find_ridges_spherical_hessian", "filter_ridges", "distance_to_ridges", "skeletonize_ridges", "dilate_ridges",
            "threshold_local", "above_local_threshold", "track_ridges", "persistent_ridges", "ridge_properties", "ridge_lines",
+           "ridge_transects",
            "Inverse_weighted_interpolation", "xr_idx_interp"]
 
 
@@ -407,6 +412,13 @@ def ridge_lines(ridges, intensity=None, cyclic=False, metric='sphere', radius=63
     ``metric='sphere'`` (the default): lengths are great-circle arcs in the unit of ``radius`` (metres on the default Earth),
     link by link, from the array's own coordinates in degrees (distinct, ``|latitude| <= 90``).  ``metric='index'``: a link
     counts 1 along an edge and ``sqrt(2)`` across a corner."""
+    return _traced_ridge_lines(ridges, intensity, cyclic, metric, radius)[:2]
+
+
+def _traced_ridge_lines(ridges, intensity, cyclic, metric, radius, before_engine=None):
+    """``ridge_lines``' two tables and, for ``ridge_transects``, what they were made from: the engine, the device trace, the
+    sorted coordinates and the function that brings a field into the traced order.  ``before_engine(lat, lon, shape)`` runs
+    after this function's own checks and before an engine is asked for."""
     if metric not in Engine.METRICS:
         raise ValueError(f"metric {metric!r}: 'index' or 'sphere'")
     dims = tuple(ridges.dims)
@@ -432,11 +444,13 @@ def ridge_lines(ridges, intensity=None, cyclic=False, metric='sphere', radius=63
     v = sorted_values(ridges)
     Engine.checked_line_options(v.shape, cyclic, metric, lat, lon, radius, None)
     w = None if intensity is None else sorted_values(intensity).astype(np.float64).reshape(-1, lat.size, lon.size)
+    if before_engine is not None:
+        before_engine(lat, lon, v.shape)
     eng = get_engine()
     mask = eng.to_device(v, v.dtype)
-    t = eng.trace_lines(mask, cyclic, metric, lat if metric == 'sphere' else None, lon if metric == 'sphere' else None, radius)
+    traced = eng.trace_lines(mask, cyclic, metric, lat if metric == 'sphere' else None, lon if metric == 'sphere' else None, radius)
     labels, _ = eng.label_components(mask, 2, cyclic)
-    t = {k: _to_np(x) for k, x in t.items()}
+    t = {k: _to_np(x) for k, x in traced.items()}
     labels = _to_np(labels).reshape(-1, lat.size * lon.size)
     nx = lon.size
     plane, first, last = t["plane"].astype(np.int64), t["first"].astype(np.int64), t["last"].astype(np.int64)
@@ -474,7 +488,76 @@ def ridge_lines(ridges, intensity=None, cyclic=False, metric='sphere', radius=63
         for name, op in (("max_intensity", np.maximum), ("min_intensity", np.minimum)):
             lines[name] = op.reduceat(value, at) if at.size else np.zeros(0)
         lines["mean_intensity"] = (np.add.reduceat(value, at) / lines["count"]) if at.size else np.zeros(0)
-    return lines, points
+    return lines, points, {"engine": eng, "trace": traced, "lat": lat, "lon": lon, "sorted_values": sorted_values}
+
+
+def ridge_transects(ridges, fields, half_width, spacing, smooth=3, orient='left', method='linear', cyclic=False, radius=6371000.0):
+    """What other fields do beside a ridge: every field of ``fields`` sampled along great circles across the lines of a
+    thinned mask, as a function of the signed distance from the line, and the composite of those profiles per line -- the rain,
+    water vapour or pressure profile across a convergence zone, which the reference's driver approximates by painting pixels
+    along the Hessian eigenvector (``find_area``, LCS/area_of_influence.py:17-87; its painted mask is not reproduced: it steps in
+    degrees, which is wrong away from the equator, and gives the normal's sign no meaning).  Returns ``(lines, points,
+    transects)`` (``Engine.ridge_transects``; include/lcs_hip.h states the definition).
+
+    ``ridges``: as for ``ridge_lines`` -- a thinned mask over ``latitude`` and ``longitude`` with at most one more dimension,
+    sorted ascending here; a pixel is foreground when it is ``!= 0`` and not NaN.  ``lines`` and ``points`` are exactly what
+    ``ridge_lines(ridges, None, cyclic, 'sphere', radius)`` returns; ``points`` additionally carries ``normal_east``,
+    ``normal_north`` (the components of the unit normal the transect leaves the point along, towards positive offsets) and
+    ``heading`` (degrees clockwise from north of the direction of travel along the line, in ``[0, 360)``; NaN where the point
+    has no tangent: lone pixels and lines of one point).
+
+    ``fields``: one labelled array, or a dict of name -> array, each with the dims and coordinates of ``ridges``; float32 or
+    float64 (anything else is converted to float64; mixed dtypes to float64), and the results take that dtype.  With a 3-D
+    input the points of each plane read that plane of every field.
+
+    The transect through a point is the great circle at right angles to the line there -- to the chord between the points
+    ``smooth`` before and after it along the line, clamped at the ends of an open line and wrapped on a ring.  It is sampled at
+    the offsets ``s_k = k * spacing`` for ``k = -K .. K``, ``K = floor(half_width / spacing)``, in the unit of ``radius`` (metres
+    on the default Earth).  ``orient='left'``: positive offsets lie to the left of the direction of travel; ``'north'``: on the
+    side whose normal has a positive north component (east where it has none); ``'east'``: likewise with east first.
+    ``method='linear'``: bilinear in degrees between the four nodes around the position, NaN where one of them is NaN;
+    ``'nearest'``: the nearer node in each axis.  The latitudes need not be uniform.  Positions outside the grid are NaN;
+    ``cyclic``: longitudes are wrapped into ``[longitude[0], longitude[0] + 360)`` and the cell after the last one ends at the
+    first (a span below 360 degrees).
+
+    ``transects`` is a dict of numpy arrays with ``M = 2 K + 1``: ``offset`` ``(M,)``; ``latitude``, ``longitude`` ``(n_points,
+    M)`` float64, the sample positions in degrees as the device wrote them; ``values`` ``(n_fields, n_points, M)``, or a dict by
+    name when a dict was given; ``line_mean`` and ``line_count`` ``(n_fields, n_lines, M)`` (dicts likewise): the mean of the
+    finite values over the points of each line, offset by offset, and how many entered it (NaN where none did).  The
+    cross-ridge gradient at the ridge is ``(values[:, :, K + 1] - values[:, :, K - 1]) / (2 * spacing)``."""
+    named = isinstance(fields, dict)
+    group = dict(fields) if named else {None: fields}
+    if not group:
+        raise ValueError("fields: a labelled array or a dict of name -> array with at least one entry")
+    dims = tuple(ridges.dims)
+    glat, glon = _coord(ridges, "latitude"), _coord(ridges, "longitude")
+    for name, da in group.items():
+        if not hasattr(da, "dims") or set(da.dims) != set(dims):
+            raise ValueError(f"ridges and fields{'' if name is None else f'[{name!r}]'} differ in their dims")
+        if not (np.array_equal(_coord(da, "latitude"), glat) and np.array_equal(_coord(da, "longitude"), glon)):
+            raise ValueError(f"ridges and fields{'' if name is None else f'[{name!r}]'} differ in their coordinates")
+        if dict(zip(da.dims, np.shape(da.values))) != dict(zip(dims, np.shape(ridges.values))):
+            raise ValueError(f"ridges and fields{'' if name is None else f'[{name!r}]'} differ in their shapes")
+
+    def check(lat, lon, shape):                                                # every refusal, before a device
+        Engine.checked_transect_options(shape, lat, lon, half_width, spacing, smooth, orient, method, cyclic, radius)
+    lines, points, made = _traced_ridge_lines(ridges, None, cyclic, 'sphere', radius, before_engine=check)
+    stack = [made["sorted_values"](da) for da in group.values()]
+    dtype = stack[0].dtype if all(v.dtype == stack[0].dtype for v in stack) else np.dtype(np.float64)
+    stack = np.stack([v.astype(dtype, copy=False) for v in stack])
+    got = made["engine"].ridge_transects(made["trace"], stack, made["lat"], made["lon"], half_width, spacing, smooth, orient,
+                                         method, cyclic, radius)
+    got = {k: _to_np(v) for k, v in got.items()}
+    points["normal_east"], points["normal_north"] = got["normal_east"], got["normal_north"]
+    with np.errstate(invalid="ignore"):
+        heading = np.mod(np.degrees(np.arctan2(got["tangent_east"], got["tangent_north"])), 360.0)
+        points["heading"] = np.where(heading >= 360.0, 0.0, heading)        # (a tiny negative angle rounds up to 360 itself)
+
+    def by_name(a):
+        return {name: a[k] for k, name in enumerate(group)} if named else a
+    transects = {"offset": got["offset"], "latitude": got["latitude"], "longitude": got["longitude"], "values": by_name(got["values"]),
+                 "line_mean": by_name(got["line_mean"]), "line_count": by_name(got["line_count"])}
+    return lines, points, transects
 
 
 def distance_to_ridges(ridges, cyclic=False, sampling=None, max_distance=None, return_labels=False, connectivity=2,
