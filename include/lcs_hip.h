@@ -38,7 +38,7 @@ extern "C" {
  * client built against 100 must be rebuilt), lc_ctx_get_level_chunk, lc_ctx_set/get_f64_fidelity, lc_advect_ex and
  * lc_sample_raw added, lc_field_pack accepts packed_dev == NULL at order 1 (fused-level image only).  lc_version() returns the value the LIBRARY
  * was built with: compare it with this macro before any other call (tests/c/abi_smoke.c, _capi.load do). */
-#define LC_VERSION 104 /* 0.1.4: + lc_mask_morphology, lc_morph_work_elems (added without a bump), + lc_label_components, lc_label_work_elems, lc_component_sums, lc_component_apply, + lc_strain, lc_ctx_last_strain_kernel, + lc_advect_series_dirs, + lc_advect_series, lc_sigma_batch, + lc_tracer_sample, lc_ctx_last_tracer_kernel (additive: no argument list changed), + lc_ctx_set_host_pipeline, lc_copy_to_device, lc_copy_to_host, lc_ctx_set_host_cache, lc_ctx_trim, lc_ctx_last_host_marks, lc_ctx_set_xcd_split (0.1.3: + lc_ctx_last_pack_kernel; 0.1.2: + lc_ctx_set_verify, lc_ctx_read_verify, LC_F64_WIND_F32_LIN32) */
+#define LC_VERSION 104 /* 0.1.4: + lc_aux_gradient, lc_ctx_last_aux_kernel (added without a bump), + lc_mask_morphology, lc_morph_work_elems (added without a bump), + lc_label_components, lc_label_work_elems, lc_component_sums, lc_component_apply, + lc_strain, lc_ctx_last_strain_kernel, + lc_advect_series_dirs, + lc_advect_series, lc_sigma_batch, + lc_tracer_sample, lc_ctx_last_tracer_kernel (additive: no argument list changed), + lc_ctx_set_host_pipeline, lc_copy_to_device, lc_copy_to_host, lc_ctx_set_host_cache, lc_ctx_trim, lc_ctx_last_host_marks, lc_ctx_set_xcd_split (0.1.3: + lc_ctx_last_pack_kernel; 0.1.2: + lc_ctx_set_verify, lc_ctx_read_verify, LC_F64_WIND_F32_LIN32) */
 
 typedef struct lc_ctx lc_ctx;
 
@@ -604,6 +604,38 @@ int lc_strain(lc_ctx *ctx, const void *x_dep, const void *y_dep, int dtype, int 
               const void *seed_lat_dev, double dlat, double dlon, int fd_fp32_cast, int n_members,
               void *s1_out, void *s2_out, void *e_lon_out, void *e_lat_out);
 const char *lc_ctx_last_strain_kernel(const lc_ctx *ctx);
+
+/* The flow-map gradient from an AUXILIARY GRID, reduced in one launch: for callers who advect four extra parcels per output
+ * point, seeded at (lat[r], lon[c] +- d_lon) and (lat[r] +- d_lat, lon[c]), and hand their departure points in.  Replaces
+ * LCS.flowmap_gradient (LCS/LCS.py:171-225) + tools.derivative_spherical_coords (LCS/tools.py:248-267) + the singular value
+ * (LCS/LCS.py:152-154) where the caller asks for it, and differs from them on purpose:
+ *   - the six derivatives are centred differences of the four auxiliary parcels of the SAME output point, not a 5-point index
+ *     stencil over neighbouring output points: no cyclic longitude wrap, no one-sided / 2 rows, ny and nx may be 1;
+ *   - the chords P_e - P_w and P_n - P_s on the reference's sphere (LCS/LCS.py:195-199) are formed from half-sums and
+ *     half-differences of the angles (no cancellation), in the dtype; X, Y, Z are never rounded to float32 (Q11);
+ *   - dXdx = dX_ew / (k sep_lon[c] R cos(k seed_lat[r])), dXdy = dX_ns / (k sep_lat[r] R), k = pi / 180, likewise Y and Z;
+ *   - a NaN in any of a cell's eight inputs, or in its sep_lat / sep_lon, gives NaN in every output of that cell and in no
+ *     other cell (the caller marks invalid rows / columns with a NaN separation).
+ *   x_e .. y_s     departure points of the east, west, north and south parcels, [n_members][ny*nx] dtype elements
+ *   seed_lat_dev   [ny] latitudes of the output rows (the centre grid)
+ *   sep_lat_dev    [ny] lat_n[r] - lat_s[r], sep_lon_dev [nx] lon_e[c] - lon_w[c], in degrees, from the coordinates as rounded
+ *   tensor_layout  for sigma_out only: LC_LAYOUT_REFERENCE is lc_sigma's value of these derivatives, LC_LAYOUT_PHYSICAL equals s1
+ *   sigma_out, s1_out, s2_out, e_lon_out, e_lat_out   [n_members][ny*nx]; s1, s2 and the direction as lc_strain defines them
+ *                  (same sign and isotropy rules); each may be NULL (not written), at least one is not
+ * dtype LC_F32 or LC_F64.  Refused with LC_EINVAL before any HIP call: a null context or argument structure, a wrong
+ * struct_size, a bad dtype or tensor_layout, ny or nx < 1, a plane of 2^31 cells or more, n_members outside 1..65535, a null
+ * input, no output.  lc_ctx_last_aux_kernel: what the context's last lc_aux_gradient launched ("" before any, or for a null
+ * context): "aux_gradient_kernel_f32" or "aux_gradient_kernel<double>". */
+typedef struct lc_aux_gradient_args {
+    size_t struct_size; /* sizeof(lc_aux_gradient_args): checked before any other field */
+    const void *x_e, *y_e, *x_w, *y_w, *x_n, *y_n, *x_s, *y_s;
+    int dtype, ny, nx, n_members;
+    const void *seed_lat_dev, *sep_lat_dev, *sep_lon_dev;
+    int tensor_layout;
+    void *sigma_out, *s1_out, *s2_out, *e_lon_out, *e_lat_out;
+} lc_aux_gradient_args;
+int lc_aux_gradient(lc_ctx *ctx, const lc_aux_gradient_args *args);
+const char *lc_ctx_last_aux_kernel(const lc_ctx *ctx);
 
 /* The 9-component "def_tensor" itself, for callers of LCS.flowmap_gradient
  * (LCS/LCS.py:171-225): planes dXdx,dXdy,dYdx,dYdy,dZdx,dZdy,dXdr,dYdr,dZdr (the last

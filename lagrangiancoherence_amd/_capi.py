@@ -341,6 +341,20 @@ PROTOTYPES["lc_ridges_work_elems"] = (_sz, [_i, _i, _i])
 PROTOTYPES["lc_ridges_batch"] = (_i, [_vp, C.POINTER(RidgesArgs)])
 PROTOTYPES["lc_ctx_last_ridges_kernel"] = (C.c_char_p, [_vp])
 
+
+class AuxGradientArgs(C.Structure):
+    """``lc_aux_gradient_args`` of include/lcs_hip.h, field for field."""
+    _fields_ = [("struct_size", _sz),
+                ("x_e", _vp), ("y_e", _vp), ("x_w", _vp), ("y_w", _vp), ("x_n", _vp), ("y_n", _vp), ("x_s", _vp), ("y_s", _vp),
+                ("dtype", _i), ("ny", _i), ("nx", _i), ("n_members", _i),
+                ("seed_lat_dev", _vp), ("sep_lat_dev", _vp), ("sep_lon_dev", _vp),
+                ("tensor_layout", _i),
+                ("sigma_out", _vp), ("s1_out", _vp), ("s2_out", _vp), ("e_lon_out", _vp), ("e_lat_out", _vp)]
+
+
+PROTOTYPES["lc_aux_gradient"] = (_i, [_vp, C.POINTER(AuxGradientArgs)])
+PROTOTYPES["lc_ctx_last_aux_kernel"] = (C.c_char_p, [_vp])
+
 _lib = None
 
 

@@ -1,6 +1,7 @@
 // The flow-map gradient on chip, shared by sigma.hip and strain.hip: per seed, the six derivatives
 //   dXdx, dXdy, dYdx, dYdy, dZdx, dZdy
 // of the departure point's X, Y, Z on the sphere along the seed grid, and the 2 x 2 Gram eigenvalue both files reduce them with.
+// The Gram step and the strain step (stretch_of) are also what aux_gradient.hip reduces its own six derivatives with.
 // Restates
 //   LCS.flowmap_gradient               LCS/LCS.py:195-208    lon/lat -> X,Y,Z on the sphere
 //   tools.derivative_spherical_coords  LCS/tools.py:254-264  metric dx, dy
@@ -280,6 +281,49 @@ __device__ __forceinline__ Gram gram_eigen(int layout, double a_, double b_, dou
     const double disc = sqrt(dpq * dpq + 4.0 * g.r * g.r);
     g.lam = 0.5 * ((g.p + g.q) + disc);
     return g;
+}
+
+// ======================================================================================
+// Strain step, float64 for both arithmetics, shared by strain.hip and aux_gradient.hip: both singular values of the 3 x 2
+// Jacobian [[a, b], [c, d], [e, f]] (a..f = dXdx, dXdy, dYdx, dYdy, dZdx, dZdy; physical layout) and the unit eigenvector
+// (ex, ey) of F^T F for the larger eigenvalue in (east, north) components.  s2 = |col1 x col2| / s1 (0 where s1 == 0).
+// Sign: ex > 0, or ex == 0 and ey > 0; (1, 0) where F^T F is a multiple of the identity.  NaN in -> NaN in every member.
+// s2 / the direction are only computed where asked for (the others are left 0).
+// ======================================================================================
+struct Stretch {
+    double s1, s2, ex, ey;
+};
+__device__ __forceinline__ Stretch stretch_of(double a_, double b_, double c_, double d_, double e_, double f_, bool want_s2,
+                                              bool want_dir) {
+#pragma clang fp contract(off)
+    const auto [p, q, r, lam] = gram_eigen(LC_LAYOUT_PHYSICAL, a_, b_, c_, d_, e_, f_);
+    Stretch s = {sqrt(lam), 0.0, 0.0, 0.0};  // NaN in -> NaN out (Q14)
+    if (want_s2) {
+        // |col1 x col2| = s1 s2 = sqrt(det F^T F) without the cancellation of (p + q) - disc
+        const double cx = c_ * f_ - e_ * d_, cy = e_ * b_ - a_ * f_, cz = a_ * d_ - c_ * b_;
+        const double area = sqrt(cx * cx + cy * cy + cz * cz);
+        s.s2 = s.s1 == 0.0 ? 0.0 : area / s.s1;
+    }
+    if (want_dir) {
+        // (F^T F - lam I) e = 0: the row that does not cancel
+        double vx = p >= q ? lam - q : r;
+        double vy = p >= q ? r : lam - p;
+        const double n = sqrt(vx * vx + vy * vy);
+        if (n == 0.0) {  // isotropic cell (disc == 0)
+            vx = 1.0;
+            vy = 0.0;
+        } else {  // (NaN stays NaN: no comparison below holds for it)
+            vx = vx / n;
+            vy = vy / n;
+            if (vx < 0.0 || (vx == 0.0 && vy < 0.0)) {
+                vx = -vx;
+                vy = -vy;
+            }
+        }
+        s.ex = vx;
+        s.ey = vy;
+    }
+    return s;
 }
 
 }  // namespace

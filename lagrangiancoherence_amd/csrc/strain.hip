@@ -43,39 +43,16 @@ __device__ __forceinline__ StrainArgs<T> strain_member(const StrainArgs<T> &A0) 
     return A;
 }
 
-// Eigen step, float64: a..f = dXdx, dXdy, dYdx, dYdy, dZdx, dZdy.  p, q, r, lam: the Gram step sigma.hip runs, physical layout.
+// Eigen step, float64: a..f = dXdx, dXdy, dYdx, dYdy, dZdx, dZdy.  The Gram step sigma.hip runs (physical layout) and the
+// strain step, both flowmap_gradient.h's (stretch_of: aux_gradient.hip reduces its own derivatives with the same).
 template <typename T>
 __device__ __forceinline__ void strain_store(const StrainArgs<T> &A, size_t o, double a_, double b_, double c_, double d_,
                                              double e_, double f_) {
-#pragma clang fp contract(off)
-    const auto [p, q, r, lam] = gram_eigen(LC_LAYOUT_PHYSICAL, a_, b_, c_, d_, e_, f_);
-    const double s1 = sqrt(lam);
-    A.s1[o] = (T)s1;  // NaN in -> NaN out (Q14)
-    if (A.s2) {
-        // |col1 x col2| = s1 s2 = sqrt(det F^T F) without the cancellation of (p + q) - disc
-        const double cx = c_ * f_ - e_ * d_, cy = e_ * b_ - a_ * f_, cz = a_ * d_ - c_ * b_;
-        const double area = sqrt(cx * cx + cy * cy + cz * cz);
-        A.s2[o] = (T)(s1 == 0.0 ? 0.0 : area / s1);
-    }
-    if (A.e_lon || A.e_lat) {
-        // (F^T F - lam I) e = 0: the row that does not cancel
-        double vx = p >= q ? lam - q : r;
-        double vy = p >= q ? r : lam - p;
-        const double n = sqrt(vx * vx + vy * vy);
-        if (n == 0.0) {  // isotropic cell (disc == 0)
-            vx = 1.0;
-            vy = 0.0;
-        } else {  // (NaN stays NaN: no comparison below holds for it)
-            vx = vx / n;
-            vy = vy / n;
-            if (vx < 0.0 || (vx == 0.0 && vy < 0.0)) {
-                vx = -vx;
-                vy = -vy;
-            }
-        }
-        if (A.e_lon) A.e_lon[o] = (T)vx;
-        if (A.e_lat) A.e_lat[o] = (T)vy;
-    }
+    const Stretch s = stretch_of(a_, b_, c_, d_, e_, f_, A.s2 != nullptr, A.e_lon || A.e_lat);  // flowmap_gradient.h
+    A.s1[o] = (T)s.s1;  // NaN in -> NaN out (Q14)
+    if (A.s2) A.s2[o] = (T)s.s2;
+    if (A.e_lon) A.e_lon[o] = (T)s.ex;
+    if (A.e_lat) A.e_lat[o] = (T)s.ey;
 }
 
 // T: arithmetic type of positions; S: type X,Y,Z are differenced in

@@ -34,7 +34,7 @@ from typing import NamedTuple
 
 import numpy as np
 
-from .engine import Engine, common_dtype
+from .engine import Engine, _smoothing_width, common_dtype
 
 __all__ = ["LCS", "parcel_propagation", "flowmap_gradient", "get_engine"]
 
@@ -218,6 +218,11 @@ def _crop_strict(lat, lon, sub):
     return mlat, mlon
 
 
+# Engine.lcs_aux's form of each windowed engine method (LCS._run_windows with aux_grid)
+_AUX_FORMS = {"lcs_series": dict(n_dirs=1, want=("sigma",)), "lcs_bidirectional": dict(n_dirs=2, want=("sigma",)),
+              "lcs_strain": dict(n_dirs=1, want=("s1", "s2", "e_lon", "e_lat"))}
+
+
 class _Record(NamedTuple):
     """One record as :meth:`LCS._record_intake` hands it to the engine calls and to the labelling of their results."""
     like: object            # the caller's u (resampled): results come back in its class
@@ -242,13 +247,27 @@ class LCS:
     earth_r = 6371000  # metres
 
     def __init__(self, timestep: float = 1, timedim='time', SETTLS_order=0, subdomain=None, return_dpts=False,
-                 gauss_sigma=None):
+                 gauss_sigma=None, aux_grid=None):
+        """The reference's arguments (LCS/LCS.py:25-27), then ``aux_grid`` (pass it by keyword): ``None`` is the reference's
+        gradient, the 5-point stencil over neighbouring output points; a positive number of degrees takes the flow-map
+        gradient of every call form from an auxiliary grid instead -- four extra parcels per output point, offset by that much
+        east, west, north and south (``Engine.lcs_aux``; INTEGRATION.md "Auxiliary-grid FTLE").  Same labelled results; cells
+        within ``aux_grid`` of the field's edge are NaN.  Not together with ``gauss_sigma``."""
+        if aux_grid is not None:
+            if isinstance(aux_grid, bool) or not isinstance(aux_grid, (int, float, np.integer, np.floating)) \
+                    or not np.isfinite(aux_grid) or aux_grid <= 0:
+                raise ValueError(f"aux_grid {aux_grid!r}: a positive, finite offset in degrees (or None)")
+            if _smoothing_width(gauss_sigma) > 1e-15:
+                raise ValueError("aux_grid and gauss_sigma: smoothing departure fields across seeds contradicts the auxiliary "
+                                 "grid's local gradient; use one or the other")
+            aux_grid = float(aux_grid)
         self.timestep = timestep
         self.SETTLS_order = SETTLS_order
         self.timedim = timedim
         self.subdomain = subdomain
         self.gauss_sigma = gauss_sigma
         self.return_dpts = return_dpts
+        self.aux_grid = aux_grid
 
     def __call__(self, ds=None, u=None, v=None, verbose=True, s=None, resample=None, s_is_error=False,
                  isglobal=False, return_traj=False, interp_to_common_grid=True, traj_interp_order=3, truncation=20):
@@ -261,10 +280,13 @@ class LCS:
         verboseprint("*---- Parcel propagation ----*")
         dtype = common_dtype(rec.uu, rec.vv, lat, lon)
         lat_t, lon_t = lat.astype(dtype), lon.astype(dtype)
-        res = eng.lcs_wind(rec.uu, rec.vv, lat, lon, lat_t, lon_t, rec.timestep, SETTLS_order=self.SETTLS_order,
-                           interp_order=traj_interp_order, cyclic_xboundary=rec.cyclic_xboundary,
-                           fuse_levels=eng.f64_fuse_levels(dtype, lat.size * lon.size),
-                           gauss_sigma=self.gauss_sigma, return_traj=return_traj)          # LCS.py:129-154
+        if self.aux_grid is not None:
+            res = self._call_aux(eng, rec, lat_t, lon_t, dtype, traj_interp_order, return_traj)
+        else:
+            res = eng.lcs_wind(rec.uu, rec.vv, lat, lon, lat_t, lon_t, rec.timestep, SETTLS_order=self.SETTLS_order,
+                               interp_order=traj_interp_order, cyclic_xboundary=rec.cyclic_xboundary,
+                               fuse_levels=eng.f64_fuse_levels(dtype, lat.size * lon.size),
+                               gauss_sigma=self.gauss_sigma, return_traj=return_traj)          # LCS.py:129-154
         verboseprint("*---- Done eigenvalues ----*")
 
         forward = np.sign(rec.timestep) == 1
@@ -345,7 +367,8 @@ class LCS:
         res = self._run_windows("lcs_bidirectional", rec, abs(rec.timestep), traj_interp_order)
         verboseprint("*---- Done eigenvalues ----*")
 
-        sig_all, x_all, y_all = (_to_np(res[k]) for k in ("sigma", "x_dep", "y_dep"))
+        sig_all = _to_np(res["sigma"])
+        x_all, y_all = (_to_np(res[k]) for k in ("x_dep", "y_dep")) if self.return_dpts else (None, None)
         out = []
         for d, forward in ((0, False), (1, True)):
             eigenvalues = self._windows_out(rec, forward, sig_all[d], getattr(rec.like, "name", None))
@@ -429,9 +452,36 @@ class LCS:
         lat_t, lon_t = lat.astype(dtype), lon.astype(dtype)
         fuse, ext_image = eng._pack_options(dtype, self.SETTLS_order, eng.f64_fuse_levels(dtype, lat.size * lon.size), None)
         field = eng.prepare_field(rec.uu, rec.vv, lat, lon, traj_interp_order, fuse_levels=fuse, ext_image=ext_image)
-        return getattr(eng, method)(field, lat_t, lon_t, timestep, rec.wlen - 1, rec.n_windows, 0, rec.wstep,
-                                    SETTLS_order=self.SETTLS_order, interp_order=traj_interp_order,
-                                    cyclic_xboundary=rec.cyclic_xboundary, gauss_sigma=self.gauss_sigma)
+        kw = dict(SETTLS_order=self.SETTLS_order, interp_order=traj_interp_order, cyclic_xboundary=rec.cyclic_xboundary,
+                  gauss_sigma=self.gauss_sigma)
+        if self.aux_grid is not None:
+            # the same windows with the gradient of the auxiliary grid; the centre grid is advected only where it is returned
+            return eng.lcs_aux(field, lat_t, lon_t, timestep, rec.wlen - 1, rec.n_windows, 0, rec.wstep, **kw, **_AUX_FORMS[method],
+                               aux_delta=self.aux_grid, centre=bool(self.return_dpts))
+        return getattr(eng, method)(field, lat_t, lon_t, timestep, rec.wlen - 1, rec.n_windows, 0, rec.wstep, **kw)
+
+    def _call_aux(self, eng, rec: _Record, lat_t, lon_t, dtype, traj_interp_order, return_traj):
+        """``__call__``'s engine work with ``aux_grid``: the departure points and trajectories of the output grid, where they are
+        returned, by the call the reference's form makes (``Engine.pack_and_advect``: the same bits), and sigma from the
+        auxiliary grid on the same packed field (``Engine.lcs_aux``)."""
+        lat, lon = rec.lat, rec.lon
+        fuse = eng.f64_fuse_levels(dtype, lat.size * lon.size)
+        res = {}
+        if self.return_dpts or return_traj:
+            out = eng.pack_and_advect(rec.uu, rec.vv, lat, lon, lat_t, lon_t, rec.timestep, self.SETTLS_order, traj_interp_order,
+                                      rec.cyclic_xboundary, fuse, None, None, return_traj, None)
+            field = out[0]
+            res["x_dep"], res["y_dep"] = out[1], out[2]
+            if return_traj:
+                res["traj_x"], res["traj_y"] = out[3], out[4]
+        else:
+            fuse, ext_image = eng._pack_options(dtype, self.SETTLS_order, fuse, None)
+            field = eng.prepare_field(rec.uu, rec.vv, lat, lon, traj_interp_order, fuse_levels=fuse, ext_image=ext_image)
+        aux = eng.lcs_aux(field, lat_t, lon_t, rec.timestep, field.nt - 1, 1, 0, 1, SETTLS_order=self.SETTLS_order,
+                          interp_order=traj_interp_order, cyclic_xboundary=rec.cyclic_xboundary, gauss_sigma=self.gauss_sigma,
+                          aux_delta=self.aux_grid)
+        res["sigma"] = aux["sigma"][0]
+        return res
 
     def _windows_out(self, rec: _Record, forward, a, name=None, crop=True, lead=None):
         """One result of an engine call, ``a`` with trailing axes (window, latitude, longitude), as a labelled array: the strict

@@ -21,10 +21,14 @@ import numpy as np
 
 from . import _capi
 
-__all__ = ["Engine", "PackedField", "PackedTracer", "lcs_host", "lcs_global_host", "common_dtype", "x_boundary_mode"]
+__all__ = ["Engine", "PackedField", "PackedTracer", "AuxSeeds", "lcs_host", "lcs_global_host", "common_dtype", "x_boundary_mode"]
 
 _NP2LC = {np.dtype(np.float32): _capi.LC_F32, np.dtype(np.float64): _capi.LC_F64}
 _LAYOUTS = {"reference": _capi.LC_LAYOUT_REFERENCE, "physical": _capi.LC_LAYOUT_PHYSICAL}
+
+# Engine.aux_seeds: the shifted seed coordinates of an auxiliary grid (north / south latitudes, east / west longitudes, clipped
+# into the field's box), their separations lat_n - lat_s and lon_e - lon_w (NaN on invalid rows / columns) and the validity masks
+AuxSeeds = namedtuple("AuxSeeds", "lat_n lat_s lon_e lon_w sep_lat sep_lon row_valid col_valid")
 
 
 def x_boundary_mode(cyclic_xboundary, noncyclic_clamp=None, whole_grid=True) -> int:
@@ -2524,6 +2528,190 @@ class Engine:
                                     seed_lon, timestep, nsteps, n_windows, t0, t0_stride, SETTLS_order, interp_order, cyclic_xboundary,
                                     gauss_sigma, fd_fp32_cast, noncyclic_clamp, extra_planes=len(self._STRAIN_PLANES) - 1)
         return {**dict(zip(self._STRAIN_PLANES, outs)), "x_dep": x, "y_dep": y}
+
+    # ------------------------------------------------------------------ auxiliary-grid gradient
+    _AUX_OUTPUTS = ("sigma", "s1", "s2", "e_lon", "e_lat")
+    _AUX_PLANES = ("x_e", "y_e", "x_w", "y_w", "x_n", "y_n", "x_s", "y_s")     # lc_aux_gradient_args' order
+
+    @staticmethod
+    def aux_seeds(seed_lat, seed_lon, delta, field_box, dtype) -> "AuxSeeds":
+        """The four shifted seed coordinate arrays of an auxiliary grid and what the gradient divides by (:class:`AuxSeeds`).
+
+        ``delta``: the offset in degrees, a positive float or ``(dlat, dlon)``.  ``field_box``: ``(lat_min, lat_max, lon_min,
+        lon_max)`` of the wind field.  Everything is evaluated in ``dtype``, as the advect kernels will read it: ``lat + d``
+        is rounded, so the separations ``lat_n - lat_s`` and ``lon_e - lon_w`` are taken from the rounded arrays (in float32
+        the nominal ``2 d`` is wrong by up to 8e-4 relative at ``d = 0.01``).  A row is valid iff ``lat - d >= lat_min`` and
+        ``lat + d <= lat_max``, a column iff ``lon -+ d`` lies inside ``[lon_min, lon_max]`` -- for a cyclic field too: the
+        seam columns of a global field are invalid.  Shifted coordinates are clipped into the box, so no seed starts outside
+        the field; invalid rows and columns get a NaN separation, which is how ``lc_aux_gradient`` learns of them."""
+        dtype = np.dtype(dtype)
+        if dtype not in _NP2LC:
+            raise ValueError(f"aux_seeds: dtype {dtype} (float32 or float64)")
+        try:
+            dlat, dlon = (float(d) for d in (delta if np.ndim(delta) else (delta, delta)))
+        except (TypeError, ValueError):
+            raise ValueError(f"aux_seeds: delta {delta!r}: a positive number of degrees, or (dlat, dlon)") from None
+        if not (np.isfinite(dlat) and np.isfinite(dlon) and dlat > 0 and dlon > 0):
+            raise ValueError(f"aux_seeds: delta {delta!r}: a positive number of degrees, or (dlat, dlon)")
+        lat_min, lat_max, lon_min, lon_max = (dtype.type(b) for b in field_box)
+        if not (lat_min <= lat_max and lon_min <= lon_max):
+            raise ValueError(f"aux_seeds: field_box {tuple(field_box)!r}: (lat_min, lat_max, lon_min, lon_max)")
+        lat, lon = np.asarray(seed_lat, dtype=dtype), np.asarray(seed_lon, dtype=dtype)
+        if lat.ndim != 1 or lon.ndim != 1 or not lat.size or not lon.size:
+            raise ValueError("aux_seeds: seed_lat and seed_lon must be non-empty 1-D arrays")
+
+        def shifted(c, d, lo, hi):
+            plus, minus = c + dtype.type(d), c - dtype.type(d)                 # rounded in the dtype
+            with np.errstate(invalid="ignore"):
+                valid = (minus >= lo) & (plus <= hi)                           # (a NaN coordinate is invalid)
+            plus, minus = np.clip(plus, lo, hi), np.clip(minus, lo, hi)
+            sep = np.where(valid, plus - minus, dtype.type("nan")).astype(dtype)
+            return plus, minus, sep, valid
+        lat_n, lat_s, sep_lat, row_valid = shifted(lat, dlat, lat_min, lat_max)
+        lon_e, lon_w, sep_lon, col_valid = shifted(lon, dlon, lon_min, lon_max)
+        return AuxSeeds(lat_n, lat_s, lon_e, lon_w, sep_lat, sep_lon, row_valid, col_valid)
+
+    def last_aux_kernel(self) -> str:
+        """Name of the kernel the last :meth:`aux_gradient` call launched (``lc_ctx_last_aux_kernel``)."""
+        return self.lib.lc_ctx_last_aux_kernel(self.ctx).decode()
+
+    def _aux_call(self, planes, dtype, ny, nx, n, slat, sep_lat, sep_lon, tensor_layout, outs):
+        """One ``lc_aux_gradient`` call: ``planes`` the eight device tensors in ``_AUX_PLANES``' order, ``outs`` name -> tensor."""
+        a = _capi.AuxGradientArgs(struct_size=C.sizeof(_capi.AuxGradientArgs), dtype=_NP2LC[np.dtype(dtype)], ny=int(ny), nx=int(nx),
+                                  n_members=int(n), seed_lat_dev=slat.data_ptr(), sep_lat_dev=sep_lat.data_ptr(),
+                                  sep_lon_dev=sep_lon.data_ptr(), tensor_layout=_LAYOUTS[tensor_layout],
+                                  **{k: t.data_ptr() for k, t in zip(self._AUX_PLANES, planes)},
+                                  **{k + "_out": t.data_ptr() for k, t in outs.items()})
+        self._use_current_stream()
+        _capi.check(self.lib.lc_aux_gradient(self.ctx, C.byref(a)), self.lib)
+
+    def _aux_want(self, want):
+        want = tuple(want)
+        if not want or any(w not in self._AUX_OUTPUTS for w in want):
+            raise ValueError(f"want {want!r}: a non-empty subset of {self._AUX_OUTPUTS}")
+        return want
+
+    def aux_gradient(self, planes, seed_lat, sep_lat, sep_lon, want=("sigma", "s1", "s2", "e_lon", "e_lat"),
+                     tensor_layout="reference") -> dict:
+        """sigma, both stretch factors and the stretching direction from the departure points of an auxiliary grid, in one
+        launch (``lc_aux_gradient``).  ``planes``: the eight planes ``x_e, y_e, x_w, y_w, x_n, y_n, x_s, y_s`` (a mapping by
+        these names, or a sequence in this order), each ``(ny, nx)`` or ``(n, ny, nx)``: the departure points of the parcels
+        seeded east, west, north and south of every output point.  ``seed_lat``: the output rows' latitudes; ``sep_lat``
+        ``(ny,)`` and ``sep_lon`` ``(nx,)``: the separations of the shifted seed coordinates (:meth:`aux_seeds`; NaN marks a row
+        or column as invalid).  Returns each name in ``want`` as a device tensor of the input's shape and dtype: ``s1``,
+        ``s2``, ``e_lon``, ``e_lat`` as :meth:`strain` defines them, ``sigma`` in ``tensor_layout`` (``"physical"``: equal to
+        ``s1``).  A NaN input gives NaN in that cell's outputs only."""
+        torch = self.torch
+        want = self._aux_want(want)
+        if tensor_layout not in _LAYOUTS:
+            raise ValueError(f"tensor_layout {tensor_layout!r}")
+        seq = [planes[k] for k in self._AUX_PLANES] if hasattr(planes, "keys") else list(planes)
+        if len(seq) != 8:
+            raise ValueError(f"planes: the eight planes {self._AUX_PLANES}")
+        dtype = (np.dtype(str(seq[0].dtype).replace("torch.", "")) if all(isinstance(p, torch.Tensor) for p in seq)
+                 else common_dtype(*seq))
+        dev = [self.to_device(p, dtype) for p in seq]
+        shape = tuple(int(s) for s in dev[0].shape)
+        if len(shape) not in (2, 3) or any(tuple(p.shape) != shape for p in dev):
+            raise ValueError("planes must all be (ny, nx) or all (n, ny, nx)")
+        ny, nx = shape[-2:]
+        n = shape[0] if len(shape) == 3 else 1
+        slat, dla, dlo = self.to_device(seed_lat, dtype), self.to_device(sep_lat, dtype), self.to_device(sep_lon, dtype)
+        if slat.numel() != ny or dla.numel() != ny or dlo.numel() != nx:
+            raise ValueError("seed_lat and sep_lat must have one entry per row, sep_lon one per column")
+        out = {k: self._empty(shape, dtype) for k in self._AUX_OUTPUTS if k in want}
+        self._aux_call(dev, dtype, ny, nx, n, slat, dla, dlo, tensor_layout, out)
+        return {k: out[k] for k in want}
+
+    def aux_group(self, dtype, n_seeds: int, n_windows: int, cyclic_xboundary=True, n_outputs: int = 1, centre=False) -> int:
+        """Windows per group of :meth:`lcs_aux`: as many as fit ``SERIES_MEM_CAP`` (at least one).  Per window: the eight
+        position planes, the ``n_outputs`` result planes, the centre grid's two, and -- under the reference's non-cyclic clamp --
+        the four scratch planes of the advect call that is running (:meth:`series_group`).  ``n_seeds`` counts both directions."""
+        planes = 8 + int(n_outputs) + (2 if centre else 0) + (0 if cyclic_xboundary else 4)
+        per = planes * int(n_seeds) * np.dtype(dtype).itemsize
+        return max(1, min(int(n_windows), int(self.SERIES_MEM_CAP) // max(per, 1)))
+
+    def lcs_aux(self, field: PackedField, seed_lat, seed_lon, timestep, nsteps: int, n_windows: int = 1, t0=0, t0_stride=1,
+                SETTLS_order=0, interp_order=1, cyclic_xboundary=True, gauss_sigma=None, tensor_layout="reference",
+                noncyclic_clamp=None, *, aux_delta, n_dirs=1, want=("sigma",), centre=False, return_planes=False) -> dict:
+        """FTLE from an auxiliary grid (Haller): four parcels per output point, seeded ``aux_delta`` degrees east, west, north
+        and south of it, are advected through the windows of :meth:`lcs_series` (same arguments: window ``m`` runs ``nsteps``
+        steps from level ``t0 + m * t0_stride``), and the flow-map gradient at the point is the centred difference of their
+        departure points (:meth:`aux_gradient`).  The gradient is local: its accuracy is set by ``aux_delta``, not by the output
+        spacing; there is no neighbour stencil, so no cyclic seam, no one-sided rows and no NaN halo.
+
+        Per memory group (:meth:`aux_group`; results do not depend on the grouping) four ``lc_advect_series`` calls -- for
+        ``n_dirs = 2`` four ``lc_advect_series_dirs`` calls, ``timestep``'s sign then ignored as in :meth:`lcs_bidirectional`
+        --, one per shifted grid (:meth:`aux_seeds` on the field's box: shifted seeds are clipped into it), each exactly what
+        :meth:`advect` returns for that seed grid, then one ``lc_aux_gradient`` call.  ``centre=True``: a fifth advect call on
+        the unshifted grid, returned as ``x_dep`` / ``y_dep`` (:meth:`lcs_series`' bits).
+
+        Returns the names in ``want`` (``sigma`` in ``tensor_layout``, ``s1``, ``s2``, ``e_lon``, ``e_lat``) as ``(n_windows, ny,
+        nx)`` device tensors, ``(2, n_windows, ny, nx)`` for ``n_dirs = 2`` (backward first); ``"seeds"``: the :class:`AuxSeeds`
+        (rows and columns it marks invalid -- within ``aux_delta`` of the field's edge, the seam columns of a global field
+        included -- are NaN); with ``return_planes`` the eight position planes by name.  ``gauss_sigma`` is refused: smoothing
+        departure fields across seeds contradicts a local gradient."""
+        if _smoothing_width(gauss_sigma) > 1e-15:
+            raise ValueError("lcs_aux: gauss_sigma smooths the departure fields across seeds, which contradicts the auxiliary grid's "
+                             "local gradient; use one or the other")
+        _check_order(field, interp_order)
+        want = self._aux_want(want)
+        if tensor_layout not in _LAYOUTS:
+            raise ValueError(f"tensor_layout {tensor_layout!r}")
+        if n_dirs not in (1, 2):
+            raise ValueError(f"lcs_aux: n_dirs {n_dirs!r} (1 or 2)")
+        if n_dirs == 2:
+            timestep = float(timestep)
+            if not timestep or not np.isfinite(timestep):
+                raise ValueError(f"lcs_aux: timestep {timestep} (non-zero: its sign is taken from the direction)")
+            timestep = -abs(timestep)
+        n_windows, nsteps, t0, t0_stride = int(n_windows), int(nsteps), int(t0), int(t0_stride)
+        if n_windows < 1 or nsteps < 0 or t0 < 0 or t0_stride < 0:
+            raise ValueError(f"lcs_aux: n_windows {n_windows}, nsteps {nsteps}, t0 {t0}, t0_stride {t0_stride}")
+        dtype = field.dtype
+        seed_lat, seed_lon = np.asarray(seed_lat, dtype=dtype), np.asarray(seed_lon, dtype=dtype)
+        seeds = self.aux_seeds(seed_lat, seed_lon, aux_delta, (field.lat_min, field.lat_max, field.lon_min, field.lon_max), dtype)
+        dev = lambda a: self.to_device(a, dtype)
+        slat, slon = dev(seed_lat), dev(seed_lon)
+        ny, nx = int(slat.numel()), int(slon.numel())
+        # the seed grids in _AUX_PLANES' order: east, west, north, south
+        grids = ((slat, dev(seeds.lon_e)), (slat, dev(seeds.lon_w)), (dev(seeds.lat_n), slon), (dev(seeds.lat_s), slon))
+        sep_lat, sep_lon = dev(seeds.sep_lat), dev(seeds.sep_lon)
+        xmode = x_boundary_mode(cyclic_xboundary, noncyclic_clamp, True)
+        tail = (ny, nx) if n_dirs == 1 else (n_dirs, ny, nx)      # the library's plane order: window-major, plane 2w + d
+        g = self.aux_group(dtype, n_dirs * ny * nx, n_windows, cyclic_xboundary, len(want), centre)
+        outs = {k: self._empty((n_windows, *tail), dtype) for k in self._AUX_OUTPUTS if k in want}
+        # the position planes: of every window if they are returned, else of one group (reused by the next)
+        pos = [self._empty((n_windows if return_planes else g, *tail), dtype) for _ in self._AUX_PLANES]
+        x = y = None
+        if centre:
+            x, y = self._empty((n_windows, *tail), dtype), self._empty((n_windows, *tail), dtype)
+
+        def advect(la, lo, m0, n, xg, yg):
+            self._use_current_stream()
+            a = self._advect_args(field, interp_order, la, ny, lo, nx, timestep, SETTLS_order, xmode,
+                                  t0=t0 + m0 * t0_stride, nsteps=nsteps, n_members=n, t0_stride=t0_stride, out=(xg, yg))
+            _capi.check(self.lib.lc_advect_series(self.ctx, C.byref(a)) if n_dirs == 1 else
+                        self.lib.lc_advect_series_dirs(self.ctx, C.byref(a), n_dirs), self.lib)
+        for m0 in range(0, n_windows, g):
+            n = min(g, n_windows - m0)
+            p0 = m0 if return_planes else 0
+            group = [p[p0:p0 + n] for p in pos]
+            for i, (la, lo) in enumerate(grids):
+                advect(la, lo, m0, n, group[2 * i], group[2 * i + 1])
+            if centre:
+                advect(slat, slon, m0, n, x[m0:m0 + n], y[m0:m0 + n])
+            self._aux_call(group, dtype, ny, nx, n_dirs * n, slat, sep_lat, sep_lon, tensor_layout,
+                           {k: t[m0:m0 + n] for k, t in outs.items()})
+        # two directions: (n_windows, 2, ...) -> (2, n_windows, ...), as lcs_bidirectional
+        shape_out = (lambda t: t) if n_dirs == 1 else (lambda t: t.transpose(0, 1).contiguous())
+        res = {k: shape_out(outs[k]) for k in want}
+        res["seeds"] = seeds
+        if centre:
+            res["x_dep"], res["y_dep"] = shape_out(x), shape_out(y)
+        if return_planes:
+            res.update({k: shape_out(p) for k, p in zip(self._AUX_PLANES, pos)})
+        return res
 
     def synchronize(self):
         self.torch.cuda.synchronize(self.device)
