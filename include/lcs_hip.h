@@ -38,7 +38,7 @@ extern "C" {
  * client built against 100 must be rebuilt), lc_ctx_get_level_chunk, lc_ctx_set/get_f64_fidelity, lc_advect_ex and
  * lc_sample_raw added, lc_field_pack accepts packed_dev == NULL at order 1 (fused-level image only).  lc_version() returns the value the LIBRARY
  * was built with: compare it with this macro before any other call (tests/c/abi_smoke.c, _capi.load do). */
-#define LC_VERSION 104 /* 0.1.4: + lc_aux_gradient, lc_ctx_last_aux_kernel (added without a bump), + lc_mask_morphology, lc_morph_work_elems (added without a bump), + lc_label_components, lc_label_work_elems, lc_component_sums, lc_component_apply, + lc_strain, lc_ctx_last_strain_kernel, + lc_advect_series_dirs, + lc_advect_series, lc_sigma_batch, + lc_tracer_sample, lc_ctx_last_tracer_kernel (additive: no argument list changed), + lc_ctx_set_host_pipeline, lc_copy_to_device, lc_copy_to_host, lc_ctx_set_host_cache, lc_ctx_trim, lc_ctx_last_host_marks, lc_ctx_set_xcd_split (0.1.3: + lc_ctx_last_pack_kernel; 0.1.2: + lc_ctx_set_verify, lc_ctx_read_verify, LC_F64_WIND_F32_LIN32) */
+#define LC_VERSION 104 /* 0.1.4: + lc_fsle_update, lc_ctx_last_fsle_kernel (added without a bump), + lc_aux_gradient, lc_ctx_last_aux_kernel (added without a bump), + lc_mask_morphology, lc_morph_work_elems (added without a bump), + lc_label_components, lc_label_work_elems, lc_component_sums, lc_component_apply, + lc_strain, lc_ctx_last_strain_kernel, + lc_advect_series_dirs, + lc_advect_series, lc_sigma_batch, + lc_tracer_sample, lc_ctx_last_tracer_kernel (additive: no argument list changed), + lc_ctx_set_host_pipeline, lc_copy_to_device, lc_copy_to_host, lc_ctx_set_host_cache, lc_ctx_trim, lc_ctx_last_host_marks, lc_ctx_set_xcd_split (0.1.3: + lc_ctx_last_pack_kernel; 0.1.2: + lc_ctx_set_verify, lc_ctx_read_verify, LC_F64_WIND_F32_LIN32) */
 
 typedef struct lc_ctx lc_ctx;
 
@@ -636,6 +636,56 @@ typedef struct lc_aux_gradient_args {
 } lc_aux_gradient_args;
 int lc_aux_gradient(lc_ctx *ctx, const lc_aux_gradient_args *args);
 const char *lc_ctx_last_aux_kernel(const lc_ctx *ctx);
+
+/* ---- finite-size Lyapunov exponents (LCS.fsle, Engine.fsle) ----
+ * No counterpart in the reference.  A record of trajectory planes (lc_advect_ex's traj_x / traj_y) is reduced, block of levels by
+ * block of levels, to the time tau that the neighbour pairs of every cell take to separate to a threshold, and to the exponent.
+ * Positions are degrees, k = pi / 180, the grid has ny x nx seeds.
+ *   pairs       every horizontally or vertically adjacent couple of seeds; with cyclic_x column nx-1 pairs with column 0.  A cell
+ *               owns up to four pairs, in the order E, W, N, S; the E pair of (r, c) is the W pair of (r, c+1): same parcels,
+ *               same numbers
+ *   separation  of pair p at level j, the great-circle distance on a sphere of `radius` in half-angle form:
+ *               h = sin^2(k dphi / 2) + cos(k phi1) cos(k phi2) sin^2(k dlambda / 2),  d = 2 radius asin(min(1, sqrt h));
+ *               dlambda is the raw difference (the form is periodic: the seam needs no wrap).  d_p(0) is formed from seed_lat /
+ *               seed_lon, which is trajectory entry 0 (entry 0 of the block with level0 == 0 is not read)
+ *   threshold   q of pair p: mode LC_FSLE_RATIO T = thresholds[q] d_p(0); LC_FSLE_DISTANCE T = thresholds[q] metres.  A pair
+ *               is eligible for q when d_p(0) is finite, > 0 and < T
+ *   crossing    an eligible pair upcrosses at the first level j >= 1 where both separations are finite and d_p(j-1) < T <=
+ *               d_p(j); its time is t_p = (j-1 + (T - d_p(j-1)) / (d_p(j) - d_p(j-1))) |timestep|.  A level where either
+ *               separation is not finite contributes nothing
+ *   cell        tau[q][r][c] = the minimum of t_p over the cell's pairs, ties to the first pair in E, W, N, S order;
+ *               fsle[q][r][c] = ln(T / d_p*(0)) / tau for the pair p* that gave it (ratio mode: ln(thresholds[q]) / tau); both
+ *               NaN where no pair of the cell ever upcrosses.  tau is a positive duration whatever the sign of timestep: as
+ *               with FTLE, a backward record gives the attracting field
+ *   streaming   tau and fsle are the only state carried from one block of levels to the next: the test needs levels j-1 and j
+ *               only, entry 0 of a continued block is the last entry of the block before, and a cell whose tau[q] is finite is
+ *               final for q.  Any split of the levels into blocks gives, bit for bit, what one block gives.  (A block walks its
+ *               levels in order and closes a cell at the first level where a pair of it upcrosses.  Where rounding makes a
+ *               later level's time equal to an earlier level's, the earlier level's pair keeps the cell.)
+ *   traj_x, traj_y   [n_levels][ny*nx] dtype elements: positions after level0, level0 + 1, ... steps
+ *   level0      steps already consumed by earlier blocks; 0: the call writes NaN into tau and fsle itself before it starts
+ *   tau, fsle   [n_thr][ny*nx], in and out
+ *   thresholds  n_thr of them, passed by value and rounded to the dtype; the checks below apply to the rounded values
+ * dtype LC_F32 or LC_F64.  Refused with LC_EINVAL before any HIP call: a null context or argument structure, a wrong
+ * struct_size, a bad dtype or mode, ny or nx < 1 or ny * nx == 1, n_levels < 2, level0 < 0, n_thr outside 1..8, a threshold
+ * that is not finite or is <= 1 in ratio mode or <= 0 in distance mode, a radius or |timestep| that is not positive and finite,
+ * a plane of 2^31 cells or more (or a grid that needs more workgroups than one launch takes), a null pointer.
+ * lc_ctx_last_fsle_kernel: what the context's last lc_fsle_update launched ("" before any, or for a null context):
+ * "fsle_update_kernel<float, 8>" or "fsle_update_kernel<double, 8>". */
+enum lc_fsle_mode { LC_FSLE_RATIO = 0, LC_FSLE_DISTANCE = 1 };
+typedef struct lc_fsle_args {
+    size_t struct_size; /* sizeof(lc_fsle_args): checked before any other field */
+    const void *traj_x, *traj_y;
+    int dtype, ny, nx, n_levels, level0;
+    const void *seed_lat_dev, *seed_lon_dev;
+    int mode, n_thr; /* enum lc_fsle_mode */
+    double thresholds[8];
+    double radius, timestep;
+    int cyclic_x; /* non-zero: column nx-1 pairs with column 0 */
+    void *tau, *fsle;
+} lc_fsle_args;
+int lc_fsle_update(lc_ctx *ctx, const lc_fsle_args *args);
+const char *lc_ctx_last_fsle_kernel(const lc_ctx *ctx);
 
 /* The 9-component "def_tensor" itself, for callers of LCS.flowmap_gradient
  * (LCS/LCS.py:171-225): planes dXdx,dXdy,dYdx,dYdy,dZdx,dZdy,dXdr,dYdr,dZdr (the last

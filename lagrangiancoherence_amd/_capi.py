@@ -355,6 +355,24 @@ class AuxGradientArgs(C.Structure):
 PROTOTYPES["lc_aux_gradient"] = (_i, [_vp, C.POINTER(AuxGradientArgs)])
 PROTOTYPES["lc_ctx_last_aux_kernel"] = (C.c_char_p, [_vp])
 
+
+class FsleArgs(C.Structure):
+    """``lc_fsle_args`` of include/lcs_hip.h, field for field."""
+    _fields_ = [("struct_size", _sz),
+                ("traj_x", _vp), ("traj_y", _vp),
+                ("dtype", _i), ("ny", _i), ("nx", _i), ("n_levels", _i), ("level0", _i),
+                ("seed_lat_dev", _vp), ("seed_lon_dev", _vp),
+                ("mode", _i), ("n_thr", _i),
+                ("thresholds", C.c_double * 8),
+                ("radius", C.c_double), ("timestep", C.c_double),
+                ("cyclic_x", _i),
+                ("tau", _vp), ("fsle", _vp)]
+
+
+LC_FSLE_RATIO, LC_FSLE_DISTANCE = 0, 1
+PROTOTYPES["lc_fsle_update"] = (_i, [_vp, C.POINTER(FsleArgs)])
+PROTOTYPES["lc_ctx_last_fsle_kernel"] = (C.c_char_p, [_vp])
+
 _lib = None
 
 

@@ -447,11 +447,7 @@ class LCS:
         """Pack the record once -- the pack of the per-window call (Engine.lcs_wind -> pack_and_advect) -- and run the engine's
         ``method`` (``lcs_series``, ``lcs_bidirectional`` or ``lcs_strain``) over its windows."""
         eng = get_engine()
-        lat, lon = rec.lat, rec.lon
-        dtype = common_dtype(rec.uu, rec.vv, lat, lon)
-        lat_t, lon_t = lat.astype(dtype), lon.astype(dtype)
-        fuse, ext_image = eng._pack_options(dtype, self.SETTLS_order, eng.f64_fuse_levels(dtype, lat.size * lon.size), None)
-        field = eng.prepare_field(rec.uu, rec.vv, lat, lon, traj_interp_order, fuse_levels=fuse, ext_image=ext_image)
+        field, lat_t, lon_t = self._packed_record(eng, rec, traj_interp_order)
         kw = dict(SETTLS_order=self.SETTLS_order, interp_order=traj_interp_order, cyclic_xboundary=rec.cyclic_xboundary,
                   gauss_sigma=self.gauss_sigma)
         if self.aux_grid is not None:
@@ -459,6 +455,15 @@ class LCS:
             return eng.lcs_aux(field, lat_t, lon_t, timestep, rec.wlen - 1, rec.n_windows, 0, rec.wstep, **kw, **_AUX_FORMS[method],
                                aux_delta=self.aux_grid, centre=bool(self.return_dpts))
         return getattr(eng, method)(field, lat_t, lon_t, timestep, rec.wlen - 1, rec.n_windows, 0, rec.wstep, **kw)
+
+    def _packed_record(self, eng, rec: _Record, traj_interp_order):
+        """The record packed once -- the pack of the per-window call (Engine.lcs_wind -> pack_and_advect) -- and the seed
+        coordinates in its dtype: ``(field, lat, lon)``, what every windowed call form advects on."""
+        lat, lon = rec.lat, rec.lon
+        dtype = common_dtype(rec.uu, rec.vv, lat, lon)
+        fuse, ext_image = eng._pack_options(dtype, self.SETTLS_order, eng.f64_fuse_levels(dtype, lat.size * lon.size), None)
+        field = eng.prepare_field(rec.uu, rec.vv, lat, lon, traj_interp_order, fuse_levels=fuse, ext_image=ext_image)
+        return field, lat.astype(dtype), lon.astype(dtype)
 
     def _call_aux(self, eng, rec: _Record, lat_t, lon_t, dtype, traj_interp_order, return_traj):
         """``__call__``'s engine work with ``aux_grid``: the departure points and trajectories of the output grid, where they are
@@ -535,6 +540,52 @@ class LCS:
         if self.return_dpts:                                               # LCS.py:161-168
             out += (self._windows_out(rec, forward, _to_np(res["x_dep"]), crop=False),
                     self._windows_out(rec, forward, _to_np(res["y_dep"]), crop=False))
+        return out
+
+    def fsle(self, ds=None, u=None, v=None, ratio=None, final_separation=None, window=None, stride=1, verbose=True, s=None,
+             resample=None, s_is_error=False, isglobal=False, interp_to_common_grid=True, traj_interp_order=3, truncation=20,
+             level_chunk=16):
+        """Finite-size Lyapunov exponents: ``(fsle, tau)``, both with dims ``("threshold", timedim, latitude, longitude)``.
+
+        ``tau`` is the time (seconds, positive) the first of a cell's neighbour pairs -- east, west, north, south on the
+        output grid; across the ±180 seam with ``isglobal`` -- takes to separate from its initial great-circle distance ``d0``
+        to the threshold ``T``, linearly interpolated between the two time levels that bracket the crossing, and ``fsle =
+        ln(T / d0) / tau`` (1/s); both NaN where no pair reaches ``T`` inside the window.  Exactly one of ``ratio`` (``T =
+        ratio * d0``, each ``> 1``) and ``final_separation`` (``T`` in metres, each ``> 0``) is given, a scalar or a sequence of up
+        to 8 values: the ``threshold`` coordinate.  Unlike FTLE the exponent does not saturate with the window's length and picks
+        out one scale of separation.  The direction of integration is the sign of ``timestep``: a backward run gives the
+        attracting field.  The full definition: INTEGRATION.md "Finite-size Lyapunov exponents".
+
+        ``window`` / ``stride``, the intake (``resample``, sort, regrid / T20: :meth:`_record_intake`), the one pack, the
+        ``subdomain`` crop and the time labels are :meth:`strain`'s; the windows are a plain loop over ``Engine.fsle``, which
+        streams each window's trajectories through ``lc_fsle_update`` in blocks of ``level_chunk`` steps.  With ``return_dpts``
+        ``x_dep`` and ``y_dep`` are appended, dims ``(timedim, latitude, longitude)``.  Not with ``aux_grid`` for now."""
+        if (ratio is None) == (final_separation is None):
+            raise ValueError("fsle: give exactly one of ratio and final_separation")
+        if self.aux_grid is not None:
+            raise ValueError("fsle: the exponent of the auxiliary parcels is not implemented; use an LCS without aux_grid")
+        mode, given = ("ratio", ratio) if ratio is not None else ("distance", final_separation)
+        if not self.timestep:
+            raise ValueError(f"timestep {self.timestep!r}: fsle needs a non-zero step")
+        thr, mode, _, radius = Engine.checked_fsle_options(given, mode, self.timestep, self.earth_r)
+        verboseprint = print if verbose else (lambda *a, **k: None)
+        rec = self._record_intake(ds, u, v, window, stride, resample, isglobal, interp_to_common_grid, truncation, verbose)
+        verboseprint(f"*---- Parcel propagation: {rec.n_windows} window(s) ----*")
+        eng = get_engine()
+        field, lat_t, lon_t = self._packed_record(eng, rec, traj_interp_order)
+        res = [eng.fsle(field, lat_t, lon_t, rec.timestep, thr, mode, t0=w * rec.wstep, nsteps=rec.wlen - 1, level_chunk=level_chunk,
+                        SETTLS_order=self.SETTLS_order, interp_order=traj_interp_order, cyclic_xboundary=rec.cyclic_xboundary,
+                        radius=radius) for w in range(rec.n_windows)]
+        verboseprint("*---- Done finite-size exponents ----*")
+
+        forward = np.sign(rec.timestep) == 1
+        lead = {"threshold": thr}
+        stack = lambda k, axis: np.stack([_to_np(r[k]) for r in res], axis=axis)
+        out = (self._windows_out(rec, forward, stack("fsle", 1), "fsle", lead=lead),
+               self._windows_out(rec, forward, stack("tau", 1), "tau", lead=lead))
+        if self.return_dpts:                                               # LCS.py:161-168
+            out += (self._windows_out(rec, forward, stack("x_dep", 0), crop=False),
+                    self._windows_out(rec, forward, stack("y_dep", 0), crop=False))
         return out
 
 

@@ -2713,6 +2713,129 @@ class Engine:
             res.update({k: shape_out(p) for k, p in zip(self._AUX_PLANES, pos)})
         return res
 
+    # ------------------------------------------------------------------ finite-size Lyapunov exponents
+    _FSLE_MODES = {"ratio": _capi.LC_FSLE_RATIO, "distance": _capi.LC_FSLE_DISTANCE}
+    FSLE_MAX_THRESHOLDS = 8
+
+    def last_fsle_kernel(self) -> str:
+        """Name of the kernel the last :meth:`fsle_update` call launched (``lc_ctx_last_fsle_kernel``)."""
+        return self.lib.lc_ctx_last_fsle_kernel(self.ctx).decode()
+
+    @classmethod
+    def checked_fsle_options(cls, thresholds, mode, timestep, radius=6371000.0, dtype=None):
+        """``(thresholds, mode, timestep, radius)`` as :meth:`fsle_update` hands them to the library, or ``ValueError``: 1 to 8
+        finite thresholds (a scalar is one), each ``> 1`` for ``mode='ratio'`` and ``> 0`` (metres) for ``mode='distance'`` --
+        with ``dtype`` also once rounded to it, as the kernel sees them (a float32 ratio of ``1 + 1e-9`` is 1) --; a non-zero
+        finite ``timestep`` (its sign only names the direction the record was advected in); a positive finite radius."""
+        if mode not in cls._FSLE_MODES:
+            raise ValueError(f"fsle: mode {mode!r} ('ratio' or 'distance')")
+        try:
+            thr = np.atleast_1d(np.asarray(thresholds, dtype=np.float64))
+        except (TypeError, ValueError):
+            raise ValueError(f"fsle: thresholds {thresholds!r}: 1 to {cls.FSLE_MAX_THRESHOLDS} numbers") from None
+        if thr.ndim != 1 or not 1 <= thr.size <= cls.FSLE_MAX_THRESHOLDS:
+            raise ValueError(f"fsle: {thr.size} thresholds (1 to {cls.FSLE_MAX_THRESHOLDS}, one-dimensional)")
+        with np.errstate(over="ignore"):
+            seen = thr if dtype is None else thr.astype(dtype).astype(np.float64)
+        if not np.all(np.isfinite(seen)) or np.any(seen <= (1.0 if mode == "ratio" else 0.0)):
+            raise ValueError(f"fsle: thresholds {thr.tolist()}: finite, and > 1 as ratios / > 0 metres as distances"
+                             + ("" if dtype is None else f" once rounded to {np.dtype(dtype).name}"))
+        try:
+            timestep, radius = float(timestep), float(radius)
+        except (TypeError, ValueError):
+            raise ValueError(f"fsle: timestep {timestep!r}, radius {radius!r}") from None
+        if not np.isfinite(timestep) or timestep == 0:
+            raise ValueError(f"fsle: timestep {timestep} (non-zero and finite)")
+        if not np.isfinite(radius) or radius <= 0:
+            raise ValueError(f"fsle: radius {radius} (positive and finite)")
+        return thr, mode, timestep, radius
+
+    def fsle_update(self, traj_x, traj_y, seed_lat, seed_lon, thresholds, mode, timestep, level0, tau=None, fsle=None, cyclic=False,
+                    radius=6371000.0):
+        """One block of trajectory levels folded into the finite-size Lyapunov exponent (``lc_fsle_update``; the definition is in
+        include/lcs_hip.h and restated in tests/fsle.py).  ``traj_x``, ``traj_y``: ``(n_levels, ny, nx)`` positions in degrees
+        after ``level0``, ``level0 + 1``, ... steps (:meth:`advect` with ``return_traj=True``), ``n_levels >= 2``; entry 0 of a
+        continued block (``level0 > 0``) is the last entry of the block before.  ``thresholds``: 1 to 8 ratios (``mode='ratio'``:
+        a pair crosses when its separation reaches that multiple of its initial one) or final separations in metres
+        (``mode='distance'``).  ``tau``, ``fsle``: the ``(n_thr, ny, nx)`` tensors the previous block returned -- they are updated
+        in place and returned; with ``level0 == 0`` they may be omitted (or are overwritten).  ``cyclic``: column ``nx - 1`` pairs
+        with column 0.  Returns ``(tau, fsle)``: per threshold and cell the time its first neighbour pair takes to separate to
+        the threshold (seconds, positive) and ``ln(T / d0) / tau``, NaN where none does within the levels seen so far."""
+        thr, mode, timestep, radius = self.checked_fsle_options(thresholds, mode, timestep, radius)
+        level0 = int(level0)
+        if level0 < 0:
+            raise ValueError(f"fsle_update: level0 {level0}")
+        if np.ndim(traj_x) != 3 or tuple(np.shape(traj_x)) != tuple(np.shape(traj_y)):
+            raise ValueError("fsle_update: traj_x and traj_y must both be (n_levels, ny, nx)")
+        n_levels, ny, nx = (int(s) for s in np.shape(traj_x))
+        if n_levels < 2 or ny < 1 or nx < 1 or ny * nx == 1:
+            raise ValueError(f"fsle_update: {n_levels} levels of a {ny} x {nx} grid (at least two levels and two seeds)")
+        count = lambda a: int(a.numel()) if hasattr(a, "numel") else int(np.size(a))
+        if count(seed_lat) != ny or count(seed_lon) != nx:
+            raise ValueError("fsle_update: seed_lat must have one entry per row, seed_lon one per column")
+        if (tau is None) != (fsle is None) or (tau is None and level0 != 0):
+            raise ValueError("fsle_update: tau and fsle go together, and a continued block (level0 > 0) needs both")
+        dtype = (np.dtype(str(traj_x.dtype).replace("torch.", "")) if hasattr(traj_x, "data_ptr") and hasattr(traj_y, "data_ptr")
+                 else common_dtype(traj_x, traj_y))
+        if dtype not in _NP2LC:
+            raise ValueError(f"fsle_update: dtype {dtype} (float32 or float64)")
+        self.checked_fsle_options(thr, mode, timestep, radius, dtype)
+        torch = self.torch
+        tx, ty = self.to_device(traj_x, dtype), self.to_device(traj_y, dtype)
+        slat, slon = self.to_device(seed_lat, dtype).reshape(-1), self.to_device(seed_lon, dtype).reshape(-1)
+        if tau is None:
+            tau, fsle = self._empty((thr.size, ny, nx), dtype), self._empty((thr.size, ny, nx), dtype)
+        want = getattr(torch, dtype.name)
+        for t in (tau, fsle):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != (thr.size, ny, nx) or t.dtype != want or not t.is_contiguous() \
+                    or t.device != self.device:
+                raise ValueError(f"fsle_update: tau and fsle must be contiguous ({thr.size}, {ny}, {nx}) {dtype.name} tensors on {self.device}")
+        a = _capi.FsleArgs(struct_size=C.sizeof(_capi.FsleArgs), traj_x=tx.data_ptr(), traj_y=ty.data_ptr(), dtype=_NP2LC[dtype],
+                           ny=ny, nx=nx, n_levels=n_levels, level0=level0, seed_lat_dev=slat.data_ptr(), seed_lon_dev=slon.data_ptr(),
+                           mode=self._FSLE_MODES[mode], n_thr=int(thr.size), thresholds=(C.c_double * 8)(*thr.tolist()),
+                           radius=radius, timestep=timestep, cyclic_x=int(bool(cyclic)), tau=tau.data_ptr(), fsle=fsle.data_ptr())
+        self._use_current_stream()
+        _capi.check(self.lib.lc_fsle_update(self.ctx, C.byref(a)), self.lib)
+        return tau, fsle
+
+    def fsle(self, field: PackedField, seed_lat, seed_lon, timestep, thresholds, mode="ratio", t0=0, nsteps=None, level_chunk=16,
+             SETTLS_order=0, interp_order=1, cyclic_xboundary=True, noncyclic_clamp=None, radius=6371000.0) -> dict:
+        """Finite-size Lyapunov exponents of the seed grid's neighbour pairs over ``nsteps`` steps from level ``t0`` of a packed
+        field: ``{'tau', 'fsle'}`` as ``(n_thr, ny, nx)`` device tensors (:meth:`fsle_update`) and the departure points ``'x_dep'``,
+        ``'y_dep'`` of :meth:`advect`.  The record is streamed: ``advect(start=(x, y), out=(x, y), nsteps=chunk,
+        return_traj=True)`` continues in place (bit for bit what one call gives) and each block of ``level_chunk`` steps is folded
+        into tau / fsle and dropped, so at most ``level_chunk + 1`` trajectory planes per coordinate are alive at a time; the
+        result does not depend on ``level_chunk``.  Pairs close across the ±180 seam with ``cyclic_xboundary``.
+
+        ``cyclic_xboundary=False`` with the default ``reference_outer`` clamp cannot be continued (``lc_advect_from`` refuses it):
+        that case makes ONE advect over all levels and one update, and needs the full record -- ``2 (nsteps + 1)`` planes -- in
+        device memory.  ``noncyclic_clamp='pointwise'`` streams."""
+        thr, mode, timestep, radius = self.checked_fsle_options(thresholds, mode, timestep, radius, field.dtype)
+        _check_order(field, interp_order)
+        t0 = int(t0)
+        nsteps = field.nt - 1 - t0 if nsteps is None else int(nsteps)
+        level_chunk = int(level_chunk)
+        if t0 < 0 or nsteps < 1 or t0 + nsteps > field.nt - 1:
+            raise ValueError(f"fsle: t0 {t0}, nsteps {nsteps} on a record of {field.nt} levels (at least one step, inside the record)")
+        if level_chunk < 1:
+            raise ValueError(f"fsle: level_chunk {level_chunk} (at least 1)")
+        count = lambda a: int(a.numel()) if hasattr(a, "numel") else int(np.size(a))
+        if np.ndim(seed_lat) != 1 or np.ndim(seed_lon) != 1 or count(seed_lat) * count(seed_lon) < 2:
+            raise ValueError("fsle: seed_lat and seed_lon must be 1-D and hold at least two seeds between them")
+        xmode = x_boundary_mode(cyclic_xboundary, noncyclic_clamp, True)
+        kw = dict(SETTLS_order=SETTLS_order, interp_order=interp_order, cyclic_xboundary=cyclic_xboundary, noncyclic_clamp=noncyclic_clamp)
+        if xmode == _capi.LC_X_CLAMP_REFERENCE_OUTER:
+            level_chunk = nsteps               # one block: the clamp is decided over the whole grid, level by level, inside one call
+        cyclic = xmode == _capi.LC_X_CYCLIC
+        x = y = tau = fsle = None
+        for done in range(0, nsteps, level_chunk):
+            n = min(level_chunk, nsteps - done)
+            x, y, tx, ty = self.advect(field, seed_lat, seed_lon, timestep, t0=t0 + done, nsteps=n, return_traj=True,
+                                       start=None if done == 0 else (x, y), out=None if done == 0 else (x, y), **kw)
+            tau, fsle = self.fsle_update(tx, ty, seed_lat, seed_lon, thr, mode, timestep, done, tau, fsle, cyclic=cyclic, radius=radius)
+            del tx, ty
+        return {"tau": tau, "fsle": fsle, "x_dep": x, "y_dep": y}
+
     def synchronize(self):
         self.torch.cuda.synchronize(self.device)
 
