@@ -38,7 +38,7 @@ extern "C" {
  * client built against 100 must be rebuilt), lc_ctx_get_level_chunk, lc_ctx_set/get_f64_fidelity, lc_advect_ex and
  * lc_sample_raw added, lc_field_pack accepts packed_dev == NULL at order 1 (fused-level image only).  lc_version() returns the value the LIBRARY
  * was built with: compare it with this macro before any other call (tests/c/abi_smoke.c, _capi.load do). */
-#define LC_VERSION 104 /* 0.1.4: + lc_fsle_update, lc_ctx_last_fsle_kernel (added without a bump), + lc_aux_gradient, lc_ctx_last_aux_kernel (added without a bump), + lc_mask_morphology, lc_morph_work_elems (added without a bump), + lc_label_components, lc_label_work_elems, lc_component_sums, lc_component_apply, + lc_strain, lc_ctx_last_strain_kernel, + lc_advect_series_dirs, + lc_advect_series, lc_sigma_batch, + lc_tracer_sample, lc_ctx_last_tracer_kernel (additive: no argument list changed), + lc_ctx_set_host_pipeline, lc_copy_to_device, lc_copy_to_host, lc_ctx_set_host_cache, lc_ctx_trim, lc_ctx_last_host_marks, lc_ctx_set_xcd_split (0.1.3: + lc_ctx_last_pack_kernel; 0.1.2: + lc_ctx_set_verify, lc_ctx_read_verify, LC_F64_WIND_F32_LIN32) */
+#define LC_VERSION 104 /* 0.1.4: + lc_vorticity, lc_vorticity_work_elems, lc_ctx_last_vorticity_kernel, lc_lavd_update, lc_ctx_last_lavd_kernel (added without a bump), + lc_fsle_update, lc_ctx_last_fsle_kernel (added without a bump), + lc_aux_gradient, lc_ctx_last_aux_kernel (added without a bump), + lc_mask_morphology, lc_morph_work_elems (added without a bump), + lc_label_components, lc_label_work_elems, lc_component_sums, lc_component_apply, + lc_strain, lc_ctx_last_strain_kernel, + lc_advect_series_dirs, + lc_advect_series, lc_sigma_batch, + lc_tracer_sample, lc_ctx_last_tracer_kernel (additive: no argument list changed), + lc_ctx_set_host_pipeline, lc_copy_to_device, lc_copy_to_host, lc_ctx_set_host_cache, lc_ctx_trim, lc_ctx_last_host_marks, lc_ctx_set_xcd_split (0.1.3: + lc_ctx_last_pack_kernel; 0.1.2: + lc_ctx_set_verify, lc_ctx_read_verify, LC_F64_WIND_F32_LIN32) */
 
 typedef struct lc_ctx lc_ctx;
 
@@ -686,6 +686,91 @@ typedef struct lc_fsle_args {
 } lc_fsle_args;
 int lc_fsle_update(lc_ctx *ctx, const lc_fsle_args *args);
 const char *lc_ctx_last_fsle_kernel(const lc_ctx *ctx);
+
+/* ---- relative vorticity of a wind record (Engine.vorticity, tools.relative_vorticity, LCS.lavd) ----
+ * No counterpart in the reference.  u, v: [nt][ny_f][nx_f] dtype elements on a uniform ascending grid, as the samplers assume;
+ * k = pi / 180 (the float64 pi), row r lies at lat_r = lat_min + r dlat degrees, dlat = (lat_max - lat_min) / (ny_f - 1), both in
+ * float64; dphi = k dlat and dlambda = k (lon_max - lon_min) / (nx_f - 1), formed in float64 and rounded to the dtype T together
+ * with the factor 2 of the stencils; cos phi_r = cos(k lat_r) in float64, rounded to T where it multiplies a T.
+ *   omega       = (dv/dlambda - d(u cos phi)/dphi) / (radius cos phi), every operation in T; the product u cos phi is formed in
+ *               T before it is differenced
+ *   latitude    interior rows: (f[r+1] - f[r-1]) / 2dphi.  First row: ((-3 f[0] + 4 f[1]) - f[2]) / 2dphi; last row its mirror
+ *               ((3 f[n-1] - 4 f[n-2]) + f[n-3]) / 2dphi: second order (first-order edges are wrong by 23 % for solid-body
+ *               rotation on a 5 degree grid at +-80 degrees, these by 1.3 %)
+ *   longitude   centred; with cyclic_x centred across the seam (column -1 is column nx_f - 1, at spacing dlambda: the samplers'
+ *               wrap mode makes the same assumption); without it the one-sided forms above on the first and last column
+ *   pole rows   a first or last row with 90 - |lat_r| <= 1e-6 degrees (cos(pi/2) is 6e-17 in float64, not 0: dividing by it
+ *               gives garbage, not NaN).  There omega is, at every column, the mean -- summed in float64, rounded to T -- over
+ *               the finite nodes of the adjacent row's omega, NaN where that row has none: the limit a smooth flow has there.
+ *               A pole row's weight in the domain mean is exactly 0
+ *   NaN         a u or v that is not finite anywhere in a node's stencil gives NaN at that node, and only there
+ *   level_mean  [nt] float64, written in every mode: sum w omega / sum w over the finite nodes of level t off the pole rows,
+ *               w = cos phi_r, sums and products in float64 whatever T is; NaN when no node is finite
+ *   deviation   LC_VORT_DEVIATION_DOMAIN: omega = (T)((double)omega - level_mean[t]) at every node, pole rows included;
+ *               LC_VORT_DEVIATION_NONE: omega stays (regional domains, where the box's mean means little);
+ *               LC_VORT_DEVIATION_GIVEN: the same with given_dev[t] (nt float64, device) in place of level_mean[t]
+ *   work_dev    lc_vorticity_work_elems(nt, ny_f, nx_f) float64 elements of device scratch (0: sizes the call refuses): one
+ *               partial (sum w omega, sum w) per workgroup, each formed in a fixed tree; a second launch adds a level's partials
+ *               in index order.  No floating-point atomics: two runs give the same bits
+ * Refused with LC_EINVAL before any HIP call: a null context or argument structure, a wrong struct_size, a bad dtype or mode,
+ * nt < 1, ny_f < 4 or nx_f < 4 (the samplers' own minimum), a plane of 2^31 nodes or more or a record that needs more workgroups
+ * than one launch takes, latitudes or longitudes that are not finite and ascending or lie outside -90 .. 90, a radius that is
+ * not positive and finite, a null pointer (given_dev only in its mode).
+ * lc_ctx_last_vorticity_kernel: what the context's last lc_vorticity launched ("" before any, or for a null context):
+ * "vorticity_kernel<T>+vorticity_finish_kernel<T>" and, but for LC_VORT_DEVIATION_NONE, "+vorticity_subtract_kernel<T>",
+ * T float or double. */
+enum lc_vort_deviation { LC_VORT_DEVIATION_DOMAIN = 0, LC_VORT_DEVIATION_NONE = 1, LC_VORT_DEVIATION_GIVEN = 2 };
+typedef struct lc_vorticity_args {
+    size_t struct_size; /* sizeof(lc_vorticity_args): checked before any other field */
+    const void *u, *v;
+    int dtype, nt, ny_f, nx_f;
+    double lat_min, lat_max, lon_min, lon_max;
+    int cyclic_x, deviation; /* enum lc_vort_deviation */
+    double radius;
+    const double *given_dev;
+    void *omega;
+    double *level_mean;
+    void *work_dev;
+} lc_vorticity_args;
+size_t lc_vorticity_work_elems(int nt, int ny_f, int nx_f);
+int lc_vorticity(lc_ctx *ctx, const lc_vorticity_args *args);
+const char *lc_ctx_last_vorticity_kernel(const lc_ctx *ctx);
+
+/* ---- vorticity deviation, rotation and path length along trajectories (Engine.lavd_update, Engine.lavd, LCS.lavd) ----
+ * No counterpart in the reference.  LAVD(x0) = integral of |omega(x(t), t) - mean(t)| dt along the trajectory from x0 (Haller,
+ * Hadjighasem, Farazmand and Huhn 2016); the signed integral is the rotation; the great-circle length of the trajectory is the
+ * arc-length Lagrangian descriptor M of Mancho et al.  One block of trajectory levels is folded into the three running
+ * integrals of every parcel; nothing is shared between parcels.
+ *   traj_x, traj_y   [n_levels][n] dtype elements, degrees: positions after level0, level0 + 1, ... steps
+ *   c           [n_levels][n] dtype elements or NULL: omega - mean sampled at the same entries (lc_tracer_sample's c1_out)
+ *   per interval j = 1 .. n_levels - 1, in level order, in float64 without contraction (T widened first):
+ *               acc[0] += (0.5 (|c[j-1]| + |c[j]|)) |timestep|
+ *               acc[1] += (0.5 ( c[j-1]  +  c[j] )) |timestep|
+ *               acc[2] += d(j-1, j), the great-circle distance of lc_fsle_update's separation formed in T:
+ *               h = sin^2(k dphi / 2) + cos(k phi1) cos(k phi2) sin^2(k dlambda / 2),  d = 2 radius asin(min(1, sqrt h)),
+ *               dlambda the raw difference (periodic: a step across the seam is the short way round)
+ *   acc         [3][n] float64, the carried state: read unless level0 == 0 (then the sums start at 0), always written.  Entry 0
+ *               of a continued block is the last entry of the block before; each sum is float64 added in level order, so any
+ *               split of a record into blocks gives, bit for bit, what one block gives
+ *   lavd, rotation, length   [n] dtype elements, each NULL or written as (T)acc[0], (T)acc[1], (T)acc[2] (metres)
+ *   NaN         a NaN position makes that parcel's length, a NaN value that parcel's lavd and rotation, NaN from that level on,
+ *               and no other parcel's; a NaN in c does not touch length
+ *   c == NULL   only length is produced: acc[0] and acc[1] are carried unchanged (0 from level0 == 0), lavd and rotation must
+ *               be NULL
+ * Refused with LC_EINVAL before any HIP call: a null context or argument structure, a wrong struct_size, a bad dtype, n < 1,
+ * n_levels < 2, level0 < 0, a radius or |timestep| that is not positive and finite, a null traj_x, traj_y or acc, lavd or
+ * rotation without c.
+ * lc_ctx_last_lavd_kernel: "lavd_update_kernel<float | double, true | false>" (false: c == NULL); "" before any call. */
+typedef struct lc_lavd_args {
+    size_t struct_size; /* sizeof(lc_lavd_args): checked before any other field */
+    const void *traj_x, *traj_y, *c;
+    int dtype, n, n_levels, level0;
+    double timestep, radius;
+    double *acc;
+    void *lavd, *rotation, *length;
+} lc_lavd_args;
+int lc_lavd_update(lc_ctx *ctx, const lc_lavd_args *args);
+const char *lc_ctx_last_lavd_kernel(const lc_ctx *ctx);
 
 /* The 9-component "def_tensor" itself, for callers of LCS.flowmap_gradient
  * (LCS/LCS.py:171-225): planes dXdx,dXdy,dYdx,dYdy,dZdx,dZdy,dXdr,dYdr,dZdr (the last

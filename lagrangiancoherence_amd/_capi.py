@@ -373,6 +373,38 @@ LC_FSLE_RATIO, LC_FSLE_DISTANCE = 0, 1
 PROTOTYPES["lc_fsle_update"] = (_i, [_vp, C.POINTER(FsleArgs)])
 PROTOTYPES["lc_ctx_last_fsle_kernel"] = (C.c_char_p, [_vp])
 
+
+class VorticityArgs(C.Structure):
+    """``lc_vorticity_args`` of include/lcs_hip.h, field for field."""
+    _fields_ = [("struct_size", _sz),
+                ("u", _vp), ("v", _vp),
+                ("dtype", _i), ("nt", _i), ("ny_f", _i), ("nx_f", _i),
+                ("lat_min", C.c_double), ("lat_max", C.c_double), ("lon_min", C.c_double), ("lon_max", C.c_double),
+                ("cyclic_x", _i), ("deviation", _i),
+                ("radius", C.c_double),
+                ("given_dev", _vp),
+                ("omega", _vp), ("level_mean", _vp), ("work_dev", _vp)]
+
+
+LC_VORT_DEVIATION_DOMAIN, LC_VORT_DEVIATION_NONE, LC_VORT_DEVIATION_GIVEN = 0, 1, 2
+PROTOTYPES["lc_vorticity_work_elems"] = (_sz, [_i, _i, _i])
+PROTOTYPES["lc_vorticity"] = (_i, [_vp, C.POINTER(VorticityArgs)])
+PROTOTYPES["lc_ctx_last_vorticity_kernel"] = (C.c_char_p, [_vp])
+
+
+class LavdArgs(C.Structure):
+    """``lc_lavd_args`` of include/lcs_hip.h, field for field."""
+    _fields_ = [("struct_size", _sz),
+                ("traj_x", _vp), ("traj_y", _vp), ("c", _vp),
+                ("dtype", _i), ("n", _i), ("n_levels", _i), ("level0", _i),
+                ("timestep", C.c_double), ("radius", C.c_double),
+                ("acc", _vp),
+                ("lavd", _vp), ("rotation", _vp), ("length", _vp)]
+
+
+PROTOTYPES["lc_lavd_update"] = (_i, [_vp, C.POINTER(LavdArgs)])
+PROTOTYPES["lc_ctx_last_lavd_kernel"] = (C.c_char_p, [_vp])
+
 _lib = None
 
 

@@ -588,6 +588,70 @@ class LCS:
                     self._windows_out(rec, forward, stack("y_dep", 0), crop=False))
         return out
 
+    def lavd(self, ds=None, u=None, v=None, window=None, stride=1, deviation="domain", verbose=True, s=None, resample=None,
+             s_is_error=False, isglobal=False, interp_to_common_grid=True, traj_interp_order=3, truncation=20, level_chunk=16):
+        """Elliptic coherence: ``(lavd, rotation, path_length)``, each with dims ``(timedim, latitude, longitude)``.
+
+        ``lavd`` is the Lagrangian-averaged vorticity deviation of Haller et al. (2016) before the division by time: the
+        integral along each parcel's trajectory of ``|omega - mean|`` (trapezoid rule over the time levels; dimensionless),
+        ``omega`` the relative vorticity of the wind the parcels see -- the record after ``resample``, sort, regrid and T20
+        -- and ``mean`` its area-weighted domain mean at each level.  Coherent vortices are its local maxima.  ``rotation`` is
+        the signed integral of ``omega - mean``: positive for counter-clockwise rotation (cyclones in the northern hemisphere).
+        ``path_length`` is the great-circle length of the trajectory in metres (the arc-length Lagrangian descriptor).  The
+        attrs carry ``integration_time = (window length - 1) |timestep|`` seconds: divide by it for the averages.
+
+        ``deviation``: ``'domain'`` (above), ``'none'`` (integrate ``|omega|`` itself: regional boxes, whose mean means little)
+        or one value per time level of the record to subtract.  ``window`` / ``stride``, the intake (:meth:`_record_intake`),
+        the one pack, the ``subdomain`` crop and the time labels are :meth:`strain`'s and :meth:`fsle`'s; the vorticity is computed
+        and packed once for all windows (``Engine.vorticity``, ``Engine.prepare_tracer``) and each window is streamed through
+        ``Engine.lavd`` in blocks of ``level_chunk`` steps.  The direction of integration is the sign of ``timestep``.  With
+        ``return_dpts`` ``x_dep`` and ``y_dep`` are appended.  Not with ``aux_grid``.  The full definition: INTEGRATION.md
+        "Vortices: LAVD, rotation and path length"."""
+        if self.aux_grid is not None:
+            raise ValueError("lavd: the integrals of the auxiliary parcels are not implemented; use an LCS without aux_grid")
+        if not self.timestep or not np.isfinite(self.timestep):
+            raise ValueError(f"timestep {self.timestep!r}: lavd needs a non-zero finite step")
+        if isinstance(level_chunk, bool) or int(level_chunk) != level_chunk or int(level_chunk) < 1:
+            raise ValueError(f"lavd: level_chunk {level_chunk!r} (at least 1)")
+        given = Engine.checked_deviation(deviation)[1]
+        if given is not None and not isinstance(resample, str) and not isinstance(ds, str):
+            like = ds.u if ds is not None else u                            # the record as given: its levels are the windows' levels
+            if like is not None and given.size != np.asarray(like[self.timedim].values).size:
+                raise ValueError(f"lavd: {given.size} deviation values for {np.asarray(like[self.timedim].values).size} time levels")
+        verboseprint = print if verbose else (lambda *a, **k: None)
+        rec = self._record_intake(ds, u, v, window, stride, resample, isglobal, interp_to_common_grid, truncation, verbose)
+        Engine.checked_vorticity_options(np.shape(rec.uu), np.shape(rec.vv), rec.lat, rec.lon, deviation, self.earth_r)
+        verboseprint(f"*---- Vorticity and parcel propagation: {rec.n_windows} window(s) ----*")
+        eng = get_engine()
+        dtype = common_dtype(rec.uu, rec.vv, rec.lat, rec.lon)
+        omega = eng.vorticity(rec.uu, rec.vv, rec.lat, rec.lon, cyclic=rec.cyclic_xboundary, deviation=deviation, radius=self.earth_r,
+                              dtype=dtype)["omega"]
+        tracer = eng.prepare_tracer(omega, None, rec.lat, rec.lon, traj_interp_order, dtype=dtype)
+        field, lat_t, lon_t = self._packed_record(eng, rec, traj_interp_order)
+        res = [eng.lavd(field, tracer, lat_t, lon_t, rec.timestep, t0=w * rec.wstep, nsteps=rec.wlen - 1, level_chunk=int(level_chunk),
+                        SETTLS_order=self.SETTLS_order, interp_order=traj_interp_order, cyclic_xboundary=rec.cyclic_xboundary,
+                        radius=self.earth_r) for w in range(rec.n_windows)]
+        verboseprint("*---- Done vorticity deviation ----*")
+
+        forward = np.sign(rec.timestep) == 1
+        attrs = {"integration_time": (rec.wlen - 1) * abs(float(rec.timestep))}
+        stack = lambda k: np.stack([_to_np(r[k]) for r in res], axis=0)
+        out = tuple(_with_attrs(self._windows_out(rec, forward, stack(k), name), attrs)
+                    for k, name in (("lavd", "lavd"), ("rotation", "rotation"), ("length", "path_length")))
+        if self.return_dpts:                                               # LCS.py:161-168
+            out += (self._windows_out(rec, forward, stack("x_dep"), crop=False),
+                    self._windows_out(rec, forward, stack("y_dep"), crop=False))
+        return out
+
+
+def _with_attrs(a, attrs):
+    """``a`` with ``attrs`` added to its ``attrs`` mapping (a labelled-array class without one is given one)."""
+    try:
+        a.attrs.update(attrs)
+    except AttributeError:
+        a.attrs = dict(attrs)
+    return a
+
 
 def _resample_ratio(t_orig, t_new) -> int:
     """Resampled levels per original level: the resampled times must be uniformly spaced and hold every original time at

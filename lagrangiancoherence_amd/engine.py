@@ -2836,6 +2836,211 @@ class Engine:
             del tx, ty
         return {"tau": tau, "fsle": fsle, "x_dep": x, "y_dep": y}
 
+    # ------------------------------------------------------------------ vorticity, LAVD, rotation and path length
+    _VORT_DEVIATIONS = {"domain": _capi.LC_VORT_DEVIATION_DOMAIN, "none": _capi.LC_VORT_DEVIATION_NONE}
+    GRID_UNIFORM_RTOL = 1e-3     # a coordinate step may differ from the mean step by this fraction (float32 coordinates round)
+
+    def last_vorticity_kernel(self) -> str:
+        """Names of the kernels the last :meth:`vorticity` call launched (``lc_ctx_last_vorticity_kernel``)."""
+        return self.lib.lc_ctx_last_vorticity_kernel(self.ctx).decode()
+
+    def last_lavd_kernel(self) -> str:
+        """Name of the kernel the last :meth:`lavd_update` call launched (``lc_ctx_last_lavd_kernel``)."""
+        return self.lib.lc_ctx_last_lavd_kernel(self.ctx).decode()
+
+    @classmethod
+    def checked_deviation(cls, deviation, nt=None):
+        """``(mode, given)`` of a ``deviation`` argument, or ``ValueError``: ``'domain'`` (subtract each level's area-weighted
+        mean), ``'none'``, or one finite number per time level (``given``: float64, 1-D; checked against ``nt`` when it is
+        known)."""
+        if isinstance(deviation, str):
+            if deviation not in cls._VORT_DEVIATIONS:
+                raise ValueError(f"vorticity: deviation {deviation!r} ('domain', 'none' or one value per time level)")
+            return cls._VORT_DEVIATIONS[deviation], None
+        try:
+            given = np.asarray(deviation, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"vorticity: deviation {deviation!r} ('domain', 'none' or one value per time level)") from None
+        if given.ndim != 1 or given.size < 1 or not np.all(np.isfinite(given)):
+            raise ValueError("vorticity: a given deviation is one finite value per time level, one-dimensional")
+        if nt is not None and given.size != int(nt):
+            raise ValueError(f"vorticity: {given.size} deviation values for {int(nt)} time levels")
+        return _capi.LC_VORT_DEVIATION_GIVEN, np.ascontiguousarray(given)
+
+    @classmethod
+    def checked_vorticity_options(cls, u_shape, v_shape, lat_f, lon_f, deviation="domain", radius=6371000.0):
+        """``(nt, ny_f, nx_f, mode, given, radius)`` as :meth:`vorticity` hands them to the library, or ``ValueError``: ``u`` and
+        ``v`` of one ``(time, latitude, longitude)`` shape with at least 4 rows and 4 columns; finite, ascending, uniformly
+        spaced coordinates of those lengths, latitudes within -90 .. 90; a ``deviation`` :meth:`checked_deviation` accepts for
+        that many levels; a positive finite radius."""
+        u_shape, v_shape = tuple(int(s) for s in u_shape), tuple(int(s) for s in v_shape)
+        if len(u_shape) != 3 or u_shape != v_shape:
+            raise ValueError("vorticity: u and v must both be (time, latitude, longitude)")
+        nt, ny_f, nx_f = u_shape
+        if nt < 1 or ny_f < 4 or nx_f < 4:
+            raise ValueError(f"vorticity: a record of {nt} x {ny_f} x {nx_f} (at least one level of 4 x 4 nodes)")
+        try:
+            lat, lon = np.asarray(lat_f, dtype=np.float64), np.asarray(lon_f, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("vorticity: latitude and longitude must be numbers") from None
+        if lat.shape != (ny_f,) or lon.shape != (nx_f,):
+            raise ValueError("vorticity: coordinate lengths do not match the wind")
+        for c, what in ((lat, "latitude"), (lon, "longitude")):
+            d = np.diff(c)
+            if not np.all(np.isfinite(c)) or not np.all(d > 0):
+                raise ValueError(f"vorticity: {what} must be finite and ascending (sort first)")
+            if np.max(np.abs(d - d.mean())) > cls.GRID_UNIFORM_RTOL * d.mean():
+                raise ValueError(f"vorticity: {what} must be uniformly spaced (regrid first)")
+        if lat[0] < -90.0 or lat[-1] > 90.0:
+            raise ValueError(f"vorticity: latitudes {lat[0]} .. {lat[-1]} outside -90 .. 90")
+        mode, given = cls.checked_deviation(deviation, nt)
+        try:
+            radius = float(radius)
+        except (TypeError, ValueError):
+            raise ValueError(f"vorticity: radius {radius!r}") from None
+        if not np.isfinite(radius) or radius <= 0:
+            raise ValueError(f"vorticity: radius {radius} (positive and finite)")
+        return nt, ny_f, nx_f, mode, given, radius
+
+    def vorticity(self, u, v, lat_f, lon_f, cyclic=False, deviation="domain", radius=6371000.0, dtype=None) -> dict:
+        """Relative vorticity of a wind record on the sphere (``lc_vorticity``; the definition is in include/lcs_hip.h and
+        restated in tests/lavd.py): ``{'omega': (nt, ny_f, nx_f) device tensor of the compute dtype, 'level_mean': (nt,) float64
+        device tensor}``.  ``omega = (dv/dlambda - d(u cos phi)/dphi) / (R cos phi)`` with centred differences, second-order
+        one-sided ones at the first and last row (and column, unless ``cyclic``: then centred across the seam), the adjacent row's
+        mean on a pole row, NaN where a stencil holds a non-finite wind.  ``level_mean[t]`` is the ``cos phi``-weighted mean of
+        level ``t`` over its finite nodes.  ``deviation='domain'`` subtracts it from level ``t``, ``'none'`` leaves ``omega`` as it
+        is, an array subtracts one given value per level; ``level_mean`` is returned in every case.  The grid must be uniform and
+        ascending.  ``dtype``: the compute dtype; default float32 only if every input is."""
+        nt, ny_f, nx_f, mode, given, radius = self.checked_vorticity_options(np.shape(u), np.shape(v), lat_f, lon_f, deviation, radius)
+        lat, lon = np.asarray(lat_f), np.asarray(lon_f)
+        dtype = np.dtype(dtype or common_dtype(u, v, lat, lon))
+        if dtype not in _NP2LC:
+            raise ValueError(f"vorticity: dtype {dtype} (float32 or float64)")
+        elems = int(self.lib.lc_vorticity_work_elems(nt, ny_f, nx_f))
+        if elems == 0:
+            raise ValueError(f"vorticity: a record of {nt} x {ny_f} x {nx_f} is too large for one call")
+        du, dv = self.to_device(u, dtype), self.to_device(v, dtype)
+        omega = self._empty((nt, ny_f, nx_f), dtype)
+        mean = self._empty((nt,), np.float64)
+        work = self._empty((elems,), np.float64)
+        gdev = self.to_device(given, np.float64) if given is not None else None
+        a = _capi.VorticityArgs(struct_size=C.sizeof(_capi.VorticityArgs), u=du.data_ptr(), v=dv.data_ptr(), dtype=_NP2LC[dtype], nt=nt,
+                                ny_f=ny_f, nx_f=nx_f, lat_min=float(lat[0]), lat_max=float(lat[-1]), lon_min=float(lon[0]),
+                                lon_max=float(lon[-1]), cyclic_x=int(bool(cyclic)), deviation=mode, radius=radius,
+                                given_dev=gdev.data_ptr() if gdev is not None else None, omega=omega.data_ptr(),
+                                level_mean=mean.data_ptr(), work_dev=work.data_ptr())
+        self._use_current_stream()
+        _capi.check(self.lib.lc_vorticity(self.ctx, C.byref(a)), self.lib)
+        return {"omega": omega, "level_mean": mean}
+
+    def lavd_update(self, traj_x, traj_y, c, timestep, level0, acc=None, final=False, radius=6371000.0) -> dict:
+        """One block of trajectory levels folded into the running integrals of LAVD, rotation and path length
+        (``lc_lavd_update``; the definition is in include/lcs_hip.h and restated in tests/lavd.py).  ``traj_x``, ``traj_y``:
+        ``(n_levels, ...)`` positions in degrees after ``level0``, ``level0 + 1``, ... steps, ``n_levels >= 2``; entry 0 of a
+        continued block (``level0 > 0``) is the last entry of the block before.  ``c``: the vorticity deviation sampled at the
+        same entries (:meth:`sample_tracer`), or None for the path length alone.  ``acc``: the ``(3, ...)`` float64 tensor the
+        previous block returned -- updated in place; with ``level0 == 0`` it may be omitted (or is overwritten).  Returns
+        ``{'acc'}`` and, with ``final``, ``'lavd'`` (the integral of ``|c|`` over time, trapezoid rule), ``'rotation'`` (the signed
+        integral) -- both None without ``c`` -- and ``'length'`` (metres), each of the trajectories' dtype and shape
+        ``traj_x.shape[1:]``."""
+        try:
+            timestep, radius = float(timestep), float(radius)
+        except (TypeError, ValueError):
+            raise ValueError(f"lavd_update: timestep {timestep!r}, radius {radius!r}") from None
+        if not np.isfinite(timestep) or timestep == 0:
+            raise ValueError(f"lavd_update: timestep {timestep} (non-zero and finite)")
+        if not np.isfinite(radius) or radius <= 0:
+            raise ValueError(f"lavd_update: radius {radius} (positive and finite)")
+        level0 = int(level0)
+        if level0 < 0:
+            raise ValueError(f"lavd_update: level0 {level0}")
+        shape = tuple(int(s) for s in np.shape(traj_x))
+        if len(shape) < 2 or shape != tuple(int(s) for s in np.shape(traj_y)) or (c is not None and tuple(int(s) for s in np.shape(c)) != shape):
+            raise ValueError("lavd_update: traj_x, traj_y and c must have one shape, (n_levels, ...)")
+        n_levels, n = shape[0], int(np.prod(shape[1:]))
+        if n_levels < 2 or n < 1 or n >= 1 << 31:
+            raise ValueError(f"lavd_update: {n_levels} levels of {n} parcels (at least two levels and one parcel, fewer than 2^31)")
+        if acc is None and level0 != 0:
+            raise ValueError("lavd_update: a continued block (level0 > 0) needs the acc of the block before")
+        on_dev = all(hasattr(a, "data_ptr") for a in (traj_x, traj_y) + (() if c is None else (c,)))
+        dtype = np.dtype(str(traj_x.dtype).replace("torch.", "")) if on_dev else common_dtype(traj_x, traj_y, c)
+        if dtype not in _NP2LC:
+            raise ValueError(f"lavd_update: dtype {dtype} (float32 or float64)")
+        torch = self.torch
+        tx, ty = self.to_device(traj_x, dtype), self.to_device(traj_y, dtype)
+        cd = self.to_device(c, dtype) if c is not None else None
+        if acc is None:
+            acc = self._empty((3,) + shape[1:], np.float64)
+        if not isinstance(acc, torch.Tensor) or tuple(acc.shape) != (3,) + shape[1:] or acc.dtype != torch.float64 \
+                or not acc.is_contiguous() or acc.device != self.device:
+            raise ValueError(f"lavd_update: acc must be a contiguous {(3,) + shape[1:]} float64 tensor on {self.device}")
+        out = [self._empty(shape[1:], dtype) if final and (cd is not None or k == 2) else None for k in range(3)]
+        p = lambda t: t.data_ptr() if t is not None else None
+        a = _capi.LavdArgs(struct_size=C.sizeof(_capi.LavdArgs), traj_x=tx.data_ptr(), traj_y=ty.data_ptr(), c=p(cd), dtype=_NP2LC[dtype],
+                           n=n, n_levels=n_levels, level0=level0, timestep=timestep, radius=radius, acc=acc.data_ptr(), lavd=p(out[0]),
+                           rotation=p(out[1]), length=p(out[2]))
+        self._use_current_stream()
+        _capi.check(self.lib.lc_lavd_update(self.ctx, C.byref(a)), self.lib)
+        res = {"acc": acc}
+        if final:
+            res.update(lavd=out[0], rotation=out[1], length=out[2])
+        return res
+
+    def lavd(self, field: PackedField, tracer, seed_lat, seed_lon, timestep, t0=0, nsteps=None, level_chunk=16, SETTLS_order=0,
+             interp_order=1, cyclic_xboundary=True, noncyclic_clamp=None, radius=6371000.0) -> dict:
+        """LAVD, rotation and path length of the seed grid's parcels over ``nsteps`` steps from level ``t0`` of a packed field:
+        ``{'lavd', 'rotation', 'length'}`` as ``(ny, nx)`` device tensors (:meth:`lavd_update`) and the departure points
+        ``'x_dep'``, ``'y_dep'`` of :meth:`advect`.  ``tracer``: the vorticity deviation on the wind's grid and time levels
+        (:meth:`vorticity`, then :meth:`prepare_tracer`); trajectory entry i is sampled at field level ``t0 + i`` whatever the
+        sign of ``timestep``, as :meth:`advect_tracer` samples.  ``tracer=None``: the path length alone (``'lavd'`` and
+        ``'rotation'`` are None).
+
+        The record is streamed as :meth:`fsle` streams it: each block of ``level_chunk`` steps is advected from where the last
+        one ended (bit for bit what one call gives), sampled and folded, then dropped, so ``2 (level_chunk + 1)`` position planes
+        and ``level_chunk + 1`` value planes are alive at a time; the result does not depend on ``level_chunk``.
+        ``cyclic_xboundary=False`` with the default ``reference_outer`` clamp cannot be continued and takes one block over all
+        levels; ``noncyclic_clamp='pointwise'`` streams."""
+        try:
+            timestep, radius = float(timestep), float(radius)
+        except (TypeError, ValueError):
+            raise ValueError(f"lavd: timestep {timestep!r}, radius {radius!r}") from None
+        if not np.isfinite(timestep) or timestep == 0:
+            raise ValueError(f"lavd: timestep {timestep} (non-zero and finite)")
+        if not np.isfinite(radius) or radius <= 0:
+            raise ValueError(f"lavd: radius {radius} (positive and finite)")
+        _check_order(field, interp_order)
+        if tracer is not None:
+            if tracer.dtype != field.dtype:
+                raise ValueError(f"lavd: tracer dtype {tracer.dtype} differs from the field's compute dtype {field.dtype}")
+            if (tracer.nt, tracer.ny_f, tracer.nx_f) != (field.nt, field.ny_f, field.nx_f) or \
+                    (tracer.lat_min, tracer.lat_max, tracer.lon_min, tracer.lon_max) != (field.lat_min, field.lat_max, field.lon_min, field.lon_max):
+                raise ValueError("lavd: the tracer must lie on the wind's grid and time levels")
+            _check_order(tracer, interp_order)
+        t0 = int(t0)
+        nsteps = field.nt - 1 - t0 if nsteps is None else int(nsteps)
+        level_chunk = int(level_chunk)
+        if t0 < 0 or nsteps < 1 or t0 + nsteps > field.nt - 1:
+            raise ValueError(f"lavd: t0 {t0}, nsteps {nsteps} on a record of {field.nt} levels (at least one step, inside the record)")
+        if level_chunk < 1:
+            raise ValueError(f"lavd: level_chunk {level_chunk} (at least 1)")
+        count = lambda a: int(a.numel()) if hasattr(a, "numel") else int(np.size(a))
+        if np.ndim(seed_lat) != 1 or np.ndim(seed_lon) != 1 or count(seed_lat) * count(seed_lon) < 1:
+            raise ValueError("lavd: seed_lat and seed_lon must be 1-D and hold at least one seed each")
+        xmode = x_boundary_mode(cyclic_xboundary, noncyclic_clamp, True)
+        kw = dict(SETTLS_order=SETTLS_order, interp_order=interp_order, cyclic_xboundary=cyclic_xboundary, noncyclic_clamp=noncyclic_clamp)
+        if xmode == _capi.LC_X_CLAMP_REFERENCE_OUTER:
+            level_chunk = nsteps               # one block: the clamp is decided over the whole grid, level by level, inside one call
+        x = y = acc = res = None
+        for done in range(0, nsteps, level_chunk):
+            n = min(level_chunk, nsteps - done)
+            x, y, tx, ty = self.advect(field, seed_lat, seed_lon, timestep, t0=t0 + done, nsteps=n, return_traj=True,
+                                       start=None if done == 0 else (x, y), out=None if done == 0 else (x, y), **kw)
+            c = None if tracer is None else self.sample_tracer(tracer, tx, ty, level0=t0 + done, interp_order=interp_order)[0][0]
+            res = self.lavd_update(tx, ty, c, timestep, done, acc, final=done + n == nsteps, radius=radius)
+            acc = res["acc"]
+            del tx, ty, c
+        return {"lavd": res["lavd"], "rotation": res["rotation"], "length": res["length"], "x_dep": x, "y_dep": y}
+
     def synchronize(self):
         self.torch.cuda.synchronize(self.device)
 

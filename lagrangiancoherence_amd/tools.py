@@ -51,7 +51,7 @@ from .engine import Engine, common_dtype
 __all__ = ["xr_map_coordinates", "fourth_order_derivative", "derivative_spherical_coords",
            "find_ridges_spherical_hessian", "filter_ridges", "distance_to_ridges", "skeletonize_ridges", "dilate_ridges",
            "threshold_local", "above_local_threshold", "track_ridges", "persistent_ridges", "ridge_properties", "ridge_lines",
-           "ridge_transects",
+           "ridge_transects", "relative_vorticity",
            "Inverse_weighted_interpolation", "xr_idx_interp"]
 
 
@@ -848,6 +848,43 @@ def above_local_threshold(da, block_size, offset=0, param=None, cyclic=False):
 
     Returns the boolean mask in the caller's class and dimension order."""
     return _local_threshold(da, block_size, 'gaussian', offset, 'reflect', param, cyclic, "mask")
+
+
+def relative_vorticity(u, v, cyclic=False, deviation='none', radius=6371000.0):
+    """Relative vorticity of a wind on the sphere, ``(dv/dlambda - d(u cos phi)/dphi) / (R cos phi)`` in 1/s, on the device
+    (``Engine.vorticity``): centred differences, second-order one-sided ones at the first and last row (and column, unless
+    ``cyclic``: then centred across the seam), the adjacent row's mean on a pole row, NaN where a stencil holds a non-finite
+    wind.  ``u`` and ``v`` are labelled arrays over ``latitude`` and ``longitude`` -- uniformly spaced; sorted ascending here, as
+    ``filter_ridges`` sorts -- 2-D, or 3-D with one more dimension (time).  ``deviation``: ``'none'``, ``'domain'`` (subtract
+    each level's ``cos phi``-weighted mean: the field ``LCS.lavd`` integrates) or one value per level to subtract.
+
+    Returns the vorticity in the caller's class with dims ``(time, latitude, longitude)`` (``(latitude, longitude)`` for a
+    2-D wind), named ``'vorticity'``."""
+    dims = tuple(u.dims)
+    if set(dims) != set(v.dims):
+        raise ValueError("u and v dims are different")
+    lead = [d for d in dims if d not in ("latitude", "longitude")]
+    if len(lead) > 1 or len(dims) - len(lead) != 2:
+        raise ValueError("u, v: dims (latitude, longitude) and at most one more")
+    order = (*lead, "latitude", "longitude")
+    lat, lon = _coord(u, "latitude"), _coord(u, "longitude")
+    if not (np.array_equal(lat, _coord(v, "latitude")) and np.array_equal(lon, _coord(v, "longitude"))):
+        raise ValueError("u and v coordinates differ")
+    ilat, ilon = np.argsort(lat, kind="stable"), np.argsort(lon, kind="stable")
+
+    def planes(da):
+        a = np.asarray(da.transpose(*order).values)
+        a = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+        a = np.ascontiguousarray(a[..., ilat, :][..., ilon])
+        return a if lead else a[None]
+    uu, vv = planes(u), planes(v)
+    lat, lon = lat[ilat], lon[ilon]
+    Engine.checked_vorticity_options(uu.shape, vv.shape, lat, lon, deviation, radius)
+    res = _to_np(get_engine().vorticity(uu, vv, lat, lon, cyclic=cyclic, deviation=deviation, radius=radius)["omega"])
+    coords = {"latitude": lat, "longitude": lon}
+    if lead:
+        coords[lead[0]] = _coord(u, lead[0])
+    return _make(u, res if lead else res[0], order, coords, "vorticity")
 
 
 def Inverse_weighted_interpolation(x, y, z, xi, yi, power=2):
