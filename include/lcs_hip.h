@@ -772,6 +772,65 @@ typedef struct lc_lavd_args {
 int lc_lavd_update(lc_ctx *ctx, const lc_lavd_args *args);
 const char *lc_ctx_last_lavd_kernel(const lc_ctx *ctx);
 
+/* ---- footprints: trajectory entries binned into residence-time maps (Engine.footprint_update, Engine.footprint,
+ * LCS.footprint, tools.trajectory_density) ----
+ * No counterpart in the reference.  Where the other folds write one value per parcel back on the seed grid, this one scatters
+ * every (parcel, level) entry of a block of trajectory levels into the cell of a target grid it lies in.  Every output is a sum
+ * of 64-bit integers, so the result does not depend on launch shape, kernel form, the split into blocks or the run.
+ *   traj_x, traj_y   [n_levels][n] dtype elements, degrees, n = ny nx: the layout lc_lavd_update takes
+ *   c           the same shape or NULL: the value sampled at the same entries (lc_tracer_sample's c1_out)
+ *   q           int32 [n] or NULL (all 1): the parcel's integer weight, 0 <= q <= 2^20 (the caller's guarantee, with
+ *               n levels 2^21 < 2^63 over a record).  A parcel with q == 0 contributes nothing anywhere, stats included: the
+ *               receptor mask
+ *   ny, nx      the seed grid's shape (a workgroup owns a patch of neighbouring seeds); ny = 1 for an unstructured list
+ *   entries     entry 0 of a continued block (level0 > 0) is the last entry of the block before and is skipped.  An entry's
+ *               half-weight h is 1 for the record's first entry (entry 0 of a block with level0 == 0) and for its last (the
+ *               last entry of a block with final), 2 otherwise: hits |timestep| / 2 is the trapezoid rule in time, in integers
+ *   cell        in float64 without contraction, the position widened first whatever the dtype:
+ *               fy = ((double)y - lat0) inv_dy + 0.5 with inv_dy = (ny_t - 1) / (lat1 - lat0) formed once on the host in
+ *               double, fx likewise; lat0, lat1, lon0, lon1 are the centres of the first and last target cell.  The row is
+ *               floor(fy), valid when 0 <= fy < ny_t; the column floor(fx), valid when 0 <= fx < nx_t, or with cyclic_x
+ *               floor(fx) reduced by floored modulo nx_t, valid when |fx| < 2^31.  Every comparison is made on the doubles
+ *               before any conversion: NaN, +-inf and 1e30 are simply not valid.  A position exactly on a cell edge goes to
+ *               the upper cell
+ *   sums        for a valid entry of a parcel with q > 0: hits[cell] += h, mass[cell] += h q and, with c, v = rint((double)c
+ *               c_scale) (ties to even): csum[cell] += h v and chits[cell] += h when v is finite and |v| <= 2^31, else
+ *               stats[1] += h.  For an invalid entry stats[0] += h.  stats[2] and stats[3] are written as 0 with zero_first
+ *               and otherwise left alone (but see the census form below).  Over a whole record
+ *               sum(hits) + stats[0] == 2 (levels - 1) #{q > 0}
+ *   zero_first  hits, mass, csum, chits (those given) and stats are cleared on the context's stream before the launch
+ *   outputs     hits, mass, csum, chits: each int64 [ny_t nx_t] or NULL, at least one non-NULL; csum and chits both or neither,
+ *               and only with c.  stats: int64 [4], required
+ * Refused with LC_EINVAL before any HIP call: a null context or argument structure, a wrong struct_size, a bad dtype, n < 1,
+ * ny nx != n, n_levels < 2, level0 < 0, a target grid with fewer than 2 cells a side or with ends that are not finite and
+ * ascending, c without a positive finite c_scale, csum or chits without c or only one of the two, no output at all, a null
+ * traj_x, traj_y or stats.
+ * Two kernel forms give the same integers.  "footprint_direct_kernel<T, HAS_C>": one thread per parcel, one 64-bit global
+ * atomic per sum and entry.  "footprint_tile_kernel<T, HAS_C>": a workgroup owns a patch of 8 x 64 neighbouring seeds, sums
+ * into a window of 32 x 64 target cells held in LDS -- anchored anew every 4 levels at the cell of the counted parcel nearest
+ * the patch's centre -- and flushes the window's non-zero cells with one global atomic each; an entry outside the window goes
+ * straight to global atomics, so the window never decides a result.  lc_ctx_set_footprint_form: -1 auto (the default: the rule
+ * is in footprint.hip, from the measurements in DESIGN.md), 0 direct, 1 tiled, 2 tiled with a census -- stats[2] += h for every
+ * valid entry that left the window, a measuring aid outside the contract above; any other mode is refused.
+ * lc_ctx_last_footprint_kernel: the kernel the context's last lc_footprint_update launched, T float or double, HAS_C true or
+ * false; "" before any call or for a null context. */
+typedef struct lc_footprint_args {
+    size_t struct_size; /* sizeof(lc_footprint_args): checked before any other field */
+    const void *traj_x, *traj_y, *c;
+    const int32_t *q;
+    int dtype, ny, nx, n, n_levels, level0, final;
+    int ny_t, nx_t;
+    double lat0, lat1, lon0, lon1;
+    int cyclic_x;
+    double c_scale;
+    int zero_first;
+    int64_t *hits, *mass, *csum, *chits;
+    int64_t *stats;
+} lc_footprint_args;
+int lc_footprint_update(lc_ctx *ctx, const lc_footprint_args *args);
+const char *lc_ctx_last_footprint_kernel(const lc_ctx *ctx);
+int lc_ctx_set_footprint_form(lc_ctx *ctx, int mode);
+
 /* The 9-component "def_tensor" itself, for callers of LCS.flowmap_gradient
  * (LCS/LCS.py:171-225): planes dXdx,dXdy,dYdx,dYdy,dZdx,dZdy,dXdr,dYdr,dZdr (the last
  * three all zero, LCS.py:206-208), each [ny*nx], whole grid on one device. */

@@ -405,6 +405,27 @@ class LavdArgs(C.Structure):
 PROTOTYPES["lc_lavd_update"] = (_i, [_vp, C.POINTER(LavdArgs)])
 PROTOTYPES["lc_ctx_last_lavd_kernel"] = (C.c_char_p, [_vp])
 
+
+class FootprintArgs(C.Structure):
+    """``lc_footprint_args`` of include/lcs_hip.h, field for field."""
+    _fields_ = [("struct_size", _sz),
+                ("traj_x", _vp), ("traj_y", _vp), ("c", _vp),
+                ("q", _vp),
+                ("dtype", _i), ("ny", _i), ("nx", _i), ("n", _i), ("n_levels", _i), ("level0", _i), ("final", _i),
+                ("ny_t", _i), ("nx_t", _i),
+                ("lat0", C.c_double), ("lat1", C.c_double), ("lon0", C.c_double), ("lon1", C.c_double),
+                ("cyclic_x", _i),
+                ("c_scale", C.c_double),
+                ("zero_first", _i),
+                ("hits", _vp), ("mass", _vp), ("csum", _vp), ("chits", _vp),
+                ("stats", _vp)]
+
+
+LC_FOOTPRINT_AUTO, LC_FOOTPRINT_DIRECT, LC_FOOTPRINT_TILED, LC_FOOTPRINT_TILED_CENSUS = -1, 0, 1, 2
+PROTOTYPES["lc_footprint_update"] = (_i, [_vp, C.POINTER(FootprintArgs)])
+PROTOTYPES["lc_ctx_last_footprint_kernel"] = (C.c_char_p, [_vp])
+PROTOTYPES["lc_ctx_set_footprint_form"] = (_i, [_vp, _i])
+
 _lib = None
 
 

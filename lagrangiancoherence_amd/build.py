@@ -15,7 +15,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "liblcs_hip.so")
-SOURCES = ["api.hip", "pack.hip", "advect.hip", "sigma.hip", "strain.hip", "aux_gradient.hip", "fsle.hip", "vorticity.hip", "lavd.hip", "ridges.hip", "ridges_batch.hip", "components.hip", "tracks.hip", "distance.hip", "sphere_distance.hip", "idw.hip", "transects.hip", "morphology.hip", "lines.hip", "threshold.hip", "halo.hip", "preprocess.hip"]
+SOURCES = ["api.hip", "pack.hip", "advect.hip", "sigma.hip", "strain.hip", "aux_gradient.hip", "fsle.hip", "vorticity.hip", "lavd.hip", "footprint.hip", "ridges.hip", "ridges_batch.hip", "components.hip", "tracks.hip", "distance.hip", "sphere_distance.hip", "idw.hip", "transects.hip", "morphology.hip", "lines.hip", "threshold.hip", "halo.hip", "preprocess.hip"]
 ARCH = "gfx950"
 
 

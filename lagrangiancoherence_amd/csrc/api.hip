@@ -103,6 +103,8 @@ extern "C" int lc_ctx_create(int device, lc_ctx **out) {
     c->last_fsle_kernel = "";
     c->last_vorticity_kernel = "";
     c->last_lavd_kernel = "";
+    c->last_footprint_kernel = "";
+    c->footprint_form = -1;
     c->last_ridges_kernel = "";
     c->last_threshold_kernel = "";
     c->last_idw_kernel = "";

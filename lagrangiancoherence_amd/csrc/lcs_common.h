@@ -71,6 +71,8 @@ struct lc_ctx {
     const char *last_fsle_kernel;  // what the last lc_fsle_update launched (lc_ctx_last_fsle_kernel)
     const char *last_vorticity_kernel;  // what the last lc_vorticity launched (lc_ctx_last_vorticity_kernel)
     const char *last_lavd_kernel;  // what the last lc_lavd_update launched (lc_ctx_last_lavd_kernel)
+    const char *last_footprint_kernel;  // what the last lc_footprint_update launched (lc_ctx_last_footprint_kernel)
+    int footprint_form;         // lc_footprint_update's kernel form: -1 auto (default), 0 direct, 1 tiled, 2 tiled with the window census (lc_ctx_set_footprint_form)
     lc_pending_pack pend;       // the context's one pending pack (pack.hip)
     int defer_pack;             // lc_field_pack_deferred defers (1, default) or packs the whole series at once as lc_field_pack does (0; LCS_DEFER_PACK at creation / lc_ctx_set_deferred_pack)
     int pack_share, pack_period_shift, pack_item_levels;  // a launch that carries a pack: pack workgroups (8 / 16 / 24) in every 2^shift blocks (32 .. 16384; shift 0, the default: by the pack's size), levels per item of theirs (2 / 4 / 8): lc_ctx_set_deferred_pack_mix

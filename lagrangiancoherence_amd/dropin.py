@@ -643,6 +643,135 @@ class LCS:
                     self._windows_out(rec, forward, stack("y_dep"), crop=False))
         return out
 
+    def footprint(self, ds=None, u=None, v=None, receptors=None, weights='area', C=None, grid=None, window=None, stride=1, verbose=True,
+                  s=None, resample=None, s_is_error=False, isglobal=False, interp_to_common_grid=True, traj_interp_order=3, truncation=20,
+                  level_chunk=16):
+        """Where the air that arrives at the output points has been: ``(residence, carried)``, each with dims ``(timedim, latitude,
+        longitude)`` on the target grid.
+
+        Every other call form writes what happened to a parcel back on the seed grid; this one bins the trajectories themselves.
+        ``residence`` is the time the parcels spent over each cell of the target grid (trapezoid rule over the time levels),
+        weighted: ``weights='area'`` weights each parcel by the area of its seed cell, ``R^2 cos(lat) dlat dlon`` (m^2 s: the
+        footprint does not depend on how finely the receptors are seeded), ``None`` by 1 (seconds), an array on the seed grid
+        by the caller's numbers (non-negative; NaN and 0 leave the parcel out).  ``receptors``: a mask on the seed grid -- a
+        ridge mask straight from ``find_ridges_spherical_hessian`` or ``filter_ridges``: ``!= 0`` and not NaN counts -- of the
+        parcels to follow; None: all of them (those of ``subdomain``, where one is set).  ``C``: a scalar on the wind's grid and
+        time levels (the ``C=`` of ``parcel_propagation``); ``carried`` is its mean over the visits to each cell, NaN where there
+        were none; None without ``C``.  ``grid=(lat, lon)``: the centres of the target cells, uniform and ascending; default
+        the wind's grid after the intake, its columns wrapping where ``isglobal`` and the longitudes close the circle.
+
+        The attrs carry ``integration_time`` (seconds), ``outside_fraction`` (the share of the visits that fell outside the
+        target grid) and ``dropped_values`` (visits whose value was not finite).  ``window`` / ``stride``, the intake, the one
+        pack and the time labels are :meth:`lavd`'s; the direction of integration is the sign of ``timestep`` (negative: where
+        the air came from).  With ``return_dpts`` ``x_dep`` and ``y_dep`` are appended.  Not with ``aux_grid``.  The full
+        definition: INTEGRATION.md "Footprints: where the air came from"."""
+        if self.aux_grid is not None:
+            raise ValueError("footprint: the trajectories of the auxiliary parcels are not binned; use an LCS without aux_grid")
+        if not self.timestep or not np.isfinite(self.timestep):
+            raise ValueError(f"timestep {self.timestep!r}: footprint needs a non-zero finite step")
+        if isinstance(level_chunk, bool) or int(level_chunk) != level_chunk or int(level_chunk) < 1:
+            raise ValueError(f"footprint: level_chunk {level_chunk!r} (at least 1)")
+        if isinstance(weights, str) and weights != "area":
+            raise ValueError(f"footprint: weights {weights!r} ('area', None or an array on the seed grid)")
+        if grid is not None:
+            if not isinstance(grid, (tuple, list)) or len(grid) != 2:
+                raise ValueError("footprint: grid is (lat, lon), the centres of the target cells")
+            grid = tuple(np.asarray(getattr(g, "values", g), dtype=np.float64) for g in grid)
+            Engine.checked_footprint_grid(grid[0], grid[1], False)
+        verboseprint = print if verbose else (lambda *a, **k: None)
+        rec = self._record_intake(ds, u, v, window, stride, resample, isglobal, interp_to_common_grid, truncation, verbose)
+        glat, glon = grid if grid is not None else (np.asarray(rec.lat, dtype=np.float64), np.asarray(rec.lon, dtype=np.float64))
+        mask = self._seed_mask(receptors, rec)
+        if isinstance(weights, str):
+            w = Engine.seed_cell_areas(rec.lat, rec.lon, self.earth_r)
+        elif weights is not None:
+            w = np.asarray(getattr(weights, "values", weights), dtype=np.float64)
+            if w.shape != mask.shape:
+                raise ValueError(f"footprint: weights of shape {w.shape} on a seed grid of {mask.shape}")
+        else:
+            w = None if mask.all() else np.ones(mask.shape)
+        if w is not None:
+            w = np.where(mask, w, 0.0)
+            Engine.footprint_weights(w, mask.shape)                            # its refusals, before any device work
+        eng = get_engine()
+        dtype = common_dtype(rec.uu, rec.vv, rec.lat, rec.lon)
+        tracer = None
+        if C is not None:
+            c = self._tracer_on_record(eng, C, rec, resample, isglobal, interp_to_common_grid)
+            tracer = eng.prepare_tracer(c, None, rec.lat, rec.lon, traj_interp_order, dtype=dtype)
+        verboseprint(f"*---- Parcel propagation and footprints: {rec.n_windows} window(s) ----*")
+        field, lat_t, lon_t = self._packed_record(eng, rec, traj_interp_order)
+        res = [eng.footprint(field, lat_t, lon_t, rec.timestep, glat, glon, weights=w, tracer=tracer, t0=k * rec.wstep, nsteps=rec.wlen - 1,
+                             level_chunk=int(level_chunk), SETTLS_order=self.SETTLS_order, interp_order=traj_interp_order,
+                             cyclic_xboundary=rec.cyclic_xboundary) for k in range(rec.n_windows)]
+        verboseprint("*---- Done footprints ----*")
+
+        forward = np.sign(rec.timestep) == 1
+        stats = np.sum([_to_np(r["acc"]["stats"]) for r in res], axis=0)
+        hits = int(sum(int(r["acc"]["hits"].sum()) for r in res))
+        attrs = {"integration_time": (rec.wlen - 1) * abs(float(rec.timestep)),
+                 "outside_fraction": float(stats[0]) / float(hits + int(stats[0])) if hits + int(stats[0]) else 0.0,
+                 "dropped_values": int(stats[1])}
+        target = rec._replace(lat=glat, lon=glon)
+        stack = lambda k: np.stack([r[k] if isinstance(r[k], np.ndarray) else _to_np(r[k]) for r in res], axis=0)
+        residence = _with_attrs(self._windows_out(target, forward, stack("residence" if weights is None else "mass"), "residence", crop=False), attrs)
+        carried = None if tracer is None else _with_attrs(self._windows_out(target, forward, stack("mean_value"), getattr(C, "name", None) or "carried",
+                                                                            crop=False), attrs)
+        out = (residence, carried)
+        if self.return_dpts:                                               # LCS.py:161-168
+            out += (self._windows_out(rec, forward, stack("x_dep"), crop=False),
+                    self._windows_out(rec, forward, stack("y_dep"), crop=False))
+        return out
+
+    def _seed_mask(self, receptors, rec: _Record):
+        """The parcels :meth:`footprint` follows, as a boolean mask on the whole seed grid: those of ``subdomain`` (strictly
+        inside, as the other call forms crop) that ``receptors`` marks -- a labelled ``(latitude, longitude)`` mask on the seed
+        grid's coordinates or on a part of them (a cropped result), or a plain array of the whole or the cropped grid's shape;
+        ``!= 0`` and not NaN counts."""
+        ny, nx = rec.lat.size, rec.lon.size
+        mlat, mlon = np.ones(ny, bool), np.ones(nx, bool)
+        if isinstance(self.subdomain, dict):
+            mlat, mlon = _crop_strict(rec.lat, rec.lon, self.subdomain)
+        inside = mlat[:, None] & mlon[None, :]
+        if receptors is None:
+            return inside
+        if hasattr(receptors, "dims"):
+            if set(receptors.dims) != {"latitude", "longitude"}:
+                raise ValueError(f"footprint: receptors with dims {tuple(receptors.dims)}: a (latitude, longitude) mask (one plane of a series)")
+            vals = np.asarray(receptors.transpose("latitude", "longitude").values)
+            la, lo = _coord(receptors, "latitude"), _coord(receptors, "longitude")
+            i = np.clip(np.searchsorted(rec.lat, la), 0, ny - 1)
+            j = np.clip(np.searchsorted(rec.lon, lo), 0, nx - 1)
+            if not (np.array_equal(rec.lat[i], la) and np.array_equal(rec.lon[j], lo)):
+                raise ValueError("footprint: the receptors' coordinates are not those of the seed grid")
+        else:
+            vals = np.asarray(receptors)
+            if vals.shape == (ny, nx):
+                i, j = np.arange(ny), np.arange(nx)
+            elif vals.shape == (int(mlat.sum()), int(mlon.sum())):
+                i, j = np.nonzero(mlat)[0], np.nonzero(mlon)[0]
+            else:
+                raise ValueError(f"footprint: receptors of shape {vals.shape} on a seed grid of {(ny, nx)}")
+        vals = vals.astype(np.float64)
+        full = np.zeros((ny, nx), bool)
+        full[np.ix_(i, j)] = (vals != 0) & ~np.isnan(vals)
+        return inside & full
+
+    def _tracer_on_record(self, eng, C, rec: _Record, resample, isglobal, interp_to_common_grid):
+        """``C`` as ``(time, latitude, longitude)`` values on the record the engine advects on: resampled and sorted as the wind
+        was and, where the wind was regridded, regridded (never truncated)."""
+        if set(C.dims) != {"latitude", "longitude", self.timedim}:
+            raise ValueError(f"footprint: C with dims {tuple(C.dims)}: the wind's dims")
+        if isinstance(resample, str):
+            C = C.resample({self.timedim: resample}).interpolate('linear') if _is_xarray(C) else _resample_linear(C, self.timedim, resample)
+        c, time, lat, lon = _sorted_tll(C, self.timedim)
+        if isglobal and interp_to_common_grid:
+            from . import preprocess
+            c, lat, lon = preprocess.regrid_common_grid(eng, c, lat, lon)
+        if not (np.array_equal(time, rec.time) and np.array_equal(lat, rec.lat) and np.array_equal(lon, rec.lon)):
+            raise ValueError("footprint: C's coordinates differ from the wind's")
+        return c
+
 
 def _with_attrs(a, attrs):
     """``a`` with ``attrs`` added to its ``attrs`` mapping (a labelled-array class without one is given one)."""

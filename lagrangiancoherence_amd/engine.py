@@ -3041,6 +3041,283 @@ class Engine:
             del tx, ty, c
         return {"lavd": res["lavd"], "rotation": res["rotation"], "length": res["length"], "x_dep": x, "y_dep": y}
 
+    # ------------------------------------------------------------------ footprints: residence-time maps of trajectories
+    FOOTPRINT_Q_MAX = 1 << 20       # a parcel's integer weight: 0 .. 2^20 (lc_footprint_update)
+    FOOTPRINT_PLANES = ("hits", "mass", "csum", "chits")
+    _FOOTPRINT_FORMS = {"auto": _capi.LC_FOOTPRINT_AUTO, "direct": _capi.LC_FOOTPRINT_DIRECT, "tiled": _capi.LC_FOOTPRINT_TILED,
+                        "census": _capi.LC_FOOTPRINT_TILED_CENSUS}
+
+    def last_footprint_kernel(self) -> str:
+        """Name of the kernel the last :meth:`footprint_update` call launched (``lc_ctx_last_footprint_kernel``)."""
+        return self.lib.lc_ctx_last_footprint_kernel(self.ctx).decode()
+
+    def set_footprint_form(self, mode=-1):
+        """Which kernel :meth:`footprint_update` launches (``lc_ctx_set_footprint_form``): ``-1`` / ``'auto'`` (the default: the
+        library's rule), ``0`` / ``'direct'`` (one thread per parcel, global atomics), ``1`` / ``'tiled'`` (a workgroup sums its
+        patch of seeds in an LDS window first), ``2`` / ``'census'`` (tiled; ``stats[2]`` also counts, in half-weights, the valid
+        entries that left the window: a measuring aid).  Every form gives the same integers."""
+        mode = self._FOOTPRINT_FORMS.get(mode, mode) if isinstance(mode, str) else mode
+        if isinstance(mode, bool) or not isinstance(mode, (int, np.integer)) or int(mode) not in (-1, 0, 1, 2):
+            raise ValueError(f"footprint form {mode!r}: -1 / 'auto', 0 / 'direct', 1 / 'tiled' or 2 / 'census'")
+        _capi.check(self.lib.lc_ctx_set_footprint_form(self.ctx, int(mode)), self.lib)
+
+    @classmethod
+    def checked_footprint_grid(cls, lat, lon, cyclic=False):
+        """``(ny_t, nx_t, lat0, lat1, lon0, lon1)`` of a footprint's target grid as :meth:`footprint_update` hands it to the
+        library, or ``ValueError``: ``lat`` and ``lon`` are the cell centres in degrees, one-dimensional, at least two each,
+        finite, strictly ascending and uniformly spaced, ``|lat| <= 90``; with ``cyclic`` the longitudes span 360 degrees minus
+        one spacing, so that the cell after the last one is the first.  numpy on the host; no device is touched."""
+        try:
+            lat, lon = np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("footprint grid: lat and lon must be numbers") from None
+        if lat.ndim != 1 or lon.ndim != 1 or lat.size < 2 or lon.size < 2:
+            raise ValueError("footprint grid: lat and lon: one-dimensional, at least two values each")
+        if not (np.isfinite(lat).all() and np.isfinite(lon).all()):
+            raise ValueError("footprint grid: lat and lon: finite degrees")
+        if np.abs(lat).max() > 90.0:
+            raise ValueError(f"footprint grid: lat: within [-90, 90] degrees, got {lat.min()!r} .. {lat.max()!r}")
+        for c, what in ((lat, "lat"), (lon, "lon")):
+            d = np.diff(c)
+            if not (d > 0).all():
+                raise ValueError(f"footprint grid: {what}: strictly ascending (sort first)")
+            if np.max(np.abs(d - d.mean())) > cls.GRID_UNIFORM_RTOL * d.mean():
+                raise ValueError(f"footprint grid: {what}: uniformly spaced (regrid first)")
+        if cyclic:
+            step = (lon[-1] - lon[0]) / (lon.size - 1)
+            gap = lon[0] + 360.0 - lon[-1]
+            if abs(gap - step) > cls.GRID_UNIFORM_RTOL * step:
+                raise ValueError(f"footprint grid: lon: with cyclic the axis must close after one more step: lon[0] + 360 - lon[-1] = "
+                                 f"{gap!r} against a spacing of {step!r}")
+        if lat.size * lon.size >= 1 << 31:
+            raise ValueError(f"footprint grid: {lat.size} x {lon.size} cells (fewer than 2^31)")
+        return int(lat.size), int(lon.size), float(lat[0]), float(lat[-1]), float(lon[0]), float(lon[-1])
+
+    @staticmethod
+    def seed_cell_areas(lat, lon, radius=6371000.0):
+        """``R^2 cos(lat) dlat dlon`` of every cell of a uniform seed grid, ``(ny, nx)`` float64 in the square of ``radius``'s
+        unit: the ``weights='area'`` of ``LCS.footprint``.  ``dlat`` and ``dlon`` are the mean spacings in radians (1 degree for
+        an axis of one point); the cosine is clipped at 0."""
+        lat, lon = np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64)
+        k = np.pi / 180.0
+        dlat = (lat[-1] - lat[0]) / (lat.size - 1) * k if lat.size > 1 else k
+        dlon = (lon[-1] - lon[0]) / (lon.size - 1) * k if lon.size > 1 else k
+        return np.repeat((float(radius) ** 2 * np.maximum(np.cos(lat * k), 0.0) * (dlat * dlon))[:, None], lon.size, axis=1)
+
+    @classmethod
+    def footprint_weights(cls, weights, shape):
+        """``(q, wscale)``: parcel weights quantised once, on the host, for :meth:`footprint_update`.  ``weights``: non-negative
+        numbers of the seed grid's ``shape``; NaN and 0 exclude the parcel; a negative or infinite weight is refused.  ``q =
+        rint(w / max(w) 2^20)`` as int32 and ``wscale = max(w) / 2^20``, so that ``q wscale`` is the weight to within 2^-21 of the
+        largest (a weight below that is 0: the parcel is left out).  None: ``(None, 1.0)``, every parcel counts once."""
+        if weights is None:
+            return None, 1.0
+        try:
+            w = np.array(weights, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("footprint: weights must be numbers") from None
+        if w.shape != tuple(shape):
+            raise ValueError(f"footprint: weights of shape {w.shape} for seeds of shape {tuple(shape)}")
+        w[np.isnan(w)] = 0.0
+        if np.isinf(w).any() or (w < 0).any():
+            raise ValueError("footprint: weights must be finite and not negative (NaN and 0 exclude a parcel)")
+        top = float(w.max()) if w.size else 0.0
+        if top == 0.0:
+            return np.zeros(w.shape, np.int32), 0.0
+        return np.rint(w / top * cls.FOOTPRINT_Q_MAX).astype(np.int32), top / cls.FOOTPRINT_Q_MAX
+
+    def footprint_update(self, traj_x, traj_y, grid_lat, grid_lon, level0, final, q=None, c=None, c_scale=None, acc=None, cyclic=False,
+                         want=("hits", "mass")) -> dict:
+        """One block of trajectory levels binned into the cells of a target grid (``lc_footprint_update``; the definition is in
+        include/lcs_hip.h and restated in tests/footprint.py).  ``traj_x``, ``traj_y``: ``(n_levels, ...)`` positions in degrees
+        after ``level0``, ``level0 + 1``, ... steps, ``n_levels >= 2``; entry 0 of a continued block (``level0 > 0``) is the last
+        entry of the block before and is skipped; ``final`` marks the block that ends the record.  ``grid_lat``, ``grid_lon``:
+        the centres of the target cells (:meth:`checked_footprint_grid`; ``cyclic``: the columns wrap).  ``q``: integer weights
+        ``0 .. 2^20`` of the seeds' shape (:meth:`footprint_weights`), 0 leaving a parcel out altogether; None: all 1.  ``c``:
+        values sampled at the same entries (:meth:`sample_tracer`), binned as ``rint(c c_scale)``.
+
+        Returns the accumulators ``{'hits', 'mass', 'csum', 'chits', 'stats'}``: int64 device tensors ``(ny_t, nx_t)`` -- the
+        half-weights, the half-weights times ``q``, times the scaled value, and the half-weights of the entries whose value
+        counted -- those of ``want`` (and, with ``c``, both value planes), None for the rest; ``stats`` ``(4,)``: the half-weights
+        of the entries outside the grid, of the values dropped (not finite, or beyond ``2^31 / c_scale``), 0, 0.  ``acc=None``
+        creates and clears them (only with ``level0 == 0``); given the dict an earlier call returned, the block is added into
+        it.  Every sum is an integer: any split into blocks, either kernel form and any run give the same bits."""
+        ny_t, nx_t, lat0, lat1, lon0, lon1 = self.checked_footprint_grid(grid_lat, grid_lon, cyclic)
+        level0 = int(level0)
+        if level0 < 0:
+            raise ValueError(f"footprint_update: level0 {level0}")
+        shape = tuple(int(s) for s in np.shape(traj_x))
+        if len(shape) < 2 or shape != tuple(int(s) for s in np.shape(traj_y)) or (c is not None and tuple(int(s) for s in np.shape(c)) != shape):
+            raise ValueError("footprint_update: traj_x, traj_y and c must have one shape, (n_levels, ...)")
+        n_levels, n = shape[0], int(np.prod(shape[1:]))
+        if n_levels < 2 or n < 1 or n >= 1 << 31:
+            raise ValueError(f"footprint_update: {n_levels} levels of {n} parcels (at least two levels and one parcel, fewer than 2^31)")
+        if n * (level0 + n_levels) * (2 * self.FOOTPRINT_Q_MAX) >= 1 << 63:
+            raise ValueError(f"footprint_update: {n} parcels over {level0 + n_levels} levels could overflow a 64-bit sum")
+        if acc is None and level0 != 0:
+            raise ValueError("footprint_update: a continued block (level0 > 0) needs the acc of the block before")
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if any(k not in ("hits", "mass") for k in want):
+            raise ValueError(f"footprint_update: want {want!r} (of 'hits' and 'mass'; csum and chits come with c)")
+        planes = [k for k in ("hits", "mass") if k in want] + (["csum", "chits"] if c is not None else [])
+        if not planes:
+            raise ValueError("footprint_update: no output (want is empty and there is no c)")
+        if c is not None:
+            try:
+                c_scale = float(c_scale)
+            except (TypeError, ValueError):
+                raise ValueError(f"footprint_update: c_scale {c_scale!r} (required with c: positive and finite)") from None
+            if not np.isfinite(c_scale) or c_scale <= 0:
+                raise ValueError(f"footprint_update: c_scale {c_scale} (positive and finite)")
+        torch = self.torch
+        if q is not None:
+            if tuple(int(s) for s in np.shape(q)) != shape[1:]:
+                raise ValueError(f"footprint_update: q of shape {tuple(np.shape(q))} for seeds of shape {shape[1:]}")
+            if isinstance(q, torch.Tensor):
+                if q.dtype.is_floating_point or q.dtype == torch.bool:
+                    raise ValueError("footprint_update: q must be integers (Engine.footprint_weights quantises weights)")
+                lo, hi = (int(q.min()), int(q.max()))
+            else:
+                q = np.asarray(q)
+                if q.dtype.kind not in "iu":
+                    raise ValueError("footprint_update: q must be integers (Engine.footprint_weights quantises weights)")
+                lo, hi = int(q.min()), int(q.max())
+            if lo < 0 or hi > self.FOOTPRINT_Q_MAX:
+                raise ValueError(f"footprint_update: q {lo} .. {hi} (0 to 2^20)")
+        on_dev = all(hasattr(a, "data_ptr") for a in (traj_x, traj_y) + (() if c is None else (c,)))
+        dtype = np.dtype(str(traj_x.dtype).replace("torch.", "")) if on_dev else common_dtype(traj_x, traj_y, c)
+        if dtype not in _NP2LC:
+            raise ValueError(f"footprint_update: dtype {dtype} (float32 or float64)")
+        tx, ty = self.to_device(traj_x, dtype), self.to_device(traj_y, dtype)
+        cd = self.to_device(c, dtype) if c is not None else None
+        qd = self.to_device(q, np.int32) if q is not None else None
+        zero_first = acc is None
+        if acc is None:
+            acc = {k: (torch.empty((ny_t, nx_t), dtype=torch.int64, device=self.device) if k in planes else None) for k in self.FOOTPRINT_PLANES}
+            acc["stats"] = torch.empty((4,), dtype=torch.int64, device=self.device)
+        else:
+            if not isinstance(acc, dict) or any(k not in acc for k in self.FOOTPRINT_PLANES + ("stats",)):
+                raise ValueError("footprint_update: acc must be the dict an earlier call returned")
+            for k, want_shape in [(k, (ny_t, nx_t)) for k in planes] + [("stats", (4,))]:
+                t = acc[k]
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != want_shape or t.dtype != torch.int64 or not t.is_contiguous() \
+                        or t.device != self.device:
+                    raise ValueError(f"footprint_update: acc[{k!r}] must be a contiguous {want_shape} int64 tensor on {self.device}")
+        p = lambda t: t.data_ptr() if t is not None else None
+        use = {k: (acc[k] if k in planes else None) for k in self.FOOTPRINT_PLANES}
+        a = _capi.FootprintArgs(struct_size=C.sizeof(_capi.FootprintArgs), traj_x=tx.data_ptr(), traj_y=ty.data_ptr(), c=p(cd), q=p(qd),
+                                dtype=_NP2LC[dtype], ny=n // shape[-1], nx=shape[-1], n=n, n_levels=n_levels, level0=level0,
+                                final=int(bool(final)), ny_t=ny_t, nx_t=nx_t, lat0=lat0, lat1=lat1, lon0=lon0, lon1=lon1,
+                                cyclic_x=int(bool(cyclic)), c_scale=c_scale if c is not None else 0.0, zero_first=int(zero_first),
+                                hits=p(use["hits"]), mass=p(use["mass"]), csum=p(use["csum"]), chits=p(use["chits"]),
+                                stats=acc["stats"].data_ptr())
+        self._use_current_stream()
+        _capi.check(self.lib.lc_footprint_update(self.ctx, C.byref(a)), self.lib)
+        return acc
+
+    def footprint(self, field: PackedField, seed_lat, seed_lon, timestep, grid_lat, grid_lon, weights=None, tracer=None, c_scale=None,
+                  t0=0, nsteps=None, level_chunk=16, SETTLS_order=0, interp_order=1, cyclic_xboundary=True, noncyclic_clamp=None,
+                  into=None) -> dict:
+        """Where the parcels of the seed grid have been over ``nsteps`` steps from level ``t0`` of a packed field: the residence-
+        time map of their trajectories on the target grid ``grid_lat`` x ``grid_lon`` (cell centres; the columns wrap when
+        ``cyclic_xboundary`` and the longitudes close the circle).  ``weights``: ``(ny, nx)`` non-negative parcel weights, NaN
+        and 0 leaving a parcel out (a receptor mask), quantised by :meth:`footprint_weights`; None: every parcel counts once.
+        ``tracer``: a value on the wind's grid and levels (:meth:`prepare_tracer`), sampled along the trajectories as
+        :meth:`lavd` samples and binned as ``rint(c c_scale)``; ``c_scale`` defaults to ``2^30 / max |tracer|``.
+
+        Returns ``'acc'`` -- the integer planes and ``'stats'`` of :meth:`footprint_update`, device tensors -- and, as float64
+        numpy arrays ``(ny_t, nx_t)`` formed on the host from those integers: ``'residence' = hits |timestep| / 2`` (seconds: the trapezoid rule in time), ``'mass' = mass wscale
+        |timestep| / 2`` (weight x seconds), ``'mean_value' = csum / chits / c_scale`` (NaN where ``chits == 0``; None without a
+        tracer); the departure points ``'x_dep'``, ``'y_dep'`` of :meth:`advect`; ``'wscale'``, ``'c_scale'``, ``'half_step'``.
+        ``into``: an earlier result whose integers this window (or receptor set) is added into, for climatologies: the same grid,
+        ``|timestep|``, ``wscale`` and ``c_scale`` (the earlier ``c_scale`` is the default then).
+
+        The record is streamed as :meth:`lavd` streams it, ``level_chunk`` steps at a time; the result does not depend on
+        ``level_chunk``.  ``cyclic_xboundary=False`` with the default ``reference_outer`` clamp takes one block over all levels;
+        ``noncyclic_clamp='pointwise'`` streams."""
+        try:
+            timestep = float(timestep)
+        except (TypeError, ValueError):
+            raise ValueError(f"footprint: timestep {timestep!r}") from None
+        if not np.isfinite(timestep) or timestep == 0:
+            raise ValueError(f"footprint: timestep {timestep} (non-zero and finite)")
+        _check_order(field, interp_order)
+        if tracer is not None:
+            if tracer.dtype != field.dtype:
+                raise ValueError(f"footprint: tracer dtype {tracer.dtype} differs from the field's compute dtype {field.dtype}")
+            if (tracer.nt, tracer.ny_f, tracer.nx_f) != (field.nt, field.ny_f, field.nx_f) or \
+                    (tracer.lat_min, tracer.lat_max, tracer.lon_min, tracer.lon_max) != (field.lat_min, field.lat_max, field.lon_min, field.lon_max):
+                raise ValueError("footprint: the tracer must lie on the wind's grid and time levels")
+            _check_order(tracer, interp_order)
+        t0 = int(t0)
+        nsteps = field.nt - 1 - t0 if nsteps is None else int(nsteps)
+        level_chunk = int(level_chunk)
+        if t0 < 0 or nsteps < 1 or t0 + nsteps > field.nt - 1:
+            raise ValueError(f"footprint: t0 {t0}, nsteps {nsteps} on a record of {field.nt} levels (at least one step, inside the record)")
+        if level_chunk < 1:
+            raise ValueError(f"footprint: level_chunk {level_chunk} (at least 1)")
+        count = lambda a: int(a.numel()) if hasattr(a, "numel") else int(np.size(a))
+        if np.ndim(seed_lat) != 1 or np.ndim(seed_lon) != 1 or count(seed_lat) * count(seed_lon) < 1:
+            raise ValueError("footprint: seed_lat and seed_lon must be 1-D and hold at least one seed each")
+        glat, glon = np.asarray(grid_lat, dtype=np.float64), np.asarray(grid_lon, dtype=np.float64)
+        cyclic = False
+        if cyclic_xboundary and glon.ndim == 1 and glon.size >= 2:
+            step = (glon[-1] - glon[0]) / (glon.size - 1)
+            cyclic = bool(abs((glon[0] + 360.0 - glon[-1]) - step) <= self.GRID_UNIFORM_RTOL * abs(step))
+        grid = self.checked_footprint_grid(glat, glon, cyclic)
+        q, wscale = self.footprint_weights(weights, (count(seed_lat), count(seed_lon)))
+        xmode = x_boundary_mode(cyclic_xboundary, noncyclic_clamp, True)
+        half = abs(timestep) / 2
+        acc = None
+        if into is not None:
+            if not isinstance(into, dict) or "acc" not in into or into.get("grid") != grid + (cyclic,):
+                raise ValueError("footprint: into must be an earlier result on the same target grid")
+            if into["half_step"] != half or into["wscale"] != wscale:
+                raise ValueError(f"footprint: into was built with |timestep| / 2 = {into['half_step']} and wscale {into['wscale']}, this call "
+                                 f"has {half} and {wscale} (normalise the weights to one largest value)")
+            if (tracer is None) != (into["c_scale"] is None):
+                raise ValueError("footprint: into and this call must both have a tracer, or neither")
+            if c_scale is None:
+                c_scale = into["c_scale"]
+            elif float(c_scale) != into["c_scale"]:
+                raise ValueError(f"footprint: c_scale {c_scale} differs from into's {into['c_scale']}")
+            acc = into["acc"]
+        if tracer is not None:
+            if c_scale is None:
+                top = self.torch.nan_to_num(tracer.c1.abs(), nan=0.0, posinf=0.0, neginf=0.0).max().item()
+                c_scale = float(1 << 30) / top if top > 0 else 1.0
+            c_scale = float(c_scale)
+            if not np.isfinite(c_scale) or c_scale <= 0:
+                raise ValueError(f"footprint: c_scale {c_scale} (positive and finite)")
+        else:
+            c_scale = None
+        kw = dict(SETTLS_order=SETTLS_order, interp_order=interp_order, cyclic_xboundary=cyclic_xboundary, noncyclic_clamp=noncyclic_clamp)
+        if xmode == _capi.LC_X_CLAMP_REFERENCE_OUTER:
+            level_chunk = nsteps               # one block: the clamp is decided over the whole grid, level by level, inside one call
+        qd = self.to_device(q, np.int32) if q is not None else None
+        x = y = None
+        for done in range(0, nsteps, level_chunk):
+            n = min(level_chunk, nsteps - done)
+            x, y, tx, ty = self.advect(field, seed_lat, seed_lon, timestep, t0=t0 + done, nsteps=n, return_traj=True,
+                                       start=None if done == 0 else (x, y), out=None if done == 0 else (x, y), **kw)
+            c = None if tracer is None else self.sample_tracer(tracer, tx, ty, level0=t0 + done, interp_order=interp_order)[0][0]
+            acc = self.footprint_update(tx, ty, glat, glon, done, done + n == nsteps, qd, c, c_scale, acc, cyclic)
+            del tx, ty, c
+        return self._footprint_result(acc, grid + (cyclic,), half, wscale, c_scale, x, y)
+
+    def _footprint_result(self, acc, grid, half, wscale, c_scale, x=None, y=None) -> dict:
+        """The float64 maps of :meth:`footprint` from the integers, formed with numpy on the host -- one rounding per operation,
+        in the order written, IEEE division: the same bits wherever it runs (a device division need not round correctly)."""
+        host = lambda k: self.to_host(acc[k]).astype(np.float64)
+        res = {"acc": acc, "grid": grid, "half_step": half, "wscale": wscale, "c_scale": c_scale, "x_dep": x, "y_dep": y}
+        res["residence"] = host("hits") * half if acc["hits"] is not None else None
+        res["mass"] = (host("mass") * wscale) * half if acc["mass"] is not None else None
+        res["mean_value"] = None
+        if acc["csum"] is not None:
+            with np.errstate(invalid="ignore", divide="ignore"):
+                res["mean_value"] = (host("csum") / host("chits")) / c_scale
+        return res
+
     def synchronize(self):
         self.torch.cuda.synchronize(self.device)
 

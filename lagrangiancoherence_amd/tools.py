@@ -51,7 +51,7 @@ from .engine import Engine, common_dtype
 __all__ = ["xr_map_coordinates", "fourth_order_derivative", "derivative_spherical_coords",
            "find_ridges_spherical_hessian", "filter_ridges", "distance_to_ridges", "skeletonize_ridges", "dilate_ridges",
            "threshold_local", "above_local_threshold", "track_ridges", "persistent_ridges", "ridge_properties", "ridge_lines",
-           "ridge_transects", "relative_vorticity",
+           "ridge_transects", "relative_vorticity", "trajectory_density",
            "Inverse_weighted_interpolation", "xr_idx_interp"]
 
 
@@ -885,6 +885,54 @@ def relative_vorticity(u, v, cyclic=False, deviation='none', radius=6371000.0):
     if lead:
         coords[lead[0]] = _coord(u, lead[0])
     return _make(u, res if lead else res[0], order, coords, "vorticity")
+
+
+def trajectory_density(x, y, lat, lon, weights=None, values=None, cyclic=False):
+    """Trajectories the caller already has, binned into a residence map on the device (``Engine.footprint_update``): how long
+    the parcels stayed over each cell of the grid ``lat`` x ``lon`` (cell centres in degrees, uniform and ascending; ``cyclic``:
+    the columns wrap) and what they carried there.  ``x`` and ``y`` are the ``(time, latitude, longitude)`` longitudes and
+    latitudes of ``parcel_propagation(..., return_traj=True)`` -- labelled arrays, or plain arrays with the levels first.
+    ``weights``: non-negative numbers on the seed grid, NaN and 0 leaving a parcel out; None: every parcel counts once.
+    ``values``: what the parcels carry, of ``x``'s shape (``parcel_propagation``'s ``c``).
+
+    Returns ``(residence_count, mean_value)`` on ``(latitude, longitude)`` of the target grid, float64, in ``x``'s class:
+    ``residence_count`` is the trapezoid rule over the levels in units of one step -- the first and the last level count
+    half -- so multiply it by the step for a time; with ``weights`` each visit counts by the parcel's weight (to within 2^-21
+    of the largest).  ``mean_value`` is the mean of ``values`` over the visits to each cell (to within ``max |values|`` 2^-31),
+    NaN where there were none; None without ``values``.  Positions outside the grid, and NaN, are left out."""
+    def levels_first(a, what):
+        if hasattr(a, "dims"):
+            lead = [d for d in a.dims if d not in ("latitude", "longitude")]
+            if len(lead) != 1 or len(a.dims) != 3:
+                raise ValueError(f"{what}: dims (time, latitude, longitude)")
+            a = a.transpose(lead[0], "latitude", "longitude")
+        v = np.asarray(getattr(a, "values", a))
+        return np.ascontiguousarray(v if v.dtype in (np.float32, np.float64) else v.astype(np.float64))
+    tx, ty = levels_first(x, "x"), levels_first(y, "y")
+    if tx.ndim < 2 or tx.shape != ty.shape or tx.shape[0] < 2:
+        raise ValueError("x and y: one shape, (levels, ...), at least two levels")
+    lat, lon = np.asarray(getattr(lat, "values", lat), dtype=np.float64), np.asarray(getattr(lon, "values", lon), dtype=np.float64)
+    Engine.checked_footprint_grid(lat, lon, cyclic)
+    q, wscale = Engine.footprint_weights(getattr(weights, "values", weights), tx.shape[1:])
+    c = c_scale = None
+    if values is not None:
+        c = levels_first(values, "values")
+        if c.shape != tx.shape:
+            raise ValueError("values: the shape of x")
+        top = np.abs(c[np.isfinite(c)]).max() if np.isfinite(c).any() else 0.0
+        c_scale = float(1 << 30) / float(top) if top > 0 else 1.0
+    dtype = common_dtype(tx, ty, c)
+    eng = get_engine()
+    acc = eng.footprint_update(tx.astype(dtype), ty.astype(dtype), lat, lon, 0, True, q, None if c is None else c.astype(dtype), c_scale,
+                               None, cyclic)
+    count = _to_np(acc["hits"]).astype(np.float64) * 0.5 if weights is None else (_to_np(acc["mass"]).astype(np.float64) * wscale) * 0.5
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = None if c is None else (_to_np(acc["csum"]).astype(np.float64) / _to_np(acc["chits"]).astype(np.float64)) / c_scale
+    if not hasattr(x, "dims"):
+        return count, mean
+    coords = {"latitude": lat, "longitude": lon}
+    return (_make(x, count, ("latitude", "longitude"), coords, "residence_count"),
+            None if mean is None else _make(x, mean, ("latitude", "longitude"), coords, getattr(values, "name", None) or "mean_value"))
 
 
 def Inverse_weighted_interpolation(x, y, z, xi, yi, power=2):
